@@ -10,6 +10,9 @@ Darknet-53 once per image, the three heads on B*T MC samples (dropout masks from
 per-box T-reduction + decode, sort + NMS, and (N > 1) ONE RCCL all-gather of the padded box lists.
 Weights are random-init with BN statistics calibrated on the device (no checkpoints, no network).
 
+--dump-outputs DIR writes the host copy of what the last timed step returned (kept rows, kept indices, counts) as DIR/<name>.npy;
+weights, calibration frames and input frames are seeded, so two builds run with the same arguments can be compared output for output.
+
 Prints ONE JSON line on rank 0.  `roofline` follows SURVEY.md section 8(d) for the dominant kernel = the matrix-pipe
 kernel with the most device time in the timed region (`by_kernel` lists all of them):
 
@@ -469,6 +472,25 @@ def time_steps(eng, x, cfg, steps, warmup, first_image=0):
     return dt, acc
 
 
+def dump_arrays(rows, kept, count, budget=64 << 20):
+    """What a caller of the timed path receives from one step, on the host: rows [B,cap,D] (an image's first count[b, 0] rows are
+    its kept boxes), kept [B,cap] (their box indices), count [B,2].  The library leaves the slots past an image's count undefined:
+    they are written as 0 (indices -1), so that two runs compare value for value.  Beyond `budget` bytes a fixed, seeded choice of
+    images is kept (`images` lists them)."""
+    import numpy as np
+    rows, kept, count = rows.cpu().numpy(), kept.cpu().numpy(), count.cpu().numpy()
+    B, cap, D = rows.shape
+    imgs = np.arange(B)
+    per_image = cap * D * 4 + cap * 8 + 2 * 8
+    if B * per_image > budget:
+        imgs = np.sort(np.random.default_rng(0).choice(B, max(1, budget // per_image), replace=False))
+    rows, kept, count = rows[imgs], kept[imgs].astype(np.float64), count[imgs].astype(np.float64)
+    valid = np.arange(cap)[None, :] < count[:, :1]
+    rows[~valid] = 0.0
+    kept[~valid] = -1.0
+    return {"rows": rows, "kept": kept, "count": count, "images": imgs.astype(np.float64)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -498,8 +520,13 @@ def main():
     ap.add_argument("--no-dropout", action="store_true",
                     help="[experiment, not the metric] skip the dropout masks: isolates the epilogue's RNG cost")
     ap.add_argument("--dump-steps", default=None, help="write the per-launch table (layer, variant, M, N, K, ms, TF/s) here")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned (kept rows, kept indices, counts) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
+    import numpy as np
     import torch
     import torch.distributed as dist
     from byolo import synth, dist as bdist
@@ -612,7 +639,7 @@ def main():
     for i in range(args.steps):
         if prof and every > 1:
             eng.set_profiling(2 if i % every == 0 else 0, keep=True)
-        step(args.warmup + i)
+        res = step(args.warmup + i)
     torch.cuda.synchronize()
     if pg:
         dist.barrier()
@@ -622,6 +649,8 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=x.device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    # host copies of the last timed step's outputs, before the steps below reuse its buffers
+    dumped = dump_arrays(*res) if args.dump_outputs and rank == 0 else None
 
     if prof and rank == 0:
         # the timed region is over: read the K steps' records (age K-1 = the first timed step)
@@ -907,6 +936,10 @@ def main():
         line["parity_legs_checked"] = len(checked)
         if failed:
             line["parity_failed"] = failed
+        if dumped is not None:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, a in dumped.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
         print(json.dumps(line))
         parity_exit = 3 if failed else 0
         if args.dump_steps and per_launch:
