@@ -106,6 +106,20 @@ PROTOTYPES = {
     "byolo_loss_workspace_bytes": (_sz, []),
     "byolo_loss": (_i32, [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _sz, _vp]),
     "byolo_format_ecp_json": (_i64, [_i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _P(_cp), _i32, _vp, _sz]),
+    "byolo_trainer_create": (_i32, [_vp, _i32, _P(_vp)]),
+    "byolo_trainer_destroy": (_i32, [_vp]),
+    "byolo_trainer_set_fallback": (_i32, [_vp, _vp]),
+    "byolo_trainer_workspace_bytes": (_i32, [_vp, _i32, _P(_sz)]),
+    "byolo_trainer_step": (_i32, [_vp, _vp, _i32, _u64, _vp, _vp, _vp, _vp, _vp, _f32, _i32, _vp, _vp, _sz, _vp]),
+    "byolo_trainer_num_vars": (_i32, [_vp]),
+    "byolo_trainer_var_info": (_i32, [_vp, _i32, _P(_cp), _P(_i32), _P(_i64)]),
+    "byolo_trainer_get": (_i32, [_vp, _cp, _i32, _vp, _i64]),
+    "byolo_trainer_set": (_i32, [_vp, _cp, _i32, _vp, _i64]),
+    "byolo_trainer_get_step": (_i32, [_vp, _P(_i64)]),
+    "byolo_trainer_set_step": (_i32, [_vp, _i64]),
+    "byolo_trainer_export": (_i32, [_vp, _vp]),
+    "byolo_trainer_taps": (_i32, [_vp, _P(_i32), _i32]),
+    "byolo_trainer_layer_output": (_i32, [_vp, _i32, _vp, _i64, _P(_i64), _vp]),
 }
 
 

@@ -4,6 +4,7 @@ PyTorch-ROCm is used here only as plumbing: device buffers (workspace, outputs),
 stream and torch.distributed.  All compute happens inside libbyolo.so.
 """
 import ctypes
+import weakref
 
 import numpy as np
 
@@ -35,6 +36,7 @@ class Engine:
         self.finalized = False
         self._graph = []                 # the builder calls in order: twin() replays them on a second handle
         self._twin = None
+        self._trainers = weakref.WeakSet()       # byolo.train.HeadTrainer objects bound to this handle (closed before it)
 
     # ---- arithmetic of the convolution stack (include/byolo.h: BYOLO_PREC_*) ----------------------------
     @property
@@ -151,6 +153,11 @@ class Engine:
         if self._twin is not None and self._twin.precision == precision:
             return self._twin
         self.drop_twin()
+        self._twin = self.copy(precision)
+        return self._twin
+
+    def copy(self, precision):
+        """A new finalized handle with this graph, plan and parameters in `precision`, owned by the caller (twin() keeps one)."""
         t = Engine((self.cfg.img_h, self.cfg.img_w, self.cfg.img_c), self.cfg.cls_cnt, self.cfg.drop_prob, self.cfg.max_out,
                    self.cfg.iou_thresh, self.cfg.nms_mode, bool(self.cfg.keep_all_outputs), self.device)
         for name, args in self._graph:
@@ -159,7 +166,6 @@ class Engine:
         t.set_precision(precision)
         t.set_params(self.get_params())
         t.finalize()
-        self._twin = t
         return t
 
     def drop_twin(self):
@@ -168,6 +174,8 @@ class Engine:
             self._twin = None
 
     def close(self):
+        for tr in list(getattr(self, "_trainers", ())):     # a trainer reads its handle: it goes first
+            tr.close()
         self.drop_twin() if getattr(self, "_twin", None) is not None else None
         if getattr(self, "_h", None) and self._h.value:
             lib.byolo_destroy(self._h)

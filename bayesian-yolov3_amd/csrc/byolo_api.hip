@@ -1165,6 +1165,7 @@ static int32_t enqueue_forward(byolo_t* h, const FwdArgs& a, hipStream_t st, boo
     for (size_t si = 0; si < h->steps.size(); ++si) {
         const Step& s = h->steps[si];
         const Layer& l = h->layers[s.layer];
+        if (h->stop_layer >= 0 && s.layer >= h->stop_layer) break;
         if (wait_pending && s.layer >= h->backbone_end) { HIPCHK(h, hipStreamWaitEvent(st, h->ev_convs, 0)); wait_pending = false; }
         if (h->profiling && !backbone_marked && h->backbone_end >= 0 && s.layer >= h->backbone_end) {
             HIPCHK(h, hipEventRecord(h->wslot().ev[1], st)); backbone_marked = true;
@@ -1252,6 +1253,26 @@ static int32_t enqueue_forward(byolo_t* h, const FwdArgs& a, hipStream_t st, boo
         HIPCHK(h, launch_sort_nms(n, st));
     }
     if (h->profiling) { HIPCHK(h, hipEventRecord(h->wslot().ev[4], st)); h->wslot().ev_valid = true; }
+    return BYOLO_OK;
+}
+
+int32_t byolo_run_backbone(byolo_t* h, const float* d_img, int32_t B, void* d_workspace, size_t workspace_bytes, hipStream_t st) {
+    int32_t rc = check_run(h, B, 1, "byolo_trainer_step"); if (rc) return rc;
+    if (h->backbone_end < 0) return fail(h, BYOLO_ERR_STATE, "byolo_trainer_step: the graph has no byolo_mark_backbone_end");
+    make_plan(h, B, 1);
+    if (workspace_bytes < h->plan.total) return fail(h, BYOLO_ERR_NOMEM, "byolo_trainer_step: backbone workspace %zu < %zu", workspace_bytes, h->plan.total);
+    HIPCHK(h, hipSetDevice(h->device));
+    h->last_ws = d_workspace;
+    const FwdArgs a{d_img, B, 1, 0, 0, nullptr, d_workspace, nullptr, nullptr, nullptr, nullptr};
+    h->stop_layer = h->backbone_end;
+    rc = enqueue_forward(h, a, st, false, false);
+    h->stop_layer = -1;
+    if (rc) return rc;
+    if (h->precision == 1) {
+        unsigned f = 0, ly = 0xFFFFFFFFu;
+        rc = read_status(h, st, &f, &ly); if (rc) return rc;
+        if (f) { (void)byolo_clear_status(h, st); return range_error(h, "byolo_trainer_step (backbone)", f, ly); }
+    }
     return BYOLO_OK;
 }
 

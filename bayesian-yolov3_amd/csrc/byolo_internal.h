@@ -195,6 +195,7 @@ struct byolo {
     Plan plan;
     void* last_ws = nullptr;
     int64_t first_image = 0;       // position of a call's first image in the logical batch (dropout stream)
+    int stop_layer = -1;           // >= 0: enqueue_forward stops in front of the first step of this layer (byolo_run_backbone)
     int tshard_t0 = 0, tshard_T = 0;   // byolo_set_tshard: this call's T samples are samples t0 .. t0 + T - 1 of tshard_T per image (0 = off)
     int profiling = 0;             // 0 off, 1 stage events, 2 + one event per conv launch
     // level 2: one entry per kernel launch of the convolution stack in a forward (a Winograd layer
@@ -254,3 +255,7 @@ void decide_loops(byolo_t* h);
 void make_plan(byolo_t* h, int B, int T, bool inject = false);
 int64_t piece_cap(const byolo_t* h, int32_t T);
 int32_t check_run(byolo_t* h, int32_t B, int32_t T, const char* what, bool need_device = true);
+// byolo_api.hip: the convolutions in front of byolo_mark_backbone_end as byolo_forward enqueues them (plan of (B, 1), no dropout,
+// no decode); the tensors the heads read stay live in d_workspace.  Split precision: waits for the stream and returns BYOLO_ERR_RANGE
+// (status cleared) if an activation left the range.  For the head trainer (train_heads.hip).
+int32_t byolo_run_backbone(byolo_t* h, const float* d_img, int32_t B, void* d_workspace, size_t workspace_bytes, hipStream_t st);

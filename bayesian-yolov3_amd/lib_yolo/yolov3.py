@@ -97,8 +97,9 @@ class _Yolo:
         if self._model is not None:
             raise Exception('model can only be initialized once!')
         if training:
-            raise NotImplementedError('training=True (batch-statistics BN, back-propagation, the optimiser) is out of scope; '
-                                      'ground truth with training=False evaluates the loss of the inference graph')
+            raise NotImplementedError('training=True: build the model with training=False and train its detection heads with '
+                                      'byolo.train.HeadTrainer (frozen Darknet-53: batch-statistics BN, back-propagation and Adam on '
+                                      'the device); ground truth with training=False evaluates the loss of the inference graph')
         self._gt = [gt1, gt2, gt3]              # lib_yolo/train.py:35-36: the dataset's encoded ground truth, one dict per layer
 
         self._build_model(inputs, training)
@@ -149,6 +150,7 @@ class _Yolo:
                 outs.append(mb.inputs)
 
         self._model = mb.get_model(self.obj_idx, self.cls_start_idx)
+        self._model.freeze_darknet53 = self._freeze_darknet53     # byolo.train.HeadTrainer refuses False (backbone training)
         self._model.dn_out = dn_out
         self._model.det_net_1_out, self._model.det_net_2_out, self._model.det_net_3_out = outs
 

@@ -455,6 +455,61 @@ BYOLO_API int64_t byolo_format_ecp_json(int32_t kind, const float* h_rows, int32
                                         int32_t implicit_background, const char* const* labels, int32_t n_labels,
                                         char* h_out, size_t cap);
 
+/* ---- head training with a frozen Darknet-53 (lib_yolo/train.py:53-54, :84-88 with 'freeze_darknet53': True, the only setting of
+ * the reference's uncertainty_training.py:30, yolov3_training.py:29, pretraining.py:29; csrc/train_heads.hip).
+ * A trainer is bound to a finalized handle whose graph has byolo_mark_backbone_end and, after it, stride-1 1x1 / 3x3 convolutions
+ * with batch norm, routes, upsamplings and standard / aleatoric detection layers (no T stacking: the Bayesian model with
+ * inference_mode=False).  byolo_trainer_create copies the head variables out of the handle: every convolution kernel, BN gamma /
+ * beta, detection kernel / bias after the marker (its trainable variables, TF creation order), their gradients and Adam slots
+ * (zero), and the heads' moving statistics.  It is host-only (the handle need not be finalized yet); the device copy is made by
+ * the first call that needs it.  The library owns that state until byolo_trainer_destroy; errors are reported on the bound handle
+ * (byolo_last_error(h)).  Lifetime: destroy the trainer BEFORE its handle and its fallback handle -- every call but
+ * byolo_trainer_destroy reads them; byolo_trainer_set_fallback(tr, NULL) unbinds a fallback that is about to go.  aleatoric_loss: the flag of lib_yolo/layers.py:150-153 for every layer.
+ *
+ * byolo_trainer_step = one sess.run([train_step, ...]) on d_img [B,H,W,3] (device):
+ *   backbone  byolo_forward's launches up to the marker on the bound handle, in its precision; if an activation leaves the split-f16
+ *             range the step fails with BYOLO_ERR_RANGE before anything changed -- or, with a fallback handle set
+ *             (byolo_trainer_set_fallback: an fp32 handle of the same graph and weights), runs the backbone there;
+ *   heads     conv -> dropout (rate = cfg.drop_prob, inverted, where the layer has it) -> BN over the batch's B*H*W (biased
+ *             variance, eps 1e-5) -> leaky 0.1; detection conv + bias.  Dropout keeps from byolo_rng.h keyed by (seed + step *
+ *             0x9E3779B97F4A7C15, dropout ordinal), or d_mask_bits laid out as byolo_mask_layout(h, B, 1, ordinal) describes;
+ *   loss      byolo_loss per detection layer on the ground truth of byolo_encode_gt (d_gt_* at prior box 0 of layer 0, N of all
+ *             layers per image), L2 0.0005 * sum(w^2) / 2 over every kernel and detection bias of the HANDLE (the frozen ones
+ *             are a constant); d_losses[6] (device doubles) = total, detection, regularization, loc, obj, cls (pre-update weights);
+ *   backward  gradients of the total loss (L2 term included) with respect to every trainable variable, all in fp32;
+ *   update    unless grads_only: moving mean / variance -= (moving - batch) * (1 - 0.99) with the BESSEL-CORRECTED batch variance
+ *             (TF 1.x fused batch norm), then Adam (b1 0.9, b2 0.999, eps 1e-8, TF1's lr_t = lr sqrt(1 - b2^t) / (1 - b1^t),
+ *             t = step + 1), and the step counter advances.
+ * Everything is enqueued on `stream` (split precision: the step waits once, after the backbone, for the range status).  Results
+ * are deterministic: two steps on the same inputs give the same bits.  d_workspace >= byolo_trainer_workspace_bytes(B); the
+ * last step's activations stay readable in it (byolo_trainer_layer_output).
+ * byolo_trainer_get / _set: host copies of a variable by TF name: slot 0 the value, 1 its gradient of the last step, 2 `<name>/Adam`,
+ * 3 `<name>/Adam_1`; the heads' `.../moving_mean` / `.../moving_variance` in slot 0.  Both synchronise the device.
+ * byolo_trainer_export: every trained variable and moving statistic into `dst` (byolo_set_param by name; dst is then un-finalized:
+ * finalize it to run inference with them).
+ * byolo_trainer_taps: the backbone layers the heads read (returns how many; fills up to cap indices).
+ * byolo_trainer_layer_output: NHWC shape (d_dst NULL) or a device copy of a tap's or head convolution's output of the last step
+ * (detection layers: the raw output, dense). */
+typedef struct byolo_trainer byolo_trainer_t;
+BYOLO_API int32_t byolo_trainer_create(byolo_t* h, int32_t aleatoric_loss, byolo_trainer_t** out);
+BYOLO_API int32_t byolo_trainer_destroy(byolo_trainer_t* tr);
+BYOLO_API int32_t byolo_trainer_set_fallback(byolo_trainer_t* tr, byolo_t* h_f32);
+BYOLO_API int32_t byolo_trainer_workspace_bytes(byolo_trainer_t* tr, int32_t B, size_t* bytes);
+BYOLO_API int32_t byolo_trainer_step(byolo_trainer_t* tr, const float* d_img, int32_t B, uint64_t seed, const uint32_t* d_mask_bits,
+                                     const float* d_gt_loc, const float* d_gt_obj, const int32_t* d_gt_cls, const float* d_gt_ign,
+                                     float lr, int32_t grads_only, double* d_losses, void* d_workspace, size_t workspace_bytes,
+                                     void* stream);
+BYOLO_API int32_t byolo_trainer_num_vars(const byolo_trainer_t* tr);
+BYOLO_API int32_t byolo_trainer_var_info(const byolo_trainer_t* tr, int32_t i, const char** name, int32_t* ndim, int64_t shape[4]);
+BYOLO_API int32_t byolo_trainer_get(byolo_trainer_t* tr, const char* name, int32_t slot, float* h_data, int64_t count);
+BYOLO_API int32_t byolo_trainer_set(byolo_trainer_t* tr, const char* name, int32_t slot, const float* h_data, int64_t count);
+BYOLO_API int32_t byolo_trainer_get_step(const byolo_trainer_t* tr, int64_t* step);
+BYOLO_API int32_t byolo_trainer_set_step(byolo_trainer_t* tr, int64_t step);
+BYOLO_API int32_t byolo_trainer_export(byolo_trainer_t* tr, byolo_t* dst);
+BYOLO_API int32_t byolo_trainer_taps(const byolo_trainer_t* tr, int32_t* layers, int32_t cap);
+BYOLO_API int32_t byolo_trainer_layer_output(byolo_trainer_t* tr, int32_t layer, float* d_dst, int64_t count, int64_t shape[4],
+                                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif
