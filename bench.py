@@ -13,6 +13,12 @@ Weights are random-init with BN statistics calibrated on the device (no checkpoi
 --dump-outputs DIR writes the host copy of what the last timed step returned (kept rows, kept indices, counts) as DIR/<name>.npy;
 weights, calibration frames and input frames are seeded, so two builds run with the same arguments can be compared output for output.
 
+A plain run does what the headline needs and nothing more: build the model, warm up, time the K steps, write the outputs, print the
+line (with `roofline` and `stage_ms_per_step`, read from the timed steps' own records).  --full adds everything that runs after the
+timed region: `fp32_mode`, `other_configs`, `entry_point`, `entry_point_reference_default`, `t_shard_latency_path`, `training_side`,
+`cpu_baseline` with `parity_note` (every parity leg sets `parity_ok`; exit 3 when one fails) and the checksums of one more step.
+--fp32-steps, --no-other-configs, --entry-frames, --no-cpu-baseline and --quick-parity select among these.
+
 Prints ONE JSON line on rank 0.  `roofline` follows SURVEY.md section 8(d) for the dominant kernel = the matrix-pipe
 kernel with the most device time in the timed region (`by_kernel` lists all of them):
 
@@ -522,6 +528,9 @@ def main():
     ap.add_argument("--dump-steps", default=None, help="write the per-launch table (layer, variant, M, N, K, ms, TF/s) here")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="write what the last timed step returned (kept rows, kept indices, counts) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the legs beyond the headline: fp32 mode, other configurations, entry point, "
+                         "T-shard path, training-side kernels, CPU baseline and parity, checksums of one more step")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
@@ -683,13 +692,15 @@ def main():
             for k, v in eng.stage_ms().items():
                 stage[k] += v
         eng.select_profile(0)
-    # per-rank diagnostics for the N > 1 line: which device ran which block of the global batch, and a checksum of the last
-    # step's kept indices (a wrong shard or a rank on the wrong GPU shows up as a duplicate / missing first_image or checksum)
-    last = step(args.warmup + args.steps)
-    torch.cuda.synchronize()
-    g_kept, g_count = last[1], last[2]
-    cs = [int((g_kept[b].to(torch.int64).clamp(min=0) * torch.arange(1, g_kept.shape[1] + 1, device=g_kept.device)).sum().item() % 1000003)
-          for b in range(g_kept.shape[0])]
+    # per-rank diagnostics for the N > 1 line: which device ran which block of the global batch, and (--full) a checksum of one
+    # more step's kept indices (a wrong shard or a rank on the wrong GPU shows up as a duplicate / missing first_image or checksum)
+    cs = None
+    if args.full:
+        last = step(args.warmup + args.steps)
+        torch.cuda.synchronize()
+        g_kept = last[1]
+        cs = [int((g_kept[b].to(torch.int64).clamp(min=0) * torch.arange(1, g_kept.shape[1] + 1, device=g_kept.device)).sum().item() % 1000003)
+              for b in range(g_kept.shape[0])]
     mine = {"rank": rank, "device": "cuda:%d (%s)" % (device, torch.cuda.get_device_name(device)), "first_image": rank * B, "images": B,
             "backend": backend, "nccl_world": nccl_world, "preflight_sum": preflight,
             "host_threads": {"cpu_count": os.cpu_count(), "local_world": int(os.environ.get("LOCAL_WORLD_SIZE", "1") or 1)}}
@@ -707,7 +718,7 @@ def main():
             "metric": "img/s at T=%d MC-dropout, %dx%d" % (T, cfg["H"], cfg["W"]),
             "value": imgs / dt, "unit": "img/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True, "scaling": args.scaling,
-            "ranks": ranks, "kept_checksum_per_image_of_one_more_step": cs,
+            "ranks": ranks,
             "vs_baseline": None, "dtype": "f32" if eng.precision == "f32" else "f32 via split-f16 (hi+lo fp16 pairs, 3 fp16 MFMA products, fp32 accumulate)", "data": "synthetic" + (" [EXPERIMENT: dropout off, invalid]" if args.no_dropout else ""),
             "config": {"workload": "%s: %s %dx%d T=%d, %d images/GPU (global batch %d), "
                                    "class-%s NMS max_out=1000, random-init weights with device-calibrated BN"
@@ -727,6 +738,8 @@ def main():
                                           "arithmetic in this run") if eng.precision == "split" else
                                          "fp32 operands on v_mfma_f32_32x32x2_f32, Winograd F(2x2,3x3) on the large 3x3 layers"},
         }
+        if cs is not None:
+            line["kept_checksum_per_image_of_one_more_step"] = cs
         SPLIT = (4256, 3256, 3128, 3064, 2128, 2064, 1128, 1064, 1032, 140)
         KERNELS = {4256: "conv_igemm_kernel<128,256,1,8,kx3>+fused_tail (split-f16 3x3/stride-1 on shared-tap stages with the following 1x1 convolution / detection head fused in; BYOLO_B2B)",
                    3256: "conv_igemm_kernel<128,256,1,8,kx3> (split-f16 3x3/stride-1 on shared-tap stages, 8 waves; BYOLO_KX3_WIDE)",
@@ -851,9 +864,10 @@ def main():
             line["stage_ms_per_step"] = {k: v / n_prof for k, v in stage.items()}
             if npipe > 1:       # stage events sit on the step's own stream: the first stage includes the wait for the previous step's convolutions
                 line["stage_ms_per_step"]["note"] = "pipelined steps: `backbone` includes waiting for the previous step's convolution stack (byolo_api.hip ev_convs)"
+        # --full only from here on: legs that measure or check something beside the headline figure, each after the timed region.
         # the reference's own arithmetic (float32, lib_yolo/layers.py:550) timed in the SAME run: a second handle in BYOLO_PREC_F32
         # on the same batch, a few steps on one stream after the headline region (the headline engine stays alive: its weights)
-        if world == 1 and args.fp32_steps > 0 and eng.precision != "f32" and not args.batch and args.scaling == "weak":
+        if args.full and world == 1 and args.fp32_steps > 0 and eng.precision != "f32" and not args.batch and args.scaling == "weak":
             try:
                 m32 = build(cfg, device, precision="f32")
                 dt32, acc32 = time_steps(m32.engine, x, cfg, args.fp32_steps, 2)
@@ -874,7 +888,7 @@ def main():
                 del m32
             except Exception as e:
                 line["fp32_mode"] = {"value": None, "error": repr(e)}
-        if world == 1 and not args.no_other_configs and args.config == 4 and not args.batch and args.scaling == "weak":
+        if args.full and world == 1 and not args.no_other_configs and args.config == 4 and not args.batch and args.scaling == "weak":
             line["other_configs"] = {}
             for num, name, orc in ((1, "configs[0]", "f64"), (2, "configs[1]", "f64"), (3, "configs[2]", "f64"), (5, "configs[4]", "f32"),
                                    (6, "reference default frame (inference_epistemic.py:218-221)", False),
@@ -884,7 +898,7 @@ def main():
                     line["other_configs"][name] = other_config_leg(num, device, oracle=orc and not args.no_cpu_baseline and (orc if num != 5 or not args.quick_parity else False))
                 except Exception as e:
                     line["other_configs"][name] = {"img_s": None, "error": repr(e)}
-        if world == 1 and args.entry_frames > 0 and not args.batch and args.scaling == "weak":
+        if args.full and world == 1 and args.entry_frames > 0 and not args.batch and args.scaling == "weak":
             try:
                 line["entry_point"] = entry_point_leg(cfg, device, n_frames=args.entry_frames)
                 line["entry_point"]["vs_value"] = line["entry_point"]["img_s"] / line["value"]
@@ -905,17 +919,17 @@ def main():
                     line["entry_point_reference_default"] = ep6
                 except Exception as e:
                     line["entry_point_reference_default"] = {"img_s": None, "error": repr(e)}
-        if world == 1 and not args.no_other_configs and args.config == 4 and not args.batch and args.scaling == "weak":
+        if args.full and world == 1 and not args.no_other_configs and args.config == 4 and not args.batch and args.scaling == "weak":
             try:
                 line["t_shard_latency_path"] = t_shard_leg(device)
             except Exception as e:
                 line["t_shard_latency_path"] = {"error": repr(e)}
-        if world == 1 and not args.no_other_configs and not args.batch and args.scaling == "weak":
+        if args.full and world == 1 and not args.no_other_configs and not args.batch and args.scaling == "weak":
             try:
                 line["training_side"] = training_side_leg(cfg, device)
             except Exception as e:
                 line["training_side"] = {"error": repr(e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 line["cpu_baseline"], o_rows, o_kept = cpu_baseline(cfg, eng.get_params())
                 eng.set_profiling(0)
@@ -930,7 +944,7 @@ def main():
         legs.update({"other_configs/" + k: v.get("parity") for k, v in (line.get("other_configs") or {}).items() if isinstance(v, dict)})
         failed = sorted(k for k, v in legs.items() if isinstance(v, dict) and v.get("ok") is False)
         checked = sorted(k for k, v in legs.items() if isinstance(v, dict) and v.get("ok") is not None)
-        # null, not true, when no leg ran (--no-cpu-baseline: the A/B scripts under tools/): a build that corrupted its activations
+        # null, not true, when no leg ran (a run without --full, or the A/B scripts under tools/): a build that corrupted its activations
         # read "parity_ok": true through such a run once (profiles/r6_wino_small.md); A/Bs are held to tools/rows_digest.py
         line["parity_ok"] = (not failed) if checked else None
         line["parity_legs_checked"] = len(checked)

@@ -338,13 +338,13 @@ def test_bench_line_two_ranks_with_real_engines_on_one_device():
     """`bench.py --gpus 2` with TWO real engines: the box has one GPU and RCCL refuses two ranks on one device, so both ranks run
     on cuda:0 (BYOLO_DIST_SHARE_DEVICE=1) and the collectives go through gloo (the packed all-gather staged through host memory,
     byolo/dist.py all_gather_flat).  What the line must show: two ranks with DIFFERENT first images of the global batch, the
-    global batch = 2 x the per-rank one, one kept-index checksum per image of the gathered list.  (That the N-rank job computes what
+    global batch = 2 x the per-rank one, one kept-index checksum per image of the gathered list (--full).  (That the N-rank job computes what
     one process computes is tests/test_entry_points.py::test_two_ranks_with_real_engines_write_the_single_process_json -- byte-identical
     files; the benchmark's position-weighted checksums of 1000 kept boxes per image are not comparable across per-call batch sizes:
     other tile / stream-K schedules reorder boxes whose scores differ in the last bit.)"""
     import json
     base = [sys.executable, os.path.join(os.path.dirname(HERE), "bench.py"), "--steps", "2", "--warmup", "1", "--config", "3",
-            "--no-cpu-baseline", "--fp32-steps", "0", "--entry-frames", "0", "--no-other-configs", "--no-profile"]
+            "--full", "--no-cpu-baseline", "--fp32-steps", "0", "--entry-frames", "0", "--no-other-configs", "--no-profile"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", BYOLO_DIST_BACKEND="gloo", BYOLO_DIST_SHARE_DEVICE="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port())] + base[1:] + ["--gpus", "2", "--batch", "2"]

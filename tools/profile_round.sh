@@ -12,7 +12,7 @@ TAG=${1:-round}
 OUT=$PWD/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-BENCH="python $PWD/bench.py --steps 5 --warmup 2 --no-cpu-baseline --fp32-steps 0 --entry-frames 0 --no-other-configs"
+BENCH="python $PWD/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --fp32-steps 0 --entry-frames 0 --no-other-configs"
 ONE="python $PWD/bench.py --steps 1 --warmup 1 --no-profile --no-cpu-baseline --fp32-steps 0 --pipeline 1 --entry-frames 0 --no-other-configs"
 
 cd /tmp

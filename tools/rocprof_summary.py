@@ -32,7 +32,7 @@ def main():
     for n, cnt, tot, avg, mn, mx, vg, ag, sg, lds in rows:
         print("| `%s` | %d | %.3f | %.1f | %.1f | %.1f | %.2f | %s | %s | %s | %s |"
               % (n.split("(")[0], cnt, tot / 1e6, avg / 1e3, mn / 1e3, mx / 1e3, 100.0 * tot / total, vg, ag, sg, lds))
-    # bench.py runs, after the K timed steps, ONE more step (the kept-index checksum of the line) with per-launch recording on: the last
+    # bench.py --full runs, after the K timed steps, ONE more step (the kept-index checksum of the line) with per-launch recording on: the last
     # (K + 1) * L dispatches of the kernel are steps 0 .. K - 1 of the timed region and that extra step.
     L, K, every = a.launches_per_step, a.steps, max(1, a.profile_every)
     d = c.execute("select duration from kernels where name like ? order by start desc limit ?",
