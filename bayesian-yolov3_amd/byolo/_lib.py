@@ -11,6 +11,8 @@ OK, ERR_ARG, ERR_STATE, ERR_HIP, ERR_NOMEM, ERR_RANGE = 0, -1, -2, -3, -4, -5
 DET_STANDARD, DET_ALEATORIC, DET_EPISTEMIC = 0, 1, 2
 NMS_AGNOSTIC, NMS_TWO_CLASS = 0, 1
 NORM_BN, NORM_DROPOUT = 1, 2
+AUG_SATURATION, AUG_BRIGHTNESS, AUG_HUE = 1, 2, 3
+AUG_COLORED_SALT_N_PEPPER, AUG_SALT_N_PEPPER, AUG_GAUSSIAN = 1, 2, 3
 
 
 class ByoloError(RuntimeError):
@@ -32,6 +34,12 @@ class PlanOpts(ctypes.Structure):
         "wino_split_bn", "wino_split_rounds", "winograd", "wino_fused", "stream1x1", "gemm_stream", "ksplit", "streamk",
         "plain_epilogue", "wshift_per_layer", "nms_general", "wino_split_persist")] + [(n, ctypes.c_float) for n in (
         "wino_split_min_gflop", "wino_split_chunk_mb", "wino_min_gflop", "wino_chunk_mb", "wino_min_ratio")]
+
+
+class AugPlan(ctypes.Structure):
+    """include/byolo.h byolo_aug_plan (field for field; tests/test_train_feed_cpu.py compares the two)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("y0", "x0", "ch", "cw", "row0", "rescale", "flip", "blur_k", "color_op", "noise_op")] + \
+               [("color_param", ctypes.c_float), ("noise_param", ctypes.c_float), ("noise_key", ctypes.c_uint64)]
 
 
 _i32, _i64, _f32 = ctypes.c_int32, ctypes.c_int64, ctypes.c_float
@@ -99,6 +107,7 @@ PROTOTYPES = {
     "byolo_finish_tshard": (_i32, [_vp, _vp, _i32, _i32, _vp]),
     "byolo_normalize_u8": (_i32, [_vp, _vp, _i64, _vp, _vp]),
     "byolo_copy_status": (_i32, [_vp, _vp, _vp]),
+    "byolo_augment_batch": (_i32, [_vp, _vp, _i32, _i32, _i32, _i64, _P(AugPlan), _i32, _i32, _vp, _vp]),
     "byolo_png_decode_batch": (_i32, [_P(_vp), _P(_sz), _i32, _i32, _i32, _i32, _vp, _i32, _P(_i32), _P(_i32)]),
     "byolo_feed_records": (_i32, [_P(_i32), _P(_i64), _P(_i64), _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _P(_i32), _P(_i32)]),
     "byolo_encode_gt": (_i32, [_vp, _i32, _P(_i32), _P(ctypes.c_double), _vp, _vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -95,3 +95,30 @@ def adversarial_params(shapes, variant, cls_cnt, kind, seed=7):
         out[scope + "/batch_normalization/gamma"] = gam.astype(np.float32)
         out[scope + "/batch_normalization/beta"] = bet.astype(np.float32)
     return out
+
+
+def training_shards(folder, files, records, H, W, seed=0, cls_cnt=2, prefix='synth'):
+    """A TFRecord training set from a seed: `files` shards of `records` records, each a PNG frame of H x W (smooth gradients plus
+    noise, encoded by Pillow) with 1 - 6 boxes and labels 1 .. cls_cnt (implicit background class).  Returns the file pattern."""
+    import io
+    import os
+    from PIL import Image
+    from lib_yolo.dataset_utils import make_train_example, write_tfrecords
+    os.makedirs(folder, exist_ok=True)
+    yy, xx = np.meshgrid(np.linspace(0, 1, H, dtype=np.float32), np.linspace(0, 1, W, dtype=np.float32), indexing='ij')
+    for f in range(files):
+        payloads = []
+        for r in range(records):
+            g = np.random.default_rng([int(seed), f, r])
+            a = g.random(6, dtype=np.float32)
+            base = np.stack([a[0] * yy + a1 * xx for a1 in a[1:4]], -1)
+            img = np.clip(base * 200 + g.normal(0, 12, (H, W, 3)), 0, 255).astype(np.uint8)
+            buf = io.BytesIO()
+            Image.fromarray(img).save(buf, format='PNG', compress_level=1)
+            n = int(g.integers(1, 7))
+            y0, x0 = g.uniform(0, 0.8, n), g.uniform(0, 0.9, n)
+            boxes = np.stack([y0, x0, np.minimum(y0 + g.uniform(0.05, 0.3, n), 1), np.minimum(x0 + g.uniform(0.02, 0.1, n), 1)], 1)
+            labels = g.integers(1, cls_cnt + 1, n)
+            payloads.append(make_train_example(buf.getvalue(), boxes, labels, '%s_%d_%d.png' % (prefix, f, r)))
+        write_tfrecords(os.path.join(folder, '%s-train-%05d-of-%05d' % (prefix, f, files)), payloads)
+    return os.path.join(folder, '%s-train-*-of-*' % prefix)

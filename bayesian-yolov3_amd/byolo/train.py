@@ -177,6 +177,12 @@ class HeadTrainer:
         losses = self._run(img, boxes, labels, counts, mask_bits, False, seed).cpu().numpy()
         return dict(zip(LOSS_KEYS, (float(v) for v in losses)))
 
+    def losses(self, img, boxes, labels, counts=None, mask_bits=None, seed=None):
+        """The six losses of a step on this batch -- training-mode forward (batch statistics, dropout) -- without any update: no Adam
+        step, no moving-statistics change, the step counter stays (lib_yolo/train.py:68-71, the validation run every 100 steps)."""
+        losses = self._run(img, boxes, labels, counts, mask_bits, True, seed).cpu().numpy()
+        return dict(zip(LOSS_KEYS, (float(v) for v in losses)))
+
     def gradients(self, img, boxes, labels, counts=None, mask_bits=None, seed=None):
         """The same step without the update: ({name: gradient (numpy)}, {backbone layer index: tap (CUDA tensor)},
         {loss name: float}).  The gradients include the L2 term."""

@@ -60,3 +60,22 @@ def load_darknet_weights(net_layers, weightfile):
 
     assert ptr == len(weights)                           # darknet.py:66
     return assigned
+
+
+def write_darknet_weights(net_layers, weightfile, params):
+    """Inverse of load_darknet_weights: the variables `params` ({TF name: array}) of the conv layers in `net_layers` as a Darknet
+    ``.weights`` file (test fixtures and demos: a small file written from seeded values)."""
+    chunks = [np.array([0, 2, 0, 0, 0], dtype=np.int32).tobytes()]
+    for l in net_layers:
+        if 'LeakyRelu' not in l.name:
+            continue
+        scope = '/'.join(l.name.split('/')[:2])
+        if 'detection' in l.name:
+            chunks.append(np.asarray(params[scope + '/conv2d/bias'], np.float32).tobytes())
+        else:
+            for v in ('beta', 'gamma', 'moving_mean', 'moving_variance'):
+                chunks.append(np.asarray(params['{}/batch_normalization/{}'.format(scope, v)], np.float32).tobytes())
+        chunks.append(np.ascontiguousarray(np.asarray(params[scope + '/conv2d/kernel'], np.float32).transpose(3, 2, 0, 1)).tobytes())
+    with open(weightfile, 'wb') as f:
+        for c in chunks:
+            f.write(c)

@@ -29,6 +29,7 @@ import os
 import queue
 import struct
 import threading
+import time
 
 import numpy as np
 
@@ -444,3 +445,362 @@ class TestingDataset:
         finally:
             stop.set()
             th.join(timeout=10)
+
+
+# =============================================================================================================================
+# Training / validation feed -- mirror of make_parse_fn / create_dataset / TrainValDataset (lib_yolo/dataset_utils.py:14-156)
+# =============================================================================================================================
+#
+# Record stream of a split (create_dataset + the shuffle / repeat of TrainValDataset): the files of the glob, shuffled with a
+# buffer of num_shards -> interleave(cycle_length=2, block_length=1) -> shuffle with tf.data's buffer algorithm (fill the buffer,
+# emit a uniform pick, refill) -> the next epoch reshuffles -> repeat.  What is shuffled are record REFERENCES (file, offset,
+# length), not decoded frames: the augmentation draws are keyed by the record's position in its epoch (byolo/augment.py), so
+# the distribution of batches is the same, and a buffer of 2000 decoded 1024 x 1920 frames (about 26 GB) is never held.
+# Shuffles draw from generators keyed by (config['seed'], split, epoch), so a run is reproducible; the stream restarts from its
+# seed when a training run resumes (as the reference's one-shot iterator does).
+#
+# Per batch (TrainValDataset): payloads (cache: True keeps them in host memory after the first read) -> tf.train.Example ->
+# boxes / labels (numpy) and the PNG, decoded on cpu_thread_cnt native threads (byolo_png_decode_batch) into a pinned uint8
+# batch buffer; `prefetch` batches (default: max(2, cpu_thread_cnt / batch_size), at most 16) are prepared ahead.  The consumer
+# copies each image's row band [y0, y0 + ch) to the device on a side stream and runs ONE byolo_augment_batch launch on its own stream after an event, so the crop, resize,
+# flip, blur, colour and noise of the whole batch are one kernel; the next batch's copy is started before the batch is returned.
+_TRAIN_KEYS = ('image/encoded', 'image/object/bbox/ymin', 'image/object/bbox/xmin', 'image/object/bbox/ymax', 'image/object/bbox/xmax',
+               'image/object/class/label')
+
+
+def make_parse_fn(config):
+    """parse_example of lib_yolo/dataset_utils.py:14-53: record payload -> (PNG bytes, boxes [n, 4] float32 as (ymin, xmin, ymax,
+    xmax), labels [n] int32, shifted by -1 when implicit_background_class)."""
+    shift = 1 if config['implicit_background_class'] else 0
+
+    def parse(example):
+        feats = parse_example(example)
+        enc = feats.get('image/encoded')
+        if not enc:
+            raise ValueError('record without image/encoded')
+        cols = [np.asarray(feats.get(k, []), dtype=np.float32) for k in _TRAIN_KEYS[1:5]]
+        n = max(len(c) for c in cols)
+        cols = [np.pad(c, (0, n - len(c))) for c in cols]                  # sparse_tensor_to_dense(default_value=0)
+        boxes = np.stack(cols, axis=1).astype(np.float32) if n else np.zeros((0, 4), np.float32)
+        labels = np.asarray(feats.get('image/object/class/label', []), dtype=np.int64).astype(np.int32) - shift
+        return enc[0], boxes, labels
+
+    return parse
+
+
+def make_train_example(png, boxes, labels, filename=''):
+    """A training record as create_tf_records_citypersons.py writes one: image/encoded, image/height / width, the box
+    coordinates as float lists and the class labels as an int64 list (fixtures / demo shards)."""
+    import struct
+
+    def vi(x):
+        x &= (1 << 64) - 1
+        o = b''
+        while True:
+            b = x & 0x7F
+            x >>= 7
+            o += bytes([b | (0x80 if x else 0)])
+            if not x:
+                return o
+    boxes = np.asarray(boxes, dtype=np.float32).reshape(-1, 4)
+    feats = {'image/encoded': _pb_bytes(1, _pb_bytes(1, png)), 'image/filename': _pb_bytes(1, _pb_bytes(1, filename.encode('utf-8'))),
+             'image/object/class/label': _pb_bytes(3, _pb_bytes(1, b''.join(vi(int(v)) for v in np.asarray(labels).reshape(-1))))}
+    for k, name in enumerate(('ymin', 'xmin', 'ymax', 'xmax')):
+        feats['image/object/bbox/' + name] = _pb_bytes(2, _pb_bytes(1, struct.pack('<%df' % len(boxes), *boxes[:, k])))
+    entries = b''.join(_pb_bytes(1, _pb_bytes(1, n.encode('utf-8')) + _pb_bytes(2, f)) for n, f in feats.items())
+    return _pb_bytes(1, entries)
+
+
+def shuffle_buffer(items, buffer_size, rng):
+    """tf.data shuffle: fill a buffer of buffer_size, emit a uniform pick, refill it from the input."""
+    it = iter(items)
+    buf = []
+    for x in it:
+        buf.append(x)
+        if len(buf) >= max(1, int(buffer_size)):
+            break
+    while buf:
+        i = int(rng.integers(len(buf)))
+        out = buf[i]
+        buf[i] = buf[-1]
+        buf.pop()
+        for x in it:
+            buf.append(x)
+            break
+        yield out
+
+
+class RecordStream:
+    """The record stream of one split (config[dataset_key]): `epoch(e)` = the record references of epoch e in stream order,
+    iterating yields (epoch, position in the epoch, reference) forever (repeat)."""
+
+    def __init__(self, config, dataset_key, split=None):
+        info = config[dataset_key]
+        self.split = split or dataset_key
+        self.seed = int(config.get('seed', 0))
+        self.files = sorted(glob.glob(info['file_pattern']))
+        if not self.files:
+            raise FileNotFoundError('no TFRecord file matches {}'.format(info['file_pattern']))
+        self.num_shards = int(info.get('num_shards', 1))
+        self.buffer_size = int(info.get('shuffle_buffer_size', 1))
+        self.cache = bool(info.get('cache', False))
+        self.verify_crc = info.get('verify_crc', True)
+        self._rf = {}
+        self._recs = {}
+        self._payloads = {}
+
+    def _rng(self, epoch, purpose):
+        from byolo.augment import SPLITS
+        return np.random.default_rng([self.seed & (2 ** 63 - 1), SPLITS[self.split], int(epoch), 0, purpose])
+
+    def records(self, path):
+        if path not in self._recs:
+            self._rf[path] = _RecordFile(path, self.verify_crc)
+            self._recs[path] = [(off, ln) for _, off, ln in self._rf[path]]
+        return self._recs[path]
+
+    def epoch(self, e):
+        files = list(shuffle_buffer(self.files, self.num_shards, self._rng(e, 1)))
+
+        def interleaved():                        # interleave(TFRecordDataset, cycle_length=2, block_length=1)
+            pending, active = list(files), []
+            while pending or active:
+                while len(active) < 2 and pending:
+                    p = pending.pop(0)
+                    active.append(iter([(p, k) for k in range(len(self.records(p)))]))
+                for a in list(active):
+                    try:
+                        yield next(a)
+                    except StopIteration:
+                        active.remove(a)
+        return shuffle_buffer(interleaved(), self.buffer_size, self._rng(e, 2))
+
+    def __iter__(self):
+        e = 0
+        while True:
+            for pos, ref in enumerate(self.epoch(e)):
+                yield e, pos, ref
+            e += 1
+
+    def payload(self, ref):
+        if ref in self._payloads:
+            return self._payloads[ref]
+        path, k = ref
+        off, ln = self.records(path)[k]
+        data = bytes(self._rf[path].payload(off, ln))
+        if self.cache:
+            self._payloads[ref] = data
+        return data
+
+
+def create_dataset(config, dataset_key):
+    """create_dataset of lib_yolo/dataset_utils.py:103-117, as a record stream (the parse stage runs in TrainValDataset)."""
+    return RecordStream(config, dataset_key)
+
+
+class _HostBatch:
+    __slots__ = ('buf', 'plans', 'boxes', 'labels', 'counts', 'keys', 'error')
+
+
+class _Feed:
+    """One split's batches (the iterator of TrainValDataset.train / .val)."""
+
+    def __init__(self, config, dataset_key, split, device=None):
+        import torch
+        from byolo import augment
+        self._augment = augment
+        self.config = config
+        self.split = split
+        self.stream = RecordStream(config, dataset_key, split)
+        self.parse = make_parse_fn(config)
+        self.B = int(config['batch_size'])
+        self.full = tuple(int(v) for v in config['full_img_size'][:2])
+        self.out_hw = tuple(int(v) for v in (config['crop_img_size'] if config['crop'] else config['full_img_size'])[:2])
+        self.threads = max(1, int(config.get('cpu_thread_cnt', 1)))
+        # batches prepared ahead, each decoded on its share of cpu_thread_cnt: enough of them that every thread has an image
+        self.prefetch = max(2, int(config[dataset_key].get('prefetch', 0)) or min(16, -(-self.threads // self.B)))
+        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        Hf, Wf = self.full
+        self._free = queue.Queue()
+        for _ in range(self.prefetch + 2):
+            self._free.put(torch.empty((self.B, Hf, Wf, 3), dtype=torch.uint8, pin_memory=True))
+        self._dev = [torch.empty((self.B, Hf, Wf, 3), dtype=torch.uint8, device=self.device) for _ in range(2)]
+        self._dev_free = [None, None]                     # event after the last augment that read the slot
+        self._slot = 0
+        self._side = torch.cuda.Stream(self.device)
+        self._pending = None                              # (host batch, device slot, copy event)
+        self.host_seconds = {'augment': 0.0, 'copy': 0.0}  # host time of next(): event wait + augment launch / issuing copies
+        self._returning = []
+        self._ready = queue.Queue(maxsize=self.prefetch)
+        self._stop = threading.Event()
+        self._th = threading.Thread(target=self._producer, name='byolo-train-feed-%s' % split, daemon=True)
+        self._th.start()
+
+    # ---- host side ---------------------------------------------------------------------------------------------------
+    def _load(self, items, buf, threads):
+        from byolo import hostio, _lib
+        hb = _HostBatch()
+        hb.buf, hb.error = buf, None
+        try:
+            aug = self._augment
+            n = len(items)
+            plans = aug.empty_plans(n)
+            encs, boxes, labels, keys = [], [], [], []
+            for k, (e, pos, ref) in enumerate(items):
+                try:
+                    enc, bx, lb = self.parse(self.stream.payload(ref))
+                except ValueError as err:
+                    raise ValueError('{} record {}: {}'.format(ref[0], ref[1], err))
+                win = aug.draw(self.config, self.split, e, pos, plans[k])
+                bx, lb = aug.apply_to_boxes(plans[k], win, bx, lb)
+                encs.append(enc)
+                boxes.append(bx)
+                labels.append(lb)
+                keys.append(ref)
+            arr = buf.numpy()
+            _, status, found = hostio.decode_png_batch(encs, self.full + (3,), out=arr, threads=threads)
+            for k in range(n):
+                if status[k] == _lib.PNG_OK:
+                    continue
+                if status[k] == _lib.PNG_SHAPE:
+                    raise ValueError('{} record {}: image shape {} != config full_img_size {}'.format(
+                        keys[k][0], keys[k][1], tuple(int(v) for v in found[k]), tuple(self.config['full_img_size'])))
+                try:
+                    arr[k] = decode_png_u8(encs[k], self.full + (3,))
+                except Exception as err:
+                    raise ValueError('{} record {}: {}'.format(keys[k][0], keys[k][1], err))
+            plans['row0'] = plans['y0']
+            nmax = max([1] + [len(b) for b in boxes])
+            hb.boxes = np.zeros((n, nmax, 4), np.float32)
+            hb.labels = np.zeros((n, nmax), np.int32)
+            hb.counts = np.array([len(b) for b in boxes], np.int32)
+            for k in range(n):
+                hb.boxes[k, :len(boxes[k])] = boxes[k]
+                hb.labels[k, :len(labels[k])] = labels[k]
+            hb.plans, hb.keys = plans, keys
+        except Exception as err:
+            hb.error = err
+        return hb
+
+    def _producer(self):
+        from concurrent.futures import ThreadPoolExecutor
+        per_call = max(1, -(-self.threads // self.prefetch))
+        pool = ThreadPoolExecutor(max_workers=self.prefetch, thread_name_prefix='byolo-train-decode')
+        try:
+            items = []
+            for item in self.stream:
+                items.append(item)
+                if len(items) < self.B:
+                    continue
+                buf = None
+                while buf is None:
+                    if self._stop.is_set():
+                        return
+                    try:
+                        buf = self._free.get(timeout=0.1)
+                    except queue.Empty:
+                        pass
+                fut = pool.submit(self._load, items, buf, per_call)
+                items = []
+                while not self._stop.is_set():
+                    try:
+                        self._ready.put(fut, timeout=0.1)
+                        break
+                    except queue.Full:
+                        pass
+                if self._stop.is_set():
+                    return
+        except BaseException as err:                     # framing errors reach the consumer in order
+            self._ready.put(err)
+        finally:
+            pool.shutdown(wait=True)
+
+    # ---- device side -------------------------------------------------------------------------------------------------
+    def _start_copy(self, block):
+        import torch
+        try:
+            item = self._ready.get(block=block)
+        except queue.Empty:
+            return
+        if isinstance(item, BaseException):
+            raise item
+        hb = item.result()
+        if hb.error is not None:
+            self._free.put(hb.buf)
+            raise hb.error
+        slot = self._slot
+        self._slot ^= 1
+        dev = self._dev[slot]
+        with torch.cuda.stream(self._side):
+            if self._dev_free[slot] is not None:
+                self._side.wait_event(self._dev_free[slot])
+            for k in range(len(hb.plans)):
+                y0, ch = int(hb.plans[k]['y0']), int(hb.plans[k]['ch'])
+                dev[k, :ch].copy_(hb.buf[k, y0:y0 + ch], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(self._side)
+        self._pending = (hb, slot, ev)
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        import torch
+        for buf, ev in self._returning:                  # pinned buffers whose copies are done go back to the producer
+            ev.synchronize()
+            self._free.put(buf)
+        self._returning = []
+        if self._pending is None:
+            self._start_copy(block=True)
+        hb, slot, ev = self._pending
+        self._pending = None
+        t0 = time.perf_counter()
+        cur = torch.cuda.current_stream(self.device)
+        cur.wait_event(ev)
+        src_h = max(1, int(hb.plans['ch'].max()))
+        plans = hb.plans.copy()
+        plans['row0'] = plans['y0']
+        dev = self._dev[slot][:len(plans), :src_h]
+        img = self._augment.augment_batch(dev, plans, self.out_hw, stream=cur.cuda_stream)
+        done = torch.cuda.Event()
+        done.record(cur)
+        t1 = time.perf_counter()
+        self._dev_free[slot] = done
+        self._returning.append((hb.buf, ev))
+        self._start_copy(block=False)                    # the next batch's copy overlaps the caller's step
+        self.host_seconds['augment'] += t1 - t0
+        self.host_seconds['copy'] += time.perf_counter() - t1
+        plans['row0'] = 0
+        return {'img': img, 'boxes': hb.boxes, 'labels': hb.labels, 'counts': hb.counts, 'plans': plans, 'keys': hb.keys}
+
+    def close(self):
+        import torch
+        self._side.synchronize()                         # no copy into the device slots may outlive the feed
+        torch.cuda.current_stream(self.device).synchronize()
+        self._stop.set()
+        try:
+            while True:
+                self._ready.get_nowait()
+        except queue.Empty:
+            pass
+        self._th.join(timeout=10)
+
+
+class TrainValDataset:
+    """TrainValDataset of lib_yolo/dataset_utils.py:120-167: `train` and `val` iterate batches {'img': float32 CUDA tensor
+    [B, h, w, 3] on the current stream, 'boxes' [B, nmax, 4], 'labels' [B, nmax], 'counts' [B] (numpy), 'plans' (the batch's
+    byolo.augment plans, frame coordinates), 'keys' [(file, record index)]}.  Train: crop -> augment; val: the same random crop,
+    no augmentation.  The ground truth is encoded on the device by the trainer (byolo_encode_gt), so the blueprint is only
+    checked for its shape."""
+
+    def __init__(self, model_blueprint, config):
+        if config['crop']:
+            from lib_yolo.data_augmentation import ImageCropper
+            ImageCropper(config)                          # the aspect-ratio assertion
+        self.blueprint = model_blueprint
+        self.train = _Feed(config, 'train', 'train')
+        self.val = _Feed(config, 'val', 'val')
+
+    def close(self):
+        self.train.close()
+        self.val.close()

@@ -415,6 +415,30 @@ BYOLO_API uint32_t byolo_crc32c(const void* h_data, size_t n);
  * (B * H * W * C); d_f32 is what byolo_forward takes as d_img. */
 BYOLO_API int32_t byolo_normalize_u8(byolo_t* h, const uint8_t* d_u8, int64_t n, float* d_f32, void* stream);
 
+/* ---- training feed, device side (csrc/augment.hip): the crop and augmentation of lib_yolo/data_augmentation.py for one batch
+ * in ONE launch (up to 32 images; larger batches are split into launches of 32).  Per image a plan (byolo/augment.py draws
+ * them); per output pixel, in this order: u8 * (1 / 255) (as byolo_normalize_u8) -> crop window (y0, x0, ch, cw) -> TF1 legacy
+ * bilinear resize to out_h x out_w when `rescale` (else ch == out_h and cw == out_w) -> left-right flip -> box blur k x k (SAME,
+ * zero padding) -> colour op -> noise op (counter-based hash keyed by noise_key: the stream is documented in augment.hip).
+ * Image b of d_u8 starts at byte b * img_stride and holds src_h rows of src_w * 3 bytes: the frame's rows row0 .. row0 + src_h - 1
+ * (a caller may ship only the band of rows its crop reads; row0 = 0 for whole frames).  d_out: float32 [B, out_h, out_w, 3],
+ * 4-byte aligned.  A plan out of range (window outside the shipped rows or the frame width, blur_k not in {0, 2, 3}, an unknown
+ * op code, flip / rescale not 0 / 1, a parameter that is not finite, a hue delta outside [-1, 1]) is BYOLO_ERR_ARG before
+ * anything is launched.  h may be NULL (errors: byolo_last_error(NULL)). */
+enum { BYOLO_AUG_COLOR_NONE = 0, BYOLO_AUG_SATURATION = 1, BYOLO_AUG_BRIGHTNESS = 2, BYOLO_AUG_HUE = 3 };
+enum { BYOLO_AUG_NOISE_NONE = 0, BYOLO_AUG_COLORED_SALT_N_PEPPER = 1, BYOLO_AUG_SALT_N_PEPPER = 2, BYOLO_AUG_GAUSSIAN = 3 };
+typedef struct byolo_aug_plan {
+    int32_t y0, x0, ch, cw;        /* crop window in frame coordinates                                                          */
+    int32_t row0;                  /* first frame row shipped for this image (y0 >= row0, y0 - row0 + ch <= src_h)              */
+    int32_t rescale, flip, blur_k; /* 0 / 1, 0 / 1, 0 | 2 | 3                                                                    */
+    int32_t color_op, noise_op;    /* BYOLO_AUG_COLOR_* / BYOLO_AUG_NOISE_*                                                      */
+    float color_param;             /* saturation factor, brightness delta or hue delta                                          */
+    float noise_param;             /* salt-and-pepper amount or Gaussian stddev                                                 */
+    uint64_t noise_key;            /* key of the per-element hash                                                               */
+} byolo_aug_plan;
+BYOLO_API int32_t byolo_augment_batch(byolo_t* h, const uint8_t* d_u8, int32_t B, int32_t src_h, int32_t src_w, int64_t img_stride,
+                                      const byolo_aug_plan* h_plans, int32_t out_h, int32_t out_w, float* d_out, void* stream);
+
 /* The two status words (byolo_status: {flags, layer}) copied device-to-device into d_out[2] on `stream`, without waiting: a
  * multi-GPU driver appends them to the buffer its ONE all-gather carries, so that every rank learns of any rank's
  * BYOLO_ERR_RANGE from the gathered list and all ranks switch to the fp32 mode together (byolo/inference.py). */
