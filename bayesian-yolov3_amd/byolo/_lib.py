@@ -9,7 +9,8 @@ LIB_PATH = os.environ.get("BYOLO_LIB") or os.path.join(_HERE, "libbyolo.so")
 
 OK, ERR_ARG, ERR_STATE, ERR_HIP, ERR_NOMEM, ERR_RANGE = 0, -1, -2, -3, -4, -5
 DET_STANDARD, DET_ALEATORIC, DET_EPISTEMIC = 0, 1, 2
-NMS_AGNOSTIC, NMS_TWO_CLASS = 0, 1
+NMS_AGNOSTIC, NMS_TWO_CLASS, NMS_PER_CLASS = 0, 1, 2
+NMS_MAX_CLASSES = 128          # BYOLO_NMS_MAX_CLASSES
 NORM_BN, NORM_DROPOUT = 1, 2
 AUG_SATURATION, AUG_BRIGHTNESS, AUG_HUE = 1, 2, 3
 AUG_COLORED_SALT_N_PEPPER, AUG_SALT_N_PEPPER, AUG_GAUSSIAN = 1, 2, 3
@@ -84,6 +85,8 @@ PROTOTYPES = {
     "byolo_decode": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _P(_f32), _i32, _vp, _i64, _i64, _vp]),
     "byolo_epistemic_stats": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "byolo_nms_workspace_bytes": (_sz, [_i32, _i64]),
+    "byolo_nms_workspace_bytes_ex": (_sz, [_i32, _i64, _i32, _i32]),
+    "byolo_nms_class_counts": (_i32, [_vp, _vp, _i32, _i32, _vp]),
     "byolo_sort_nms": (_i32, [_vp, _vp, _i32, _i64, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _sz, _vp, _vp, _vp, _vp]),
     "byolo_calibrate_bn": (_i32, [_vp, _vp, _i32, _vp, _sz, _vp]),
     "byolo_set_profiling": (_i32, [_vp, _i32]),

@@ -287,9 +287,22 @@ class Engine:
         check(self._h, lib.byolo_flops(self._h, int(B), int(T), ctypes.byref(f)))
         return float(f.value)
 
+    @staticmethod
+    def nms_cap(nms_mode, max_out, cls_cnt):
+        """Rows of d_rows / d_kept per image: max_out per class pass (include/byolo.h byolo_forward)."""
+        return int(max_out) * {_lib.NMS_TWO_CLASS: 2, _lib.NMS_PER_CLASS: int(cls_cnt)}.get(int(nms_mode), 1)
+
     @property
     def out_cap(self):
-        return self.cfg.max_out * (2 if self.cfg.nms_mode == _lib.NMS_TWO_CLASS else 1)
+        return self.nms_cap(self.cfg.nms_mode, self.cfg.max_out, self.cfg.cls_cnt)
+
+    def _class_counts(self, B, device, stream):
+        """[B, cls_cnt] int32: kept per class of the handle's last per-class NMS, enqueued behind it on `stream`."""
+        torch = _torch()
+        cc = torch.empty((B, self.cfg.cls_cnt), dtype=torch.int32, device=device)
+        check(self._h, lib.byolo_nms_class_counts(self._h, ctypes.c_void_p(cc.data_ptr()), int(B), int(self.cfg.cls_cnt),
+                                                  ctypes.c_void_p(stream)))
+        return cc
 
     # ---- run ------------------------------------------------------------------------------------------
     def _workspace(self, B, T, slot=0):
@@ -414,7 +427,10 @@ class Engine:
         check(self._h, lib.byolo_forward(self._h, p(img), B, int(T), ctypes.c_uint64(int(seed) & (2**64 - 1)),
                                          int(bool(dropout_on)), p(mask_bits), p(ws), ws.numel(), p(boxes), p(rows), p(kept),
                                          p(count), ctypes.c_void_p(stream)))
-        return dict(boxes=boxes, rows=rows, kept=kept, count=count)
+        res = dict(boxes=boxes, rows=rows, kept=kept, count=count)
+        if want_nms and self.cfg.nms_mode == _lib.NMS_PER_CLASS:
+            res["class_counts"] = self._class_counts(B, dev, stream)
+        return res
 
     def layer_output(self, idx):
         """Copy of layer `idx`'s output after a forward (needs keep_all_outputs=True)."""
@@ -510,15 +526,18 @@ class Engine:
         return out
 
     def sort_nms(self, boxes, obj_idx, cls_start_idx, nms_mode=None, max_out=None, iou_thresh=None):
-        """tf.image.non_max_suppression + tf.gather per image on boxes [B,N,D] (device tensor)."""
+        """tf.image.non_max_suppression + tf.gather per image on boxes [B,N,D] (device tensor).  NMS_PER_CLASS: one NMS per
+        class of the engine's cls_cnt, rows / kept [B, cls_cnt * max_out, ..], and `class_counts` [B, cls_cnt] in the result."""
         torch = _torch()
         assert boxes.is_cuda and boxes.dtype == torch.float32 and boxes.is_contiguous() and boxes.dim() == 3
         B, N, D = boxes.shape
         nms_mode = self.cfg.nms_mode if nms_mode is None else nms_mode
         max_out = self.cfg.max_out if max_out is None else max_out
         iou_thresh = self.cfg.iou_thresh if iou_thresh is None else iou_thresh
-        cap = max_out * (2 if nms_mode == _lib.NMS_TWO_CLASS else 1)
-        wsb = int(lib.byolo_nms_workspace_bytes(B, N))
+        cap = self.nms_cap(nms_mode, max_out, self.cfg.cls_cnt)
+        wsb = int(lib.byolo_nms_workspace_bytes_ex(B, N, int(nms_mode), self.cfg.cls_cnt))
+        if wsb == 0:          # a mode the library does not know: its workspace has no size; byolo_sort_nms names the error
+            wsb = int(lib.byolo_nms_workspace_bytes(B, N))
         ws = torch.empty(wsb, dtype=torch.uint8, device=boxes.device)
         rows = torch.empty((B, cap, D), dtype=torch.float32, device=boxes.device)
         kept = torch.empty((B, cap), dtype=torch.int32, device=boxes.device)
@@ -529,4 +548,7 @@ class Engine:
                                           ctypes.c_void_p(ws.data_ptr()), wsb, ctypes.c_void_p(rows.data_ptr()),
                                           ctypes.c_void_p(kept.data_ptr()), ctypes.c_void_p(count.data_ptr()),
                                           ctypes.c_void_p(stream)))
-        return dict(rows=rows, kept=kept, count=count)
+        res = dict(rows=rows, kept=kept, count=count)
+        if int(nms_mode) == _lib.NMS_PER_CLASS:
+            res["class_counts"] = self._class_counts(B, boxes.device, stream)
+        return res

@@ -33,15 +33,17 @@ def concat_bbox(net_out, batched):
     return bbox
 
 
-def nms(boxes, model, batched, two_class=False, max_out=1000):
+def nms(boxes, model, batched, two_class=False, max_out=1000, per_class=False):
     """`tf.image.non_max_suppression(boxes[:, :4], boxes[:, model.obj_idx], 1000)` + `tf.gather`
     (`inference_epistemic.py:99-102`; 2-class variant `:104-126`) through byolo_sort_nms.
+    `per_class`: that variant for the model's class count, whatever it is (BYOLO_NMS_PER_CLASS: a row belongs to the
+    class whose score is its strict maximum; `max_out` per class; class 0's kept rows first).
     Returns the kept rows: [k, D] (un-batched) or a list of per-image [k_i, D] tensors.  (The
     reference's batched version concatenates per-image results, which only works when every image
     keeps the same number of boxes -- App. D.8 -- so a list is returned instead.)"""
     b = boxes if boxes.dim() == 3 else boxes[None]
     res = model.engine.sort_nms(b.contiguous(), model.obj_idx, model.cls_start_idx,
-                                nms_mode=1 if two_class else 0, max_out=max_out)
+                                nms_mode=2 if per_class else 1 if two_class else 0, max_out=max_out)
     counts = res['count'][:, 0].cpu().tolist()
     rows = [res['rows'][i, :n] for i, n in enumerate(counts)]
     return rows if batched else rows[0]

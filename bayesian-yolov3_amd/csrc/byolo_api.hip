@@ -152,6 +152,7 @@ extern "C" int32_t byolo_destroy(byolo_t* h) {
         if (h->d_zeros) (void)hipFree(h->d_zeros);
         if (h->ev_convs) (void)hipEventDestroy(h->ev_convs);
         if (h->d_status) (void)hipFree(h->d_status);
+        if (h->pc_own) (void)hipFree(h->pc_own);
         if (h->h_status) (void)hipHostFree(h->h_status);
         for (auto& ps : h->prof) {
             for (auto& e : ps.ev) if (e) (void)hipEventDestroy(e);
@@ -944,7 +945,16 @@ static int32_t forward_impl(byolo_t* h, const float* d_img, int32_t B, int32_t T
                 return fail(h, BYOLO_ERR_ARG, "byolo_forward: injected masks describe ONE piece: keep B <= byolo_max_images (%lld at T = %d)", (long long)cap, T);
             const int64_t first = h->first_image;
             const size_t img_el = (size_t)h->cfg.img_h * h->cfg.img_w * h->cfg.img_c;
-            const size_t out_cap = (size_t)h->cfg.max_out * (h->cfg.nms_mode == BYOLO_NMS_TWO_CLASS ? 2 : 1);
+            const bool per_class = h->cfg.nms_mode == BYOLO_NMS_PER_CLASS && d_rows;
+            const size_t out_cap = (size_t)h->cfg.max_out * (h->cfg.nms_mode == BYOLO_NMS_TWO_CLASS ? 2 : h->cfg.nms_mode == BYOLO_NMS_PER_CLASS ? h->cfg.cls_cnt : 1);
+            // the pieces share one workspace, so each piece's per-class counts are copied out behind it (byolo_nms_class_counts)
+            const size_t cc = (size_t)h->cfg.cls_cnt;
+            if (per_class && h->pc_own_cap < (size_t)B * cc) {
+                HIPCHK(h, hipSetDevice(h->device));
+                if (h->pc_own) { HIPCHK(h, hipDeviceSynchronize()); HIPCHK(h, hipFree(h->pc_own)); h->pc_own = nullptr; h->pc_own_cap = 0; }
+                HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->pc_own), (size_t)B * cc * sizeof(int32_t)));
+                h->pc_own_cap = (size_t)B * cc;
+            }
             int32_t rc = BYOLO_OK;
             for (int64_t lo = 0; lo < B && rc == BYOLO_OK; lo += cap) {
                 const int32_t n = (int32_t)std::min<int64_t>(cap, B - lo);
@@ -953,7 +963,13 @@ static int32_t forward_impl(byolo_t* h, const float* d_img, int32_t B, int32_t T
                                    d_boxes ? d_boxes + (size_t)lo * h->n_boxes * h->row_len : nullptr,
                                    d_rows ? d_rows + (size_t)lo * out_cap * h->row_len : nullptr, d_kept ? d_kept + (size_t)lo * out_cap : nullptr,
                                    d_count ? d_count + (size_t)lo * 2 : nullptr, stream);
+                if (rc == BYOLO_OK && per_class) {
+                    const hipError_t e = hipMemcpyAsync(h->pc_own + (size_t)lo * cc, h->pc_counts, (size_t)n * cc * sizeof(int32_t),
+                                                        hipMemcpyDeviceToDevice, reinterpret_cast<hipStream_t>(stream));
+                    if (e != hipSuccess) rc = fail(h, BYOLO_ERR_HIP, "byolo_forward: per-class counts of a piece: %s", hipGetErrorString(e));
+                }
             }
+            if (rc == BYOLO_OK && per_class) { h->pc_counts = h->pc_own; h->pc_B = B; }
             h->first_image = first;
             return rc;
         }
@@ -983,6 +999,12 @@ static int32_t forward_piece(byolo_t* h, const float* d_img, int32_t B, int32_t 
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     h->last_ws = d_workspace;
+    if (d_rows && h->cfg.nms_mode == BYOLO_NMS_PER_CLASS) {
+        // refused before anything is enqueued (a replayed graph never comes back through enqueue_forward)
+        if (h->cls_start + h->cfg.cls_cnt > h->row_len) return fail(h, BYOLO_ERR_ARG, "byolo_forward: per-class NMS: class columns outside the row");
+        h->pc_counts = nms_class_counts_ptr(static_cast<char*>(d_workspace) + h->plan.nms_off, B, h->n_boxes, h->cfg.cls_cnt);
+        h->pc_B = B; h->pc_C = h->cfg.cls_cnt;
+    }
     // (see ev_convs)  Only where a forward fills the chip by itself: a small one -- 8 images at 416 x 416 are 0.5 TFLOP in launches of
     // a few dozen tiles -- gains from running beside the next (config 2: 2480 img/s one after the other, 3110 side by side).
     // opts.serialize_convs: 0 never, 1 forwards of >= 1 TFLOP (default), 2 always.
@@ -1247,7 +1269,8 @@ static int32_t enqueue_forward(byolo_t* h, const FwdArgs& a, hipStream_t st, boo
         NmsParams n; memset(&n, 0, sizeof n);
         n.boxes = boxes; n.B = B; n.N = h->n_boxes; n.D = h->row_len; n.obj_idx = h->obj_idx; n.cls_start = h->cls_start;
         n.two_class = h->cfg.nms_mode == BYOLO_NMS_TWO_CLASS; n.max_out = h->cfg.max_out; n.iou_thr = h->cfg.iou_thresh;
-        n.ws = ws + h->plan.nms_off; n.ws_bytes = nms_workspace_bytes(B, h->n_boxes);
+        n.per_class = h->cfg.nms_mode == BYOLO_NMS_PER_CLASS; n.C = h->cfg.cls_cnt;
+        n.ws = ws + h->plan.nms_off; n.ws_bytes = nms_workspace_bytes_ex(B, h->n_boxes, n.per_class, n.C);
         n.rows = d_rows; n.kept = d_kept; n.count = d_count; n.general_only = h->opts.nms_general != 0;
         if (n.two_class && h->cfg.cls_cnt != 2) return fail(h, BYOLO_ERR_ARG, "byolo_forward: 2-class NMS needs cls_cnt == 2");
         HIPCHK(h, launch_sort_nms(n, st));
@@ -1341,6 +1364,11 @@ extern "C" int32_t byolo_epistemic_stats(byolo_t* h, const float* d_raw, int32_t
 }
 
 extern "C" size_t byolo_nms_workspace_bytes(int32_t B, int64_t N) { return nms_workspace_bytes(B, N); }
+extern "C" size_t byolo_nms_workspace_bytes_ex(int32_t B, int64_t N, int32_t nms_mode, int32_t cls_cnt) {
+    if (B < 1 || N < 1) return 0;
+    if (nms_mode == BYOLO_NMS_PER_CLASS && (cls_cnt < 1 || cls_cnt > BYOLO_NMS_MAX_CLASSES)) return 0;
+    return nms_workspace_bytes_ex(B, N, nms_mode == BYOLO_NMS_PER_CLASS, cls_cnt);
+}
 
 extern "C" int32_t byolo_sort_nms(byolo_t* h, const float* d_boxes, int32_t B, int64_t N, int32_t D, int32_t obj_idx,
                                   int32_t cls_start_idx, int32_t nms_mode, int32_t max_out, float iou_thresh,
@@ -1350,13 +1378,30 @@ extern "C" int32_t byolo_sort_nms(byolo_t* h, const float* d_boxes, int32_t B, i
     if (B < 1 || N < 1 || D < 5 || obj_idx < 4 || obj_idx >= D) return fail(h, BYOLO_ERR_ARG, "byolo_sort_nms: bad shape");
     if (nms_mode == BYOLO_NMS_TWO_CLASS && (cls_start_idx < 0 || cls_start_idx + 1 >= D)) return fail(h, BYOLO_ERR_ARG, "byolo_sort_nms: bad cls_start_idx");
     if (max_out < 1 || max_out > 2048) return fail(h, BYOLO_ERR_ARG, "byolo_sort_nms: max_out out of [1,2048]");
-    if (ws_bytes < nms_workspace_bytes(B, N)) return fail(h, BYOLO_ERR_NOMEM, "byolo_sort_nms: workspace too small");
+    if (nms_mode < BYOLO_NMS_AGNOSTIC || nms_mode > BYOLO_NMS_PER_CLASS) return fail(h, BYOLO_ERR_ARG, "byolo_sort_nms: unknown nms_mode %d", nms_mode);
+    const bool per_class = nms_mode == BYOLO_NMS_PER_CLASS;
+    const int32_t C = h->cfg.cls_cnt;                        // the class count of the per-class mode is the handle's
+    if (per_class && (C < 1 || C > BYOLO_NMS_MAX_CLASSES)) return fail(h, BYOLO_ERR_ARG, "byolo_sort_nms: per-class NMS takes 1 .. %d classes", BYOLO_NMS_MAX_CLASSES);
+    if (per_class && (cls_start_idx < 0 || (int64_t)cls_start_idx + C > D)) return fail(h, BYOLO_ERR_ARG, "byolo_sort_nms: bad cls_start_idx (class columns outside the row)");
+    if (per_class && N >= (1ll << 31)) return fail(h, BYOLO_ERR_ARG, "byolo_sort_nms: bad shape");
+    if (ws_bytes < nms_workspace_bytes_ex(B, N, per_class, C)) return fail(h, BYOLO_ERR_NOMEM, "byolo_sort_nms: workspace too small");
     HIPCHK(h, hipSetDevice(h->device));
     NmsParams n; memset(&n, 0, sizeof n);
     n.boxes = d_boxes; n.B = B; n.N = N; n.D = D; n.obj_idx = obj_idx; n.cls_start = cls_start_idx;
     n.two_class = nms_mode == BYOLO_NMS_TWO_CLASS; n.max_out = max_out; n.iou_thr = iou_thresh;
     n.ws = d_sort_ws; n.ws_bytes = ws_bytes; n.rows = d_rows; n.kept = d_kept; n.count = d_count; n.general_only = h->opts.nms_general != 0;
+    n.per_class = per_class; n.C = C;
     HIPCHK(h, launch_sort_nms(n, reinterpret_cast<hipStream_t>(stream)));
+    if (per_class) { h->pc_counts = nms_class_counts_ptr(d_sort_ws, B, N, C); h->pc_B = B; h->pc_C = C; }
+    return BYOLO_OK;
+}
+
+extern "C" int32_t byolo_nms_class_counts(byolo_t* h, int32_t* d_class_counts, int32_t B, int32_t cls_cnt, void* stream) {
+    if (!h || !d_class_counts) return fail(h, BYOLO_ERR_ARG, "byolo_nms_class_counts: null argument");
+    if (!h->pc_counts) return fail(h, BYOLO_ERR_STATE, "byolo_nms_class_counts: no per-class NMS (BYOLO_NMS_PER_CLASS) has run on this handle");
+    if (B != h->pc_B || cls_cnt != h->pc_C) return fail(h, BYOLO_ERR_ARG, "byolo_nms_class_counts: the last per-class NMS ran [%d, %d], asked for [%d, %d]", h->pc_B, h->pc_C, B, cls_cnt);
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipMemcpyAsync(d_class_counts, h->pc_counts, (size_t)B * cls_cnt * sizeof(int32_t), hipMemcpyDeviceToDevice, reinterpret_cast<hipStream_t>(stream)));
     return BYOLO_OK;
 }
 

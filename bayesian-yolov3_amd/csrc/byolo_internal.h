@@ -194,6 +194,10 @@ struct byolo {
     int64_t n_boxes = 0; int row_len = 0, obj_idx = 0, cls_start = 0;
     Plan plan;
     void* last_ws = nullptr;
+    // byolo_nms_class_counts: where the last per-class NMS left its [pc_B, pc_C] counts -- inside that call's workspace, or in
+    // pc_own (a forward that ran in pieces)
+    const int32_t* pc_counts = nullptr; int32_t pc_B = 0, pc_C = 0;
+    int32_t* pc_own = nullptr; size_t pc_own_cap = 0;
     int64_t first_image = 0;       // position of a call's first image in the logical batch (dropout stream)
     int stop_layer = -1;           // >= 0: enqueue_forward stops in front of the first step of this layer (byolo_run_backbone)
     int tshard_t0 = 0, tshard_T = 0;   // byolo_set_tshard: this call's T samples are samples t0 .. t0 + T - 1 of tshard_T per image (0 = off)

@@ -260,6 +260,7 @@ hipError_t launch_decode(int kind, const DecodeParams& p, hipStream_t st);
 hipError_t launch_epi_stats(const DecodeParams& p, float* ev_loc, float* covar, float* obj_s, float* cls_s, hipStream_t st);
 
 size_t nms_workspace_bytes(int B, int64_t N);
+size_t nms_workspace_bytes_ex(int B, int64_t N, int per_class, int C);   // per_class: BYOLO_NMS_PER_CLASS with C classes
 struct NmsParams {
     const float* boxes;      // [B, N, D]
     int B; int64_t N; int D, obj_idx, cls_start;
@@ -267,7 +268,10 @@ struct NmsParams {
     void* ws; size_t ws_bytes;
     float* rows; int32_t* kept; int32_t* count;
     int general_only;        // byolo_plan_opts.nms_general: the general path for every image (tests)
+    int per_class, C;        // BYOLO_NMS_PER_CLASS: one NMS per class, C = class count (1 .. BYOLO_MAX_CLASSES); ws_bytes >=
+                             // nms_workspace_bytes_ex(B, N, 1, C), rows / kept hold C * max_out per image
 };
+const int32_t* nms_class_counts_ptr(void* ws, int B, int64_t N, int C);   // per_class: the kept-per-class counts [B, C] inside ws
 hipError_t launch_sort_nms(const NmsParams& p, hipStream_t st);
 
 // ---- ground-truth encoding and training loss (train_kernels.hip) ------------------------

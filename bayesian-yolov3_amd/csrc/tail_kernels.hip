@@ -503,16 +503,95 @@ __device__ __forceinline__ bool iou_gt(const NBox& i, const NBox& j, float thr) 
     return iou > thr;
 }
 
+// LDS of one walk: the kept boxes so far, the staging of the wave whose turn it is, the kept count.
+struct WalkLds {
+    float k_y0[NMS_MAXK], k_x0[NMS_MAXK], k_y1[NMS_MAXK], k_x1[NMS_MAXK], k_ar[NMS_MAXK];
+    float w_y0[64], w_x0[64], w_y1[64], w_x1[64], w_ar[64];
+    int s_nk;
+};
+
+// One greedy pass of the whole workgroup over the score-ordered `keys[0 .. n_valid)`: member(row) says whether the
+// row is a candidate of this pass, emit(pos, idx) receives the pos-th kept box.  Returns the number kept (uniform).
+template <class Member, class Emit>
+__device__ __forceinline__ int greedy_walk(WalkLds& L, const float* bx, int D, const unsigned long long* keys, int n_valid,
+                                           int max_out, float thr, Member member, Emit emit) {
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    if (tid == 0) L.s_nk = 0;
+    __syncthreads();
+    int nk_cur = 0;                                          // register copy of s_nk, uniform across the block
+    for (int base = 0; base < n_valid && nk_cur < max_out; base += NMS_THREADS) {
+        const int i = base + tid;
+        bool alive = i < n_valid;
+        int idx = -1;
+        NBox me = {0, 0, 0, 0, 0};
+        if (alive) {
+            idx = (int)(keys[i] & 0xFFFFFFFFull);
+            const float* r = bx + (size_t)idx * D;
+            me = make_box(r[0], r[1], r[2], r[3]);
+            alive = member(r);
+        }
+        // phase A: against everything kept in earlier rounds
+        for (int k = 0; k < nk_cur; ++k) {
+            if (alive) {
+                const NBox kb = {L.k_y0[k], L.k_x0[k], L.k_y1[k], L.k_x1[k], L.k_ar[k]};
+                if (iou_gt(me, kb, thr)) alive = false;
+            }
+        }
+        // phase B: the 16 waves take turns
+        for (int sub = 0; sub < NMS_THREADS / 64 && nk_cur < max_out; ++sub) {
+            if (wave == sub) {
+                const unsigned long long alive_mask = __ballot(alive);
+                if (alive_mask) {
+                    L.w_y0[lane] = me.y0; L.w_x0[lane] = me.x0; L.w_y1[lane] = me.y1; L.w_x1[lane] = me.x1; L.w_ar[lane] = me.area;
+                    unsigned long long supp = 0ull;          // bit e: earlier live candidate e overlaps me
+                    for (int e = 0; e < 64; ++e) {
+                        if (e < lane && ((alive_mask >> e) & 1ull) && alive) {
+                            const NBox ob = {L.w_y0[e], L.w_x0[e], L.w_y1[e], L.w_x1[e], L.w_ar[e]};
+                            if (iou_gt(me, ob, thr)) supp |= (1ull << e);
+                        }
+                    }
+                    const unsigned int supp_lo = (unsigned int)supp, supp_hi = (unsigned int)(supp >> 32);
+                    unsigned long long keptmask = 0ull;
+                    int room = max_out - nk_cur;
+                    for (int e = 0; e < 64 && room > 0; ++e) {           // serial greedy resolve (uniform)
+                        if ((alive_mask >> e) & 1ull) {
+                            const unsigned long long se =
+                                ((unsigned long long)(unsigned int)__builtin_amdgcn_readlane((int)supp_hi, e) << 32) |
+                                (unsigned int)__builtin_amdgcn_readlane((int)supp_lo, e);
+                            if ((se & keptmask) == 0ull) { keptmask |= (1ull << e); --room; }
+                        }
+                    }
+                    if ((keptmask >> lane) & 1ull) {
+                        const int pos = nk_cur + __popcll(keptmask & ((1ull << lane) - 1ull));
+                        L.k_y0[pos] = me.y0; L.k_x0[pos] = me.x0; L.k_y1[pos] = me.y1; L.k_x1[pos] = me.x1; L.k_ar[pos] = me.area;
+                        emit(pos, idx);
+                    }
+                    if (lane == 0) L.s_nk = nk_cur + __popcll(keptmask);
+                }
+            }
+            __syncthreads();
+            const int nk_new = L.s_nk;
+            if (wave > sub && alive) {
+                for (int k = nk_cur; k < nk_new; ++k) {
+                    const NBox kb = {L.k_y0[k], L.k_x0[k], L.k_y1[k], L.k_x1[k], L.k_ar[k]};
+                    if (iou_gt(me, kb, thr)) { alive = false; break; }
+                }
+            }
+            nk_cur = nk_new;
+            __syncthreads();                                 // nobody still reads s_nk / w_* when the next wave writes
+        }
+    }
+    return nk_cur;
+}
+
 __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const float* boxes, int64_t N, int D, int obj_idx,
                                                           int cls_start, int two_class, int max_out, float thr,
                                                           int64_t NP, const unsigned long long* keys_all,
                                                           const int* n_valid_all, float* rows, int32_t* kept,
                                                           int32_t* count, const int* need) {
-    __shared__ float k_y0[NMS_MAXK], k_x0[NMS_MAXK], k_y1[NMS_MAXK], k_x1[NMS_MAXK], k_ar[NMS_MAXK];
+    __shared__ WalkLds L;
     __shared__ int k_idx[2 * NMS_MAXK];
-    __shared__ float w_y0[64], w_x0[64], w_y1[64], w_x1[64], w_ar[64];
-    __shared__ int s_nk;
-    const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int b = blockIdx.x, tid = threadIdx.x;
     if (need && !need[b]) return;                            // the fast path already finished this image
     const float* bx = boxes + (size_t)b * N * D;
     const unsigned long long* keys = keys_all + (size_t)b * NP;
@@ -521,76 +600,15 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const float* boxes, in
     int out_base = 0, first_cnt = 0;
 
     for (int pass = 0; pass < npass; ++pass) {
-        if (tid == 0) s_nk = 0;
-        __syncthreads();
-        int nk_cur = 0;                                      // register copy of s_nk, uniform across the block
-        for (int base = 0; base < n_valid && nk_cur < max_out; base += NMS_THREADS) {
-            const int i = base + tid;
-            bool alive = i < n_valid;
-            int idx = -1;
-            NBox me = {0, 0, 0, 0, 0};
-            if (alive) {
-                idx = (int)(keys[i] & 0xFFFFFFFFull);
-                const float* r = bx + (size_t)idx * D;
-                me = make_box(r[0], r[1], r[2], r[3]);
-                if (two_class) {
-                    const float c0 = r[cls_start], c1 = r[cls_start + 1];
-                    alive = (pass == 0) ? (c0 > c1) : (c1 > c0);      // strict; ties dropped (:108-110)
-                }
-            }
-            // phase A: against everything kept in earlier rounds
-            for (int k = 0; k < nk_cur; ++k) {
-                if (alive) {
-                    const NBox kb = {k_y0[k], k_x0[k], k_y1[k], k_x1[k], k_ar[k]};
-                    if (iou_gt(me, kb, thr)) alive = false;
-                }
-            }
-            // phase B: the 16 waves take turns
-            for (int sub = 0; sub < NMS_THREADS / 64 && nk_cur < max_out; ++sub) {
-                if (wave == sub) {
-                    const unsigned long long alive_mask = __ballot(alive);
-                    if (alive_mask) {
-                        w_y0[lane] = me.y0; w_x0[lane] = me.x0; w_y1[lane] = me.y1; w_x1[lane] = me.x1; w_ar[lane] = me.area;
-                        unsigned long long supp = 0ull;      // bit e: earlier live candidate e overlaps me
-                        for (int e = 0; e < 64; ++e) {
-                            if (e < lane && ((alive_mask >> e) & 1ull) && alive) {
-                                const NBox ob = {w_y0[e], w_x0[e], w_y1[e], w_x1[e], w_ar[e]};
-                                if (iou_gt(me, ob, thr)) supp |= (1ull << e);
-                            }
-                        }
-                        const unsigned int supp_lo = (unsigned int)supp, supp_hi = (unsigned int)(supp >> 32);
-                        unsigned long long keptmask = 0ull;
-                        int room = max_out - nk_cur;
-                        for (int e = 0; e < 64 && room > 0; ++e) {       // serial greedy resolve (uniform)
-                            if ((alive_mask >> e) & 1ull) {
-                                const unsigned long long se =
-                                    ((unsigned long long)(unsigned int)__builtin_amdgcn_readlane((int)supp_hi, e) << 32) |
-                                    (unsigned int)__builtin_amdgcn_readlane((int)supp_lo, e);
-                                if ((se & keptmask) == 0ull) { keptmask |= (1ull << e); --room; }
-                            }
-                        }
-                        if ((keptmask >> lane) & 1ull) {
-                            const int pos = nk_cur + __popcll(keptmask & ((1ull << lane) - 1ull));
-                            k_y0[pos] = me.y0; k_x0[pos] = me.x0; k_y1[pos] = me.y1; k_x1[pos] = me.x1; k_ar[pos] = me.area;
-                            k_idx[out_base + pos] = idx;
-                        }
-                        if (lane == 0) s_nk = nk_cur + __popcll(keptmask);
-                    }
-                }
-                __syncthreads();
-                const int nk_new = s_nk;
-                if (wave > sub && alive) {
-                    for (int k = nk_cur; k < nk_new; ++k) {
-                        const NBox kb = {k_y0[k], k_x0[k], k_y1[k], k_x1[k], k_ar[k]};
-                        if (iou_gt(me, kb, thr)) { alive = false; break; }
-                    }
-                }
-                nk_cur = nk_new;
-                __syncthreads();                             // nobody still reads s_nk / w_* when the next wave writes
-            }
-        }
-        if (pass == 0) first_cnt = nk_cur;
-        out_base += nk_cur;
+        const int nk = greedy_walk(L, bx, D, keys, n_valid, max_out, thr,
+            [&](const float* r) {
+                if (!two_class) return true;
+                const float c0 = r[cls_start], c1 = r[cls_start + 1];
+                return (pass == 0) ? (c0 > c1) : (c1 > c0);               // strict; ties dropped (:108-110)
+            },
+            [&](int pos, int idx) { k_idx[out_base + pos] = idx; });
+        if (pass == 0) first_cnt = nk;
+        out_base += nk;
         __syncthreads();
     }
     // gather rows (tf.gather) + zero fill
@@ -731,17 +749,12 @@ __global__ __launch_bounds__(1024) void topk_select_kernel(const float* boxes, i
     if (tid == 0) { n_cand_all[b] = C; more_all[b] = n_valid > C ? 1 : 0; }
 }
 
-__global__ __launch_bounds__(64) void nms_matrix_kernel(const float* boxes, int64_t N, int D, float thr,
-                                                        const unsigned long long* cand_all, const int* n_cand_all,
-                                                        unsigned long long* mask_all) {
+// One 64 x 64 tile of a suppression matrix: rows rb*64.., bit columns w*64.. of the Kc-long sorted prefix `cand`;
+// `mask` holds NMS_WORDS words per row.  One wave.
+__device__ __forceinline__ void matrix_tile(const float* bx, int D, float thr, const unsigned long long* cand, int Kc,
+                                            int rb, int w, unsigned long long* mask) {
     __shared__ float c_y0[64], c_x0[64], c_y1[64], c_x1[64], c_ar[64];
-    const int w = blockIdx.x, rb = blockIdx.y, b = blockIdx.z, lane = threadIdx.x;
-    if (w < rb) return;                                      // lower triangle is never read
-    int Kc = n_cand_all[b];
-    if (Kc > NMS_TOPK) Kc = NMS_TOPK;
-    if (rb * 64 >= Kc) return;
-    const float* bx = boxes + (size_t)b * N * D;
-    const unsigned long long* cand = cand_all + (size_t)b * NMS_CAP;
+    const int lane = threadIdx.x;
     const int r = rb * 64 + lane, c = w * 64 + lane;
     NBox me = {0, 0, 0, 0, 0};
     if (r < Kc) { const float* q = bx + (size_t)(cand[r] & 0xFFFFFFFFull) * D; me = make_box(q[0], q[1], q[2], q[3]); }
@@ -760,26 +773,33 @@ __global__ __launch_bounds__(64) void nms_matrix_kernel(const float* boxes, int6
                 if (iou_gt(me, o, thr)) bits |= 1ull << e;
             }
         }
-        mask_all[((size_t)b * NMS_TOPK + r) * NMS_WORDS + w] = bits;
+        mask[(size_t)r * NMS_WORDS + w] = bits;
     }
 }
 
-__global__ __launch_bounds__(256) void nms_scan_kernel(int max_out, int pass, const unsigned long long* cand_all,
-                                                       const int* n_cand_all, const int* more_all,
-                                                       const unsigned long long* mask_all, int* kidx_all, int* cnt_all,
-                                                       int* need) {
+__global__ __launch_bounds__(64) void nms_matrix_kernel(const float* boxes, int64_t N, int D, float thr,
+                                                        const unsigned long long* cand_all, const int* n_cand_all,
+                                                        unsigned long long* mask_all) {
+    const int w = blockIdx.x, rb = blockIdx.y, b = blockIdx.z;
+    if (w < rb) return;                                      // lower triangle is never read
+    int Kc = n_cand_all[b];
+    if (Kc > NMS_TOPK) Kc = NMS_TOPK;
+    if (rb * 64 >= Kc) return;
+    matrix_tile(boxes + (size_t)b * N * D, D, thr, cand_all + (size_t)b * NMS_CAP, Kc, rb, w,
+                mask_all + (size_t)b * NMS_TOPK * NMS_WORDS);
+}
+
+// Serial greedy scan of one sorted prefix (`cand`, n_cand keys, its matrix `mask`) by one 256-thread workgroup:
+// kept indices to `kidx`, their number to *cnt, *need = 1 where the prefix cannot prove the result.
+__device__ __forceinline__ void scan_prefix(int max_out, const unsigned long long* cand, int n_cand, const int* more,
+                                            const unsigned long long* mask, int* kidx, int* cnt, int* need) {
     // The 64 matrix rows of a step, double-buffered (2 x 32 KiB, dynamic LDS): waves 1..3 fetch the rows of step c+1
     // while wave 0 resolves step c -- the fetch latency (L2) leaves the serial chain.
     extern __shared__ __attribute__((aligned(16))) unsigned long long rows_all[];   // [2][64][NMS_WORDS]
     __shared__ int s_nk, s_done;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n_cand = n_cand_all[b];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int Kc = n_cand > NMS_TOPK ? NMS_TOPK : n_cand;
     const int nwords = (Kc + 63) / 64;
-    const unsigned long long* cand = cand_all + (size_t)b * NMS_CAP;
-    const unsigned long long* mask = mask_all + (size_t)b * NMS_TOPK * NMS_WORDS;
-    const int base = pass ? cnt_all[2 * b] : 0;
-    int* kidx = kidx_all + (size_t)b * 2 * NMS_MAXK + base;
     if (tid == 0) { s_nk = 0; s_done = 0; }
     auto fetch = [&](int c, int first, int nthreads) {       // rows of step c -> buffer c & 1, by `nthreads` threads from `first`
         unsigned long long (*rows)[NMS_WORDS] = reinterpret_cast<unsigned long long (*)[NMS_WORDS]>(rows_all + (size_t)(c & 1) * 64 * NMS_WORDS);
@@ -839,10 +859,22 @@ __global__ __launch_bounds__(256) void nms_scan_kernel(int max_out, int pass, co
     }
     if (tid == 0) {
         const int nk = s_nk;
-        cnt_all[2 * b + pass] = nk;
+        *cnt = nk;
         // prefix exhausted without filling max_out although more candidates exist -> general path
-        if (nk < max_out && (more_all[b] || n_cand > Kc)) need[b] = 1;
+        if (nk < max_out && (*more || n_cand > Kc)) *need = 1;
     }
+}
+
+
+__global__ __launch_bounds__(256) void nms_scan_kernel(int max_out, int pass, const unsigned long long* cand_all,
+                                                       const int* n_cand_all, const int* more_all,
+                                                       const unsigned long long* mask_all, int* kidx_all, int* cnt_all,
+                                                       int* need) {
+    const int b = blockIdx.x;
+    const int n_cand = n_cand_all[b];
+    const int base = pass ? cnt_all[2 * b] : 0;
+    scan_prefix(max_out, cand_all + (size_t)b * NMS_CAP, n_cand, &more_all[b], mask_all + (size_t)b * NMS_TOPK * NMS_WORDS,
+                kidx_all + (size_t)b * 2 * NMS_MAXK + base, &cnt_all[2 * b + pass], &need[b]);
 }
 
 __global__ __launch_bounds__(1024) void nms_finish_kernel(const float* boxes, int64_t N, int D, int max_out, int npass,
@@ -864,8 +896,375 @@ __global__ __launch_bounds__(1024) void nms_finish_kernel(const float* boxes, in
     if (tid == 0) { count[2 * b] = total; count[2 * b + 1] = first; }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Per-class mode (BYOLO_NMS_PER_CLASS): the classes of an image run side by side.
+//   pc_classify   every row: its class (the strict unique maximum of the C class scores, else none) as one byte --
+//                 the digit above the score bits of the sort key -- and the per-image class histogram (two kernels:
+//                 rows read in place for few classes, class scores staged through LDS for many)
+//   pc_offsets    per image: segment / matrix-row / tile offsets of the classes (prefix sums of the histogram)
+//   pc_scatter    counting sort on the class digit: (score key, index) of every member into its class segment
+//   pc_select     grid (class, image): sorted prefix of the segment -- the whole segment where it fits LDS (NMS_CAP),
+//                 else the 3-level radix select of topk_select over the segment's keys
+//   pc_matrix     the 64 x 64 tiles of all classes' suppression matrices, as one linear list per image
+//   pc_scan       grid (class, image): scan_prefix; a class whose prefix cannot prove its result sets need[b][c]
+//   pc_general    grid (class, image), flagged classes only: full sort of the segment + greedy_walk
+//   pc_finish     kept rows of class 0, 1, ... back to back, zero fill, counts
+// An empty class costs one workgroup that reads its length and returns, in every stage.
+// ------------------------------------------------------------------------------------------------
+static constexpr int PC_NONE = 255;                          // class byte of a row that belongs to no class
+static_assert(BYOLO_MAX_CLASSES < PC_NONE, "the class digit of the per-class NMS key is one byte");
+static constexpr int PC_ROWS = 128;                          // output rows per pc_finish workgroup
+static constexpr int PC_TILE = 64;                           // rows per pc_classify_tiled workgroup
+static constexpr int PC_DIRECT_C = 8;                        // up to this many classes pc_classify reads the rows in place
+
+struct PcWs {
+    unsigned char* cls;                                      // [B][N]
+    int *hist, *cursor;                                      // [B][C+1] members per class (slot C unused), scatter cursors
+    int *seg_off, *row_off, *tile_off;                       // [B][C+1] exclusive prefix sums
+    int *n_cand, *more, *need;                               // [B][C+1]
+    int* cnt;                                                // [B][C] kept per class
+    unsigned long long *seg, *cand;                          // [B][N] keys by class segment: unordered / sorted prefix
+    unsigned long long* mask;                                // [B][R][NMS_WORDS], R = pc_mask_rows
+    int* kidx;                                               // [B][C][NMS_MAXK]
+};
+static inline int64_t pc_mask_rows(int64_t N, int C) { return std::min<int64_t>(N, (int64_t)C * NMS_TOPK); }
+static inline int64_t pc_max_tiles(int64_t N, int C) {       // sum of T(T+1)/2 over classes, T <= 64, sum T <= N/64 + C
+    return std::min<int64_t>((int64_t)C * (NMS_WORDS * (NMS_WORDS + 1) / 2), (N / 64 + C) * (NMS_WORDS + 1) / 2 + 1);
+}
+static size_t pc_ws_layout(int B, int64_t N, int C, char* base, PcWs* w) {
+    size_t o = 0;
+    auto take = [&](size_t bytes) { char* p = base ? base + o : nullptr; o += (bytes + 255) / 256 * 256; return p; };
+    const size_t ci = (size_t)B * (C + 1) * 4;
+    char* hc = take(2 * ci);                                 // hist + cursor: cleared by one memset
+    char* so = take(ci); char* ro = take(ci); char* to = take(ci); char* nc = take(ci); char* mo = take(ci); char* ne = take(ci);
+    char* cn = take((size_t)B * C * 4);
+    char* cl = take((size_t)B * N);
+    char* sg = take((size_t)B * N * 8); char* cd = take((size_t)B * N * 8);
+    char* mk = take((size_t)B * pc_mask_rows(N, C) * NMS_WORDS * 8);
+    char* ki = take((size_t)B * C * NMS_MAXK * 4);
+    if (w) { w->hist = (int*)hc; w->cursor = (int*)(hc ? hc + ci : nullptr); w->seg_off = (int*)so; w->row_off = (int*)ro;
+             w->tile_off = (int*)to; w->n_cand = (int*)nc; w->more = (int*)mo; w->need = (int*)ne; w->cnt = (int*)cn;
+             w->cls = (unsigned char*)cl; w->seg = (unsigned long long*)sg; w->cand = (unsigned long long*)cd;
+             w->mask = (unsigned long long*)mk; w->kidx = (int*)ki; }
+    return o;
+}
+const int32_t* nms_class_counts_ptr(void* ws, int B, int64_t N, int C) {
+    PcWs w;
+    pc_ws_layout(B, N, C, reinterpret_cast<char*>(ws), &w);
+    return w.cnt;
+}
+size_t nms_workspace_bytes_ex(int B, int64_t N, int per_class, int C) {
+    return per_class ? pc_ws_layout(B, N, C, nullptr, nullptr) : nms_workspace_bytes(B, N);
+}
+
+// The class of one row from its C class scores `t` (global memory or LDS) and its score: class c iff cls[c] > cls[k] for every
+// k != c -- a maximum attained twice or any NaN leaves no such c; a score that is no NMS candidate leaves none either.
+__device__ __forceinline__ int classify_row(const float* t, int C, float score) {
+    if (score_key(score) == 0xFFFFFFFFu) return PC_NONE;
+    float best = t[0];
+    int arg = 0;
+    bool uniq = true, nan = C > 1 && best != best;
+    for (int c = 1; c < C; ++c) {
+        const float v = t[c];
+        nan |= v != v;
+        if (v > best) { best = v; arg = c; uniq = true; }
+        else if (v == best) uniq = false;
+    }
+    return (uniq && !nan) ? arg : PC_NONE;
+}
+
+// Few classes (C <= PC_DIRECT_C): one lane per row reads its class scores where they are.
+__global__ __launch_bounds__(256) void pc_classify_kernel(const float* boxes, int64_t N, int D, int obj_idx, int cls_start,
+                                                          int C, unsigned char* cls_all, int* hist_all) {
+    __shared__ int h[PC_DIRECT_C];
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * 256 + tid;
+    if (tid < C) h[tid] = 0;
+    __syncthreads();
+    if (i < N) {
+        const float* r = boxes + ((size_t)b * N + i) * D;
+        const int cl = classify_row(r + cls_start, C, r[obj_idx]);
+        cls_all[(size_t)b * N + i] = (unsigned char)cl;
+        if (cl != PC_NONE) atomicAdd(&h[cl], 1);
+    }
+    __syncthreads();
+    if (tid < C && h[tid]) atomicAdd(&hist_all[(size_t)b * (C + 1) + tid], h[tid]);
+}
+
+// Many classes: the class scores of PC_TILE rows go through LDS -- the workgroup reads each row's C columns with consecutive
+// lanes, then one lane per row scans them (row stride odd: no bank conflict).  Lanes that walk wide rows of their own in global
+// memory touch 64 cache lines per load and evict each other's lines before the next column is read (C = 80: 1.7 ms for
+// 11 x 120 960 rows that way).
+__global__ __launch_bounds__(256) void pc_classify_tiled_kernel(const float* boxes, int64_t N, int D, int obj_idx, int cls_start,
+                                                                int C, unsigned char* cls_all, int* hist_all) {
+    __shared__ float tile[PC_TILE * (BYOLO_MAX_CLASSES + 1)];
+    __shared__ int h[BYOLO_MAX_CLASSES];
+    const int b = blockIdx.y, tid = threadIdx.x, S = C | 1;
+    const int64_t i0 = (int64_t)blockIdx.x * PC_TILE;
+    const int nrow = N - i0 < PC_TILE ? (int)(N - i0) : PC_TILE;
+    const float* bx = boxes + ((size_t)b * N + i0) * D;
+    for (int c = tid; c < C; c += 256) h[c] = 0;
+    for (int e = tid; e < nrow * C; e += 256) {
+        const int r = e / C, c = e - r * C;
+        tile[r * S + c] = bx[(size_t)r * D + cls_start + c];
+    }
+    __syncthreads();
+    if (tid < nrow) {
+        const int cl = classify_row(tile + tid * S, C, bx[(size_t)tid * D + obj_idx]);
+        cls_all[(size_t)b * N + i0 + tid] = (unsigned char)cl;
+        if (cl != PC_NONE) atomicAdd(&h[cl], 1);
+    }
+    __syncthreads();
+    for (int c = tid; c < C; c += 256)
+        if (h[c]) atomicAdd(&hist_all[(size_t)b * (C + 1) + c], h[c]);
+}
+
+__global__ __launch_bounds__(64) void pc_offsets_kernel(int C, int general_only, PcWs w) {
+    __shared__ int hist[BYOLO_MAX_CLASSES];
+    const int b = blockIdx.x, tid = threadIdx.x, CS = C + 1;
+    for (int c = tid; c < C; c += 64) {
+        hist[c] = w.hist[(size_t)b * CS + c];
+        w.n_cand[(size_t)b * CS + c] = 0; w.more[(size_t)b * CS + c] = 0; w.need[(size_t)b * CS + c] = general_only;
+        w.cnt[(size_t)b * C + c] = 0;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int so = 0, ro = 0, to = 0;
+        for (int c = 0; c <= C; ++c) {
+            w.seg_off[(size_t)b * CS + c] = so; w.row_off[(size_t)b * CS + c] = ro; w.tile_off[(size_t)b * CS + c] = to;
+            if (c == C) break;
+            const int n = hist[c], kc = n < NMS_TOPK ? n : NMS_TOPK, t = (kc + 63) / 64;
+            so += n; ro += kc; to += t * (t + 1) / 2;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void pc_scatter_kernel(const float* boxes, int64_t N, int D, int obj_idx, int C, PcWs w) {
+    __shared__ int h[BYOLO_MAX_CLASSES], base[BYOLO_MAX_CLASSES];
+    const int b = blockIdx.y, tid = threadIdx.x, CS = C + 1;
+    const int64_t i = (int64_t)blockIdx.x * 256 + tid;
+    for (int c = tid; c < C; c += 256) h[c] = 0;
+    __syncthreads();
+    const int cl = i < N ? (int)w.cls[(size_t)b * N + i] : PC_NONE;
+    int rank = -1;
+    if (cl != PC_NONE) rank = atomicAdd(&h[cl], 1);
+    __syncthreads();
+    for (int c = tid; c < C; c += 256)
+        if (h[c]) base[c] = w.seg_off[(size_t)b * CS + c] + atomicAdd(&w.cursor[(size_t)b * CS + c], h[c]);
+    __syncthreads();
+    if (rank >= 0) {
+        const unsigned int k = score_key(boxes[((size_t)b * N + i) * D + obj_idx]);
+        w.seg[(size_t)b * N + base[cl] + rank] = ((unsigned long long)k << 32) | (unsigned int)i;
+    }
+}
+
+__global__ __launch_bounds__(1024) void pc_select_kernel(int64_t N, int C, PcWs w) {
+    extern __shared__ __attribute__((aligned(16))) unsigned long long sbuf[];      // NMS_CAP keys
+    __shared__ int hist[2048];
+    __shared__ int part[32];
+    __shared__ int s_digit, s_below, s_le, s_cnt;
+    const int c = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, CS = C + 1;
+    const int n = w.hist[(size_t)b * CS + c];
+    if (n == 0) return;                                      // n_cand = more = 0 from pc_offsets
+    const size_t off = (size_t)b * N + w.seg_off[(size_t)b * CS + c];
+    const unsigned long long* seg = w.seg + off;
+    int Cn = n;
+    bool ties_overflow = false;
+    if (n <= NMS_CAP) {
+        for (int i = tid; i < n; i += 1024) sbuf[i] = seg[i];
+    } else {                                                 // radix select of the best >= NMS_TOPK keys, as topk_select_kernel
+        unsigned int prefix = 0, pmask = 0;
+        int below = 0;
+        const int shifts[3] = {21, 10, 0}, widths[3] = {11, 11, 10};
+        for (int level = 0; level < 3; ++level) {
+            const int shift = shifts[level], nd = 1 << widths[level];
+            for (int i = tid; i < 2048; i += 1024) hist[i] = 0;
+            __syncthreads();
+            for (int i = tid; i < n; i += 1024) {
+                const unsigned int k = (unsigned int)(seg[i] >> 32);
+                if ((k & pmask) == prefix) atomicAdd(&hist[(k >> shift) & (nd - 1)], 1);
+            }
+            __syncthreads();
+            if (tid < 32) { int s = 0; for (int d = tid * 64; d < tid * 64 + 64; ++d) s += hist[d]; part[tid] = s; }
+            __syncthreads();
+            if (tid == 0) {                                  // smallest digit d with below + #(digit <= d) >= NMS_TOPK
+                int cum = below, q = 0;
+                while (q < 31 && cum + part[q] < NMS_TOPK) { cum += part[q]; ++q; }
+                int d = q * 64;
+                while (d < q * 64 + 63 && cum + hist[d] < NMS_TOPK) { cum += hist[d]; ++d; }
+                s_digit = d; s_below = cum; s_le = cum + hist[d];
+            }
+            __syncthreads();
+            prefix |= (unsigned int)s_digit << shift;
+            pmask |= (unsigned int)(nd - 1) << shift;
+            below = s_below;
+            Cn = s_le;
+            __syncthreads();
+            if (Cn <= NMS_CAP) break;                        // every key <= this (partial) threshold fits
+            if (level == 2) ties_overflow = true;            // > NMS_CAP members share one exact score
+        }
+        if (ties_overflow) {
+            if (tid == 0) { w.need[(size_t)b * CS + c] = 1; w.more[(size_t)b * CS + c] = 1; }
+            return;                                          // n_cand stays 0: no tile, an empty scan
+        }
+        if (tid == 0) s_cnt = 0;
+        __syncthreads();
+        for (int i = tid; i < n; i += 1024) {
+            const unsigned long long k = seg[i];
+            if (((unsigned int)(k >> 32) & pmask) <= prefix) sbuf[atomicAdd(&s_cnt, 1)] = k;
+        }
+    }
+    __syncthreads();
+    int P2 = 64;
+    while (P2 < Cn) P2 <<= 1;
+    for (int i = Cn + tid; i < P2; i += 1024) sbuf[i] = ~0ull;
+    __syncthreads();
+    for (int k = 2; k <= P2; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = tid; t < P2 / 2; t += 1024) {
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+                ce(sbuf[i], sbuf[i + j], (i & k) == 0);
+            }
+            __syncthreads();
+        }
+    unsigned long long* cand = w.cand + off;
+    for (int i = tid; i < Cn; i += 1024) cand[i] = sbuf[i];
+    if (tid == 0) { w.n_cand[(size_t)b * CS + c] = Cn; w.more[(size_t)b * CS + c] = n > Cn ? 1 : 0; }
+}
+
+__global__ __launch_bounds__(64) void pc_matrix_kernel(const float* boxes, int64_t N, int D, float thr, int C, int64_t R, PcWs w) {
+    const int b = blockIdx.y, CS = C + 1;
+    const int* toff = w.tile_off + (size_t)b * CS;
+    // the image's tiles are dealt round over a grid that does not grow with the class count: a workgroup without a tile
+    // costs a launch slot, and most classes have few
+    for (int t = blockIdx.x; t < toff[C]; t += gridDim.x) {
+        int lo = 0, hi = C - 1;                              // the class of tile t: the last c with toff[c] <= t
+        while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (toff[mid] <= t) lo = mid; else hi = mid - 1; }
+        const int c = lo;
+        int Kc = w.n_cand[(size_t)b * CS + c];               // 0 where pc_select handed the class over
+        if (Kc > NMS_TOPK) Kc = NMS_TOPK;
+        const int n = w.hist[(size_t)b * CS + c];
+        const int T = ((n < NMS_TOPK ? n : NMS_TOPK) + 63) / 64;     // the tile grid pc_offsets counted for this class
+        int rb = 0, lt = t - toff[c];                        // row block rb holds the T - rb tiles w = rb .. T-1
+        while (lt >= T - rb) { lt -= T - rb; ++rb; }
+        const int wd = rb + lt;
+        if (rb * 64 >= Kc) continue;
+        matrix_tile(boxes + (size_t)b * N * D, D, thr, w.cand + (size_t)b * N + w.seg_off[(size_t)b * CS + c], Kc, rb, wd,
+                    w.mask + ((size_t)b * R + w.row_off[(size_t)b * CS + c]) * NMS_WORDS);
+        __syncthreads();                                     // the tile's LDS columns are read out before the next tile's land
+    }
+}
+
+__global__ __launch_bounds__(256) void pc_scan_kernel(int64_t N, int C, int64_t R, int max_out, PcWs w) {
+    const int c = blockIdx.x, b = blockIdx.y, CS = C + 1;
+    const size_t bc = (size_t)b * CS + c;
+    if (w.hist[bc] == 0) return;                             // cnt = 0 from pc_offsets
+    scan_prefix(max_out, w.cand + (size_t)b * N + w.seg_off[bc], w.n_cand[bc], &w.more[bc],
+                w.mask + ((size_t)b * R + w.row_off[bc]) * NMS_WORDS, w.kidx + ((size_t)b * C + c) * NMS_MAXK,
+                &w.cnt[(size_t)b * C + c], &w.need[bc]);
+}
+
+__global__ __launch_bounds__(NMS_THREADS) void pc_general_kernel(const float* boxes, int64_t N, int D, int C, int max_out,
+                                                                 float thr, PcWs w) {
+    __shared__ WalkLds L;
+    const int c = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, CS = C + 1;
+    const size_t bc = (size_t)b * CS + c;
+    const int n = w.hist[bc];
+    if (!w.need[bc] || n == 0) return;
+    unsigned long long* keys = w.seg + (size_t)b * N + w.seg_off[bc];
+    // bitonic sort of an arbitrary length: every comparison ascending (the first step of a merge mirrors its upper
+    // half), so the virtual +inf padding beyond n never moves and pairs that reach into it are skipped
+    int P2 = 1;
+    while (P2 < n) P2 <<= 1;
+    for (int k = 2; k <= P2; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = tid; t < P2 / 2; t += NMS_THREADS) {
+                int i, p;
+                if (j == (k >> 1)) { const int blk = t / j, o = t - blk * j; i = blk * k + o; p = blk * k + (k - 1 - o); }
+                else { i = ((t & ~(j - 1)) << 1) | (t & (j - 1)); p = i + j; }
+                if (p < n) {
+                    const unsigned long long a = keys[i], q = keys[p];
+                    if (a > q) { keys[i] = q; keys[p] = a; }
+                }
+            }
+            __syncthreads();
+        }
+    int* kidx = w.kidx + ((size_t)b * C + c) * NMS_MAXK;
+    const int nk = greedy_walk(L, boxes + (size_t)b * N * D, D, keys, n, max_out, thr,
+                               [](const float*) { return true; }, [&](int pos, int idx) { kidx[pos] = idx; });
+    if (tid == 0) w.cnt[(size_t)b * C + c] = nk;
+}
+
+__global__ __launch_bounds__(256) void pc_finish_kernel(const float* boxes, int64_t N, int D, int C, int max_out, PcWs w,
+                                                        float* rows, int32_t* kept, int32_t* count) {
+    __shared__ int pre[BYOLO_MAX_CLASSES + 1];               // kept before class c
+    __shared__ int src[PC_ROWS];                             // source row of each output row of this workgroup, -1 = none
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const int* cnt = w.cnt + (size_t)b * C;
+    for (int c = tid; c < C; c += 256) pre[c + 1] = cnt[c];
+    __syncthreads();
+    if (tid == 0) { int s = 0; for (int c = 0; c < C; ++c) { const int n = pre[c + 1]; pre[c] = s; s += n; } pre[C] = s; }
+    __syncthreads();
+    const int total = pre[C], cap = C * max_out, k0 = blockIdx.x * PC_ROWS;
+    const int nrow = cap - k0 < PC_ROWS ? cap - k0 : PC_ROWS;
+    if (tid < nrow) {
+        const int k = k0 + tid;
+        int idx = -1;
+        if (k < total) {
+            int lo = 0, hi = C - 1;                          // the last class with pre[c] <= k
+            while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (pre[mid] <= k) lo = mid; else hi = mid - 1; }
+            idx = w.kidx[((size_t)b * C + lo) * NMS_MAXK + (k - pre[lo])];
+        }
+        src[tid] = idx;
+        kept[(size_t)b * cap + k] = idx;
+    }
+    __syncthreads();
+    const float* bx = boxes + (size_t)b * N * D;
+    float* ro = rows + ((size_t)b * cap + k0) * D;
+    for (int e = tid; e < nrow * D; e += 256) {
+        const int k = e / D, col = e - k * D;
+        ro[e] = src[k] >= 0 ? bx[(size_t)src[k] * D + col] : 0.f;
+    }
+    if (blockIdx.x == 0 && tid == 0) { count[2 * b] = total; count[2 * b + 1] = cnt[0]; }
+}
+
+static hipError_t launch_per_class_nms(const NmsParams& p, hipStream_t st) {
+    const int C = p.C;
+    if (C < 1 || C > BYOLO_MAX_CLASSES || p.cls_start < 0 || p.cls_start + C > p.D) return hipErrorInvalidValue;
+    if (p.N >= (1ll << 31) || p.ws_bytes < pc_ws_layout(p.B, p.N, C, nullptr, nullptr)) return hipErrorInvalidValue;
+    PcWs w;
+    pc_ws_layout(p.B, p.N, C, reinterpret_cast<char*>(p.ws), &w);
+    const int64_t R = pc_mask_rows(p.N, C);
+    const dim3 by_row((unsigned)((p.N + 255) / 256), p.B), by_tile((unsigned)((p.N + PC_TILE - 1) / PC_TILE), p.B), by_class(C, p.B);
+    if (hipError_t e = hipMemsetAsync(w.hist, 0, (size_t)2 * p.B * (C + 1) * 4, st); e != hipSuccess) return e;
+    if (C <= PC_DIRECT_C)
+        hipLaunchKernelGGL(pc_classify_kernel, by_row, dim3(256), 0, st, p.boxes, p.N, p.D, p.obj_idx, p.cls_start, C, w.cls, w.hist);
+    else
+        hipLaunchKernelGGL(pc_classify_tiled_kernel, by_tile, dim3(256), 0, st, p.boxes, p.N, p.D, p.obj_idx, p.cls_start, C, w.cls, w.hist);
+    hipLaunchKernelGGL(pc_offsets_kernel, dim3(p.B), dim3(64), 0, st, C, p.general_only != 0 ? 1 : 0, w);
+    hipLaunchKernelGGL(pc_scatter_kernel, by_row, dim3(256), 0, st, p.boxes, p.N, p.D, p.obj_idx, C, w);
+    if (!p.general_only) {
+        static std::atomic<uint64_t> sel_attr_done{0}, scan_attr_done{0};
+        const size_t lds = (size_t)NMS_CAP * sizeof(unsigned long long);
+        if (hipError_t e = set_dynamic_lds_once(reinterpret_cast<const void*>(pc_select_kernel), lds, sel_attr_done); e != hipSuccess) return e;
+        const size_t scan_lds = (size_t)2 * 64 * NMS_WORDS * sizeof(unsigned long long);
+        if (hipError_t e = set_dynamic_lds_once(reinterpret_cast<const void*>(pc_scan_kernel), scan_lds, scan_attr_done); e != hipSuccess) return e;
+        hipLaunchKernelGGL(pc_select_kernel, by_class, dim3(1024), lds, st, p.N, C, w);
+        // enough one-wave workgroups to fill the chip's wave slots over the batch, never more than there can be tiles
+        const int64_t mgrid = std::min<int64_t>(pc_max_tiles(p.N, C), std::max(512, std::min(8192, 32768 / p.B)));
+        hipLaunchKernelGGL(pc_matrix_kernel, dim3((unsigned)mgrid, p.B), dim3(64), 0, st, p.boxes, p.N, p.D,
+                           p.iou_thr, C, R, w);
+        hipLaunchKernelGGL(pc_scan_kernel, by_class, dim3(256), scan_lds, st, p.N, C, R, p.max_out, w);
+    }
+    hipLaunchKernelGGL(pc_general_kernel, by_class, dim3(NMS_THREADS), 0, st, p.boxes, p.N, p.D, C, p.max_out, p.iou_thr, w);
+    hipLaunchKernelGGL(pc_finish_kernel, dim3((unsigned)(((int64_t)C * p.max_out + PC_ROWS - 1) / PC_ROWS), p.B), dim3(256), 0, st,
+                       p.boxes, p.N, p.D, C, p.max_out, w, p.rows, p.kept, p.count);
+    return hipGetLastError();
+}
+
 hipError_t launch_sort_nms(const NmsParams& p, hipStream_t st) {
     if (p.max_out > NMS_MAXK || p.max_out < 1) return hipErrorInvalidValue;
+    if (p.per_class) return launch_per_class_nms(p, st);
     const int64_t NP = sort_np(p.N);
     if (p.ws_bytes < nms_workspace_bytes(p.B, p.N)) return hipErrorInvalidValue;
     NmsWs w;

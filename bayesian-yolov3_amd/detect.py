@@ -23,7 +23,9 @@ def _box_op(driver, first_only):
     """One of the reference's three `box_op_*` (`detect.py:21-33`): concat the detection layers' rows and run the
     driver module's NMS; the two non-Bayesian drivers return a batch and the reference takes image 0."""
     def op(model):
-        kept = driver.nms(driver.concat_bbox([d.bbox for d in model.det_layers]), model)
+        # engine_options={'nms_mode': 2}: the per-class NMS (any cls_cnt) instead of the reference's class-blind one
+        per_class = getattr(getattr(model.engine, 'cfg', None), 'nms_mode', 0) == 2
+        kept = (driver.nms_all_classes if per_class else driver.nms)(driver.concat_bbox([d.bbox for d in model.det_layers]), model)
         return kept[0] if first_only else kept
     return op
 

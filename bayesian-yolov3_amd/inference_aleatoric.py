@@ -7,7 +7,7 @@ Same entry points and helpers as the reference: `main()`, `inference(config)`, `
 
 Differences, all additive: `nms` returns a list of per-image row tensors instead of concatenating them
 (the reference's concat needs equal kept counts per image, `inference_aleatoric.py:137-143`); optional keys
-`weights='synthetic'`, `engine_options={'nms_mode': 1}`.
+`weights='synthetic'`, `engine_options={'nms_mode': 1}` (the paper's 2-class NMS) or `{'nms_mode': 2}` (per-class NMS for any `cls_cnt`).
 """
 import json
 import logging
@@ -30,6 +30,12 @@ def nms(boxes, model):
 def nms_per_class(boxes, model):
     # the variant used for the paper (ped iff cls0 > cls1, rider iff cls1 > cls0; NMS 1000 each; ped then rider)
     return _inf.nms(boxes, model, batched=True, two_class=True)
+
+
+def nms_all_classes(boxes, model):
+    # the same for any class count: a row belongs to the class whose score is its strict maximum; NMS 1000 per class;
+    # class 0's kept rows, then class 1's, ... (what `engine_options={'nms_mode': 2}` runs inside the inference loop)
+    return _inf.nms(boxes, model, batched=True, per_class=True)
 
 
 def bbox_to_ecp_format(bbox, img_size, model, config):

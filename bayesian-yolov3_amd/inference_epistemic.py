@@ -8,7 +8,7 @@ Same entry points and helpers as the reference: `main()`, `inference(config)`, `
 
 Differences, all additive: `batch_size > 1` is allowed (every image is reduced over its own T samples;
 the reference asserts 1, `inference_epistemic.py:193`), and optional keys `weights='synthetic'`,
-`seed`, `engine_options={'nms_mode': 1}` (the paper's per-class NMS, reference :104-126).
+`seed`, `engine_options={'nms_mode': 1}` (the paper's per-class NMS, reference :104-126) or `{'nms_mode': 2}` (the same for any `cls_cnt`).
 """
 import json
 import logging
@@ -31,6 +31,12 @@ def nms(boxes, model):
 def nms_per_class(boxes, model):
     # the variant used for the paper (ped iff cls0 > cls1, rider iff cls1 > cls0; NMS 1000 each; ped then rider)
     return _inf.nms(boxes, model, batched=False, two_class=True)
+
+
+def nms_all_classes(boxes, model):
+    # the same for any class count: a row belongs to the class whose score is its strict maximum; NMS 1000 per class;
+    # class 0's kept rows, then class 1's, ... (what `engine_options={'nms_mode': 2}` runs inside the inference loop)
+    return _inf.nms(boxes, model, batched=False, per_class=True)
 
 
 def bbox_to_ecp_format(bbox, img_size, model, config):

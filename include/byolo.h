@@ -43,8 +43,14 @@ typedef struct byolo byolo_t;
 
 /* decode kinds == the three detection-layer factories of lib_yolo/model.py:107 / :132 / :157 */
 enum { BYOLO_DET_STANDARD = 0, BYOLO_DET_ALEATORIC = 1, BYOLO_DET_EPISTEMIC = 2 };
-/* inference_epistemic.py:99-102 (class-agnostic) and :104-126 (commented-out 2-class variant) */
-enum { BYOLO_NMS_AGNOSTIC = 0, BYOLO_NMS_TWO_CLASS = 1 };
+/* inference_epistemic.py:99-102 (class-agnostic) and :104-126 (commented-out 2-class variant); BYOLO_NMS_PER_CLASS is that
+ * variant for any class count: row i belongs to class c iff cls[i][c] > cls[i][k] for every k != c (float32, strictly: a
+ * maximum attained twice or a NaN class score leaves the row in no class; with one class every row is in class 0), one
+ * tf.image.non_max_suppression per class over its members, the kept rows of class 0, 1, ... back to back.  Two classes give
+ * BYOLO_NMS_TWO_CLASS bit for bit, one class BYOLO_NMS_AGNOSTIC.  Limits of the mode: 1 .. BYOLO_NMS_MAX_CLASSES classes (the
+ * class is one byte above the score bits of the sort key, 255 = no class; the decode kernels stop at 128), N < 2^31. */
+enum { BYOLO_NMS_AGNOSTIC = 0, BYOLO_NMS_TWO_CLASS = 1, BYOLO_NMS_PER_CLASS = 2 };
+#define BYOLO_NMS_MAX_CLASSES 128
 /* normaliser list of lib_yolo/layers.py:556-571 */
 enum { BYOLO_NORM_BN = 1, BYOLO_NORM_DROPOUT = 2 };
 
@@ -233,6 +239,8 @@ BYOLO_API int32_t byolo_plan_tensor(byolo_t* h, int32_t tensor, int64_t* offset,
  *   d_rows    [B,max_out*(1|2),D]   NMS-kept rows, score order (2-class: ped rows then rider rows)
  *   d_kept    [B,max_out*(1|2)]     int32 global box indices of the kept rows
  *   d_count   [B,2]                 int32 {total kept, kept in first class (== total if agnostic)}
+ *   BYOLO_NMS_PER_CLASS: d_rows [B,cls_cnt*max_out,D], d_kept [B,cls_cnt*max_out] (class 0's kept rows, then class 1's, ...;
+ *   zero rows / -1 behind the last), d_count as above; the kept-per-class counts [B,cls_cnt]: byolo_nms_class_counts.
  * seed: dropout stream (see csrc/byolo_rng.h); dropout is active iff the layer has
  * BYOLO_NORM_DROPOUT and `dropout_on` != 0 (standard_test_dropout=True quirk, layers.py:567-568).
  * d_mask_bits (nullable): INJECTED dropout masks instead of the library's counter stream -- tf.layers.dropout draws
@@ -318,8 +326,17 @@ BYOLO_API int32_t byolo_epistemic_stats(byolo_t* h, const float* d_raw, int32_t 
                                         float* d_ev_loc, float* d_epi_covar, float* d_obj_samples, float* d_cls_samples,
                                         void* stream);
 /* tf.image.non_max_suppression + tf.gather per image on d_boxes [B,N,D] (scores = column obj_idx).
- * d_sort_ws: >= byolo_nms_workspace_bytes(B, N). */
+ * d_sort_ws: >= byolo_nms_workspace_bytes(B, N); BYOLO_NMS_PER_CLASS: >= byolo_nms_workspace_bytes_ex(B, N, nms_mode, cls_cnt)
+ * (the other modes: the same value as byolo_nms_workspace_bytes; 0 for arguments the mode refuses).  The per-class mode takes
+ * its class count from the handle (byolo_cfg.cls_cnt), reads the class scores in columns cls_start_idx .. cls_start_idx +
+ * cls_cnt - 1 and sizes d_rows / d_kept by cls_cnt * max_out per image (see byolo_forward).  Refused with BYOLO_ERR_ARG before
+ * anything is launched: an unknown mode, class columns outside the row, max_out above 2048 (the limit PER CLASS).
+ * byolo_nms_class_counts: the kept-per-class counts [B,cls_cnt] int32 of the handle's LAST per-class NMS (byolo_sort_nms or
+ * byolo_forward with d_rows), copied to d_class_counts on `stream` (order it behind that call); B and cls_cnt must be that
+ * call's.  BYOLO_ERR_STATE before the first such call. */
 BYOLO_API size_t  byolo_nms_workspace_bytes(int32_t B, int64_t N);
+BYOLO_API size_t  byolo_nms_workspace_bytes_ex(int32_t B, int64_t N, int32_t nms_mode, int32_t cls_cnt);
+BYOLO_API int32_t byolo_nms_class_counts(byolo_t* h, int32_t* d_class_counts, int32_t B, int32_t cls_cnt, void* stream);
 BYOLO_API int32_t byolo_sort_nms(byolo_t* h, const float* d_boxes, int32_t B, int64_t N, int32_t D, int32_t obj_idx,
                        int32_t cls_start_idx, int32_t nms_mode, int32_t max_out, float iou_thresh,
                        void* d_sort_ws, size_t ws_bytes,

@@ -1,10 +1,12 @@
 #!/usr/bin/env python
-"""soak_nms.py -- randomised sweep of the tail (score sort + greedy NMS + gather: tf.image.non_max_suppression and
-the 2-class variant, inference_epistemic.py:99-128) on the GPU against the oracle NMS: kept indices, gathered rows
+"""soak_nms.py -- randomised sweep of the tail (score sort + greedy NMS + gather: tf.image.non_max_suppression, the
+2-class variant, inference_epistemic.py:99-128, and the per-class mode for any class count) on the GPU against the oracle
+NMS (the per-class mode: its composition over the classes, tests/_nms_per_class_ref.py): kept indices, gathered rows
 and counts bit-exact.  Random box counts 1 .. 130 000, row widths, batch sizes, max_out, IoU thresholds and box
 populations built to hit every path of tail_kernels.hip (bit-matrix fast path on a 4096 prefix, radix-select overflow
 on mass ties, prefix exhaustion under heavy clustering, the general fallback): spread / clustered / identical boxes,
-tied scores, zero-area and flipped corners, NaN and +-inf scores and coordinates.
+tied scores, zero-area and flipped corners, NaN and +-inf scores and coordinates; in the per-class mode 1 .. 128 classes with
+tied, NaN, skewed and empty class-score columns.
 
     python tools/soak_nms.py --cases 200 --seed 1 > gpurun_out/soak_nms.md
 
@@ -19,6 +21,7 @@ import numpy as np
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "bayesian-yolov3_amd"))
+sys.path.insert(0, os.path.join(REPO, "tests"))
 
 
 def make_rows(g, B, N, D, obj_idx, cls_start):
@@ -65,26 +68,56 @@ def make_rows(g, B, N, D, obj_idx, cls_start):
     return rows, kinds
 
 
-def one_case(g, idx):
+def class_scores(g, rows, cls_start, C):
+    """Per-class mode: class-score populations per image -- ties at the maximum, NaN, one dominant class, empty classes."""
+    kinds = []
+    for b in range(rows.shape[0]):
+        cls = rows[b, :, cls_start:cls_start + C]
+        kind = g.choice(["random", "rounded", "some_nan", "skewed", "empty", "all_equal"])
+        if kind == "rounded":
+            cls[...] = np.round(cls, int(g.integers(1, 3)))
+        elif kind == "some_nan":
+            cls[g.random(cls.shape) < 0.02] = np.nan
+        elif kind == "skewed":
+            cls[:, int(g.integers(0, C))] += (np.float32(0.6) * (g.random(len(cls)) < 0.5)).astype(np.float32)
+        elif kind == "empty":
+            cls[:, g.random(C) < 0.5] = -1.0
+        elif kind == "all_equal":
+            cls[...] = 0.5
+        kinds.append(kind)
+    return kinds
+
+
+def one_case(g, idx, modes):
     import torch
     from byolo import Engine
     from oracle import nms_ref
+    import _nms_per_class_ref as pcr
     B = int(g.integers(1, 4))
     N = int(g.choice([1, 2, 63, 64, 65, 1000, 4095, 4096, 4097, 8193, 22743, 64512, 120960, int(g.integers(1, 130000))]))
     D = int(g.choice([7, 16, 23]))
     obj_idx, cls_start = {7: (4, 5), 16: (9, 11), 23: (14, 17)}[D]
-    two = bool(g.integers(0, 2))
+    mode = int(g.choice(modes))
+    two = mode == 1
+    C = int(g.choice([1, 2, 3, 5, 20, 80, 128])) if mode == 2 else 2
+    if mode == 2:
+        D = cls_start + C + int(g.integers(0, 3))
     max_out = int(g.choice([1, 10, 100, 1000, 1000, 1000, 2048]))       # the ABI takes 1 .. 2048
     iou = float(g.choice([0.5, 0.5, 0.5, 0.3, 0.7, 0.0, 1.0]))
     rows, kinds = make_rows(g, B, N, D, obj_idx, cls_start)
+    if mode == 2:
+        kinds = ["%s/%s" % kc for kc in zip(kinds, class_scores(g, rows, cls_start, C))]
     t0 = time.time()
-    eng = Engine((64, 64, 3), 2, nms_mode=1 if two else 0, max_out=max_out, iou_thresh=iou)
+    eng = Engine((64, 64, 3), C, nms_mode=mode, max_out=max_out, iou_thresh=iou)
     res = eng.sort_nms(torch.from_numpy(rows).cuda(), obj_idx=obj_idx, cls_start_idx=cls_start)
     torch.cuda.synchronize()
     kept, count, out = res["kept"].cpu().numpy(), res["count"].cpu().numpy(), res["rows"].cpu().numpy()
     tot = []
     for b in range(B):
-        if two:
+        if mode == 2:
+            r_rows, r_keep, per_class = pcr.nms_per_class(rows[b], obj_idx, cls_start, C, max_out, iou); n_ped = int(per_class[0])
+            assert np.array_equal(res["class_counts"][b].cpu().numpy(), per_class), "image %d (%s): kept per class" % (b, kinds[b])
+        elif two:
             r_rows, r_keep, n_ped = nms_ref.nms_two_class(rows[b], obj_idx, cls_start, max_out, iou)
         else:
             r_rows, r_keep = nms_ref.nms_agnostic(rows[b], obj_idx, max_out, iou); n_ped = len(r_keep)
@@ -96,7 +129,7 @@ def one_case(g, idx):
         assert (kept[b, n:] == -1).all() and (out[b, n:] == 0).all()
         tot.append(n)
     eng.close()
-    return "| %d | %d | %d | %d | %s | %d | %.1f | %s | %s | %.1f |" % (idx, B, N, D, "2-class" if two else "agnostic", max_out, iou,
+    return "| %d | %d | %d | %d | %s | %d | %.1f | %s | %s | %.1f |" % (idx, B, N, D, ("agnostic", "2-class", "per-class C=%d" % C)[mode], max_out, iou,
                                                                  " ".join(kinds), tot, time.time() - t0)
 
 
@@ -104,13 +137,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", type=int, default=100)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--modes", default="0,1,2", help="the BYOLO_NMS_* modes to draw from")
     a = ap.parse_args()
     g = np.random.default_rng(a.seed)
     print("| # | B | N | D | mode | max_out | IoU | boxes / scores per image | kept | s |\n|---|---|---|---|---|---|---|---|---|---|")
     bad = 0
     for i in range(a.cases):
         try:
-            print(one_case(g, i), flush=True)
+            print(one_case(g, i, [int(m) for m in a.modes.split(",")]), flush=True)
         except Exception as e:
             bad += 1
             print("| %d | FAILED: %s |" % (i, str(e).replace("\n", " ")[:300]), flush=True)

@@ -38,7 +38,7 @@ def one_case(rng, idx, a):
         B = int(rng.integers(1, a.max_B + 1))
         if (H // 32) * (W // 32) * B * max(T, 3) <= a.budget:
             break
-    nms_mode = int(rng.integers(0, 2)) if cls_cnt == 2 else 0      # the 2-class mode is defined for C = 2
+    nms_mode = int(rng.choice([0, 1, 2] if cls_cnt == 2 else [0, 2]))      # the 2-class mode is defined for C = 2, the per-class one for every C
     env = {"BYOLO_WINOGRAD": str(rng.choice(["", "0", "2"])), "BYOLO_WINO_FUSED": str(rng.choice(["", "0", "2"])),
            "BYOLO_KSPLIT": str(rng.choice(["", "", "0", "2", "3", "5"])),
            "BYOLO_WINO_CHUNK_MB": str(rng.choice(["", "", "1", "8", "64"])),       # small budgets: many chunks per layer
@@ -93,7 +93,13 @@ def one_case(rng, idx, a):
         float(u_gpu.max()), float(u_cpu.max()))
     err = "%.2f / %.2f" % (float(u_gpu.max()), float(u_cpu.max()))
     # tail in isolation, bit-exact on the GPU's own rows
-    refn = cpu_ref.nms_batch(torch.from_numpy(boxes), variant, max_out=1000, two_class=bool(nms_mode), cls_cnt=cls_cnt)
+    if nms_mode == 2:                       # the per-class mode: the composition of the oracle NMS over the classes
+        import _nms_per_class_ref as pcr
+        _, obj_idx, cs = cpu_ref.row_layout(variant, cls_cnt)
+        refn = [pcr.nms_per_class(boxes[b], obj_idx, cs, cls_cnt) for b in range(B)]
+        assert np.array_equal(out["class_counts"].cpu().numpy(), np.stack([r[2] for r in refn])), "case %d: kept per class" % idx
+    else:
+        refn = cpu_ref.nms_batch(torch.from_numpy(boxes), variant, max_out=1000, two_class=bool(nms_mode), cls_cnt=cls_cnt)
     kept, count, rows = out["kept"].cpu().numpy(), out["count"].cpu().numpy(), out["rows"].cpu().numpy()
     for b in range(B):
         n = int(count[b, 0])
