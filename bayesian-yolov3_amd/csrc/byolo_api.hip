@@ -65,7 +65,7 @@ static void plan_opts_defaults(byolo_plan_opts& o) {
     o.struct_bytes = (int32_t)sizeof o;
     o.graphs = 1; o.serialize_convs = 1; o.serialize_heads = 1; o.dedup = 1; o.lowmain = 1; o.kx3 = 1; o.p1 = 1; o.b2b = 1; o.kx3_wide = 0;
     o.wino_split = 1; o.wino_split_min_c = 256; o.wino_split_bn = 0; o.wino_split_rounds = 0;
-    o.winograd = 1; o.wino_fused = 1; o.stream1x1 = 1; o.gemm_stream = 1; o.ksplit = -1; o.streamk = 1; o.plain_epilogue = 1; o.wino_split_persist = 0;
+    o.winograd = 1; o.wino_fused = 1; o.stream1x1 = 1; o.gemm_stream = 1; o.ksplit = -1; o.streamk = 1; o.plain_epilogue = 1; o.wino_split_persist = 0; o.wino_split_feed = 3;
     o.wino_split_min_gflop = 30.f; o.wino_split_chunk_mb = 1500.f; o.wino_min_gflop = 10.f; o.wino_chunk_mb = 800.f; o.wino_min_ratio = 80.f;
 }
 // The environment is the default filler of a NEW handle and nothing else: the A/B scripts under tools/ and the tests set a variable,
@@ -79,7 +79,7 @@ static void plan_opts_from_env(byolo_plan_opts& o) {
     geti("BYOLO_WINO_SPLIT", o.wino_split); geti("BYOLO_WINO_SPLIT_MIN_C", o.wino_split_min_c); geti("BYOLO_WINO_SPLIT_BN", o.wino_split_bn);
     geti("BYOLO_WINO_SPLIT_ROUNDS", o.wino_split_rounds); geti("BYOLO_WINOGRAD", o.winograd);
     geti("BYOLO_WINO_FUSED", o.wino_fused); geti("BYOLO_STREAM1X1", o.stream1x1); geti("BYOLO_GEMM_STREAM", o.gemm_stream);
-    geti("BYOLO_KSPLIT", o.ksplit); geti("BYOLO_STREAMK", o.streamk); geti("BYOLO_PLAIN_EPILOGUE", o.plain_epilogue); geti("BYOLO_WINO_SPLIT_PERSIST", o.wino_split_persist);
+    geti("BYOLO_KSPLIT", o.ksplit); geti("BYOLO_STREAMK", o.streamk); geti("BYOLO_PLAIN_EPILOGUE", o.plain_epilogue); geti("BYOLO_WINO_SPLIT_PERSIST", o.wino_split_persist); geti("BYOLO_WINO_SPLIT_FEED", o.wino_split_feed);
     geti("BYOLO_WSHIFT_PER_LAYER", o.wshift_per_layer); geti("BYOLO_NMS_GENERAL", o.nms_general);
     getf("BYOLO_WINO_SPLIT_MIN_GFLOP", o.wino_split_min_gflop); getf("BYOLO_WINO_SPLIT_CHUNK_MB", o.wino_split_chunk_mb);
     getf("BYOLO_WINO_MIN_GFLOP", o.wino_min_gflop); getf("BYOLO_WINO_CHUNK_MB", o.wino_chunk_mb); getf("BYOLO_WINO_MIN_RATIO", o.wino_min_ratio);
@@ -106,7 +106,7 @@ extern "C" int32_t byolo_set_plan_opts(byolo_t* h, const byolo_plan_opts* o) {
     if (o->graphs < 0 || o->graphs > 2 || o->serialize_convs < 0 || o->serialize_convs > 2 || o->b2b < 0 || o->b2b > 2 || o->kx3_wide < 0 || o->kx3_wide > 2 ||
         o->wino_split < 0 || o->wino_split > 2 || o->winograd < 0 || o->winograd > 2 || o->wino_fused < 0 || o->wino_fused > 2 || o->stream1x1 < 0 || o->stream1x1 > 2 ||
         o->streamk < 0 || o->streamk > 2 || o->ksplit < -1 || o->ksplit > 64 || (o->wino_split_bn != 0 && o->wino_split_bn != 128 && o->wino_split_bn != 256) ||
-        o->wino_split_rounds < 0 || o->wino_split_persist < 0 || o->wino_split_persist > 2 || !(o->wino_split_chunk_mb > 0.f) || !(o->wino_chunk_mb > 0.f) || !(o->wino_split_min_gflop >= 0.f) || !(o->wino_min_gflop >= 0.f) || !(o->wino_min_ratio >= 0.f))
+        o->wino_split_rounds < 0 || o->wino_split_persist < 0 || o->wino_split_persist > 2 || o->wino_split_feed < 0 || o->wino_split_feed > 3 || !(o->wino_split_chunk_mb > 0.f) || !(o->wino_chunk_mb > 0.f) || !(o->wino_split_min_gflop >= 0.f) || !(o->wino_min_gflop >= 0.f) || !(o->wino_min_ratio >= 0.f))
         return fail(h, BYOLO_ERR_ARG, "byolo_set_plan_opts: a field outside its range (include/byolo.h)");
     const byolo_plan_opts& c = h->opts;
     // what byolo_lower / byolo_finalize have baked into steps and packed weights
@@ -485,6 +485,9 @@ static int32_t lower_once(byolo_t* h) {
             if (all_tile && l.drop_ordinal >= 0 && l.fused_residual < 0) {
                 st.mode = STEP_REP;                          // conv once per image, T masked epilogues
                 for (int k = 0; k < st.in.n; ++k) st.in.s[k].tile = false;
+                h->aux.push_back({l.H, l.W, l.filters});     // the raw accumulators per image, for a plan that replays inside the reader's transform
+                st.raw_tensor = n + (int)h->aux.size() - 1;
+                h->last_use.push_back(-1);
             } else if (st.in.n == 2 && any_tile && !all_tile) {
                 const int kt = st.in.s[0].tile ? 0 : 1;      // the tiled (T-invariant) source
                 Step part; part.layer = i; part.mode = STEP_PARTIAL;
@@ -604,7 +607,7 @@ static void fill_conv(const byolo_t* h, const Step& st, const float* d_img, char
     p.wpk = dptr(h, st.w_off);
     if (st.mode == STEP_PARTIAL) { p.scale = h->d_ones; p.shift = h->d_zeros; }      // raw accumulators
     else { p.scale = dptr(h, l.scale_off); p.shift = dptr(h, l.shift_off); }
-    p.dst = reinterpret_cast<float*>(ws + h->plan.off[st.out_tensor]);
+    p.dst = h->plan.off[st.out_tensor] >= 0 ? reinterpret_cast<float*>(ws + h->plan.off[st.out_tensor]) : nullptr;      // (none: a STEP_REP folded into its reader stores into Step::raw_tensor instead, Plan::feed)
     // buffer-descriptor extents (check_run bounds every tensor by CONV_MAX_SRC_BYTES) and the launch-constant divisors
     p.src0_bytes = (uint32_t)((uint64_t)nsrc[0] * Hs[0] * Wsz[0] * Cs[0] * 4);
     p.src1_bytes = Cs[1] ? (uint32_t)((uint64_t)nsrc[1] * Hs[1] * Wsz[1] * Cs[1] * 4) : p.src0_bytes;
@@ -632,7 +635,7 @@ static void fill_finish(const byolo_t* h, const Step& st, char* ws, int B, int T
     memset(&f, 0, sizeof f);
     f.low = reinterpret_cast<const float*>(ws + h->plan.off[st.low_tensor]);
     f.part = st.addend_tensor >= 0 ? reinterpret_cast<const float*>(ws + h->plan.off[st.addend_tensor]) : nullptr;
-    f.dst = reinterpret_cast<float*>(ws + h->plan.off[st.out_tensor]);
+    f.dst = h->plan.off[st.out_tensor] >= 0 ? reinterpret_cast<float*>(ws + h->plan.off[st.out_tensor]) : nullptr;      // (none: the plan folded this step into its reader, Plan::feed)
     f.T = l.stacked ? T : 1; f.S = B * f.T; f.H = l.H; f.W = l.W; f.N = l.filters;
     f.mode = mode;
     if (mode == 0) { f.scale = h->d_ones; f.shift = h->d_zeros; }
@@ -768,8 +771,9 @@ static int32_t run_winograd(byolo_t* h, const Step& s, const Layer& l, const Con
 // One 3x3 / stride-1 convolution as Winograd F(2x2,3x3) in split-f16 arithmetic (wino_split.hip): per chunk of samples the input
 // transform and ONE launch of GEMM + output transform + epilogue.  `c` = the ConvParams of the direct launch.
 // Profile variants: -4 the transform, 140 the fused launch (carries the direct-convolution FLOPs of its samples).
+// `feed`: null, or a WinoParams holding the feed / src_ fields of the element-wise step the transform evaluates itself (Plan::feed).
 static int32_t run_wino_split(byolo_t* h, const Step& s, const Layer& l, const ConvParams& c, const WinoPlan& wp, double algo_flops,
-                              char* ws, hipStream_t st) {
+                              char* ws, hipStream_t st, const WinoParams* feed = nullptr) {
     const bool prof = h->profiling >= 2;
     int32_t rc;
     const int S = c.M / (l.H * l.W), tt = wp.th * wp.tw;
@@ -778,7 +782,8 @@ static int32_t run_wino_split(byolo_t* h, const Step& s, const Layer& l, const C
     for (int s0 = 0; s0 < S; s0 += wp.chunk) {
         const int ns = std::min(wp.chunk, S - s0);
         WinoParams w; memset(&w, 0, sizeof w);
-        w.x = c.src0; w.v = V;
+        if (feed) w = *feed;
+        w.x = feed ? nullptr : c.src0; w.v = V;
         w.H = l.H; w.W = l.W; w.C = c.C0; w.N = c.N; w.th = wp.th; w.tw = wp.tw;
         w.s0 = s0; w.P = ns * tt; w.P_pad = (int)align_up((size_t)w.P, 128);
         w.d_tt = make_fastdiv((uint32_t)tt); w.d_tw = make_fastdiv((uint32_t)wp.tw);
@@ -1184,6 +1189,44 @@ static int32_t enqueue_forward(byolo_t* h, const FwdArgs& a, hipStream_t st, boo
         algo = (s.mode == STEP_PARTIAL && !s.low) ? 0.0 : 2.0 * (double)(S_all * l.H * l.W) * l.filters * (double)(l.ksize * l.ksize * l.Cin);      // (the `low` launch carries the layer's)
         return BYOLO_OK;
     };
+    // a STEP_FINISH step's parameters: what its launch takes, or -- folded into its reader -- what that reader's input transform takes
+    auto finish_params = [&](const Step& s, FinishParams& f) -> int32_t {
+        const Layer& l = h->layers[s.layer];
+        byolo_drop_keys keys{0, 0, 0};
+        const bool drop = l.drop_ordinal >= 0 && dropout_on;
+        const uint32_t* bits = nullptr;
+        if (drop) {
+            keys = byolo_layer_keys(seed, (uint32_t)l.drop_ordinal, (double)h->cfg.drop_prob);
+            if (inject) {
+                int64_t n_el = 0;
+                const int64_t off = mask_layout(h, B, T, l.drop_ordinal, &n_el);
+                if (n_el >= ((int64_t)1 << 32)) return fail(h, BYOLO_ERR_ARG, "byolo_forward: injected masks index a dropout tensor with 32 bits; layer '%s' has %lld elements", l.scope.c_str(), (long long)n_el);
+                bits = d_mask_bits + off / 32;
+            }
+        }
+        fill_finish(h, s, ws, B, T, h->precision == 1 ? 2 : 1, drop, keys, bits, inject, f);
+        return BYOLO_OK;
+    };
+    // the src_ fields of a convolution whose input transform evaluates the step in front of it (Plan::feed_src)
+    auto feed_params = [&](size_t pi, WinoParams& w) -> int32_t {
+        const Step& ps = h->steps[pi];
+        memset(&w, 0, sizeof w);
+        w.feed = h->plan.feed[pi];
+        if (w.feed == 1) {                                      // the replayed epilogue of the per-image convolution, as its own launch would run it
+            ConvParams c; int tile = 0; double algo = 0.0;
+            int32_t rc = prep(pi, c, tile, algo); if (rc) return rc;
+            w.src_low = reinterpret_cast<const float*>(ws + h->plan.off[ps.raw_tensor]); w.src_T = T;
+            w.src_scale = c.scale; w.src_shift = c.shift; w.src_flags = c.flags; w.src_k0 = c.k0; w.src_k1 = c.k1; w.src_thr = c.thr;
+            w.src_idx_base = c.idx_base; w.src_mask_bits = c.mask_bits; w.src_status = c.status; w.src_layer_idx = c.layer_idx;
+        } else {
+            FinishParams f;
+            int32_t rc = finish_params(ps, f); if (rc) return rc;
+            w.src_low = f.low; w.src_part = f.part; w.src_T = f.T;
+            w.src_scale = f.scale; w.src_shift = f.shift; w.src_flags = f.flags; w.src_k0 = f.k0; w.src_k1 = f.k1; w.src_thr = f.thr;
+            w.src_idx_base = f.idx_base; w.src_mask_bits = f.mask_bits; w.src_status = f.status; w.src_layer_idx = f.layer_idx;
+        }
+        return BYOLO_OK;
+    };
     for (size_t si = 0; si < h->steps.size(); ++si) {
         const Step& s = h->steps[si];
         const Layer& l = h->layers[s.layer];
@@ -1193,21 +1236,10 @@ static int32_t enqueue_forward(byolo_t* h, const FwdArgs& a, hipStream_t st, boo
             HIPCHK(h, hipEventRecord(h->wslot().ev[1], st)); backbone_marked = true;
         }
         ConvParams p;
+        if (h->plan.feed[si] == 2) continue;                    // its reader's input transform finishes the two halves (Plan::feed)
         if (s.mode == STEP_FINISH) {
             FinishParams f;
-            byolo_drop_keys keys{0, 0, 0};
-            const bool drop = l.drop_ordinal >= 0 && dropout_on;
-            const uint32_t* bits = nullptr;
-            if (drop) {
-                keys = byolo_layer_keys(seed, (uint32_t)l.drop_ordinal, (double)h->cfg.drop_prob);
-                if (inject) {
-                    int64_t n_el = 0;
-                    const int64_t off = mask_layout(h, B, T, l.drop_ordinal, &n_el);
-                    if (n_el >= ((int64_t)1 << 32)) return fail(h, BYOLO_ERR_ARG, "byolo_forward: injected masks index a dropout tensor with 32 bits; layer '%s' has %lld elements", l.scope.c_str(), (long long)n_el);
-                    bits = d_mask_bits + off / 32;
-                }
-            }
-            fill_finish(h, s, ws, B, T, h->precision == 1 ? 2 : 1, drop, keys, bits, inject, f);
+            rc = finish_params(s, f); if (rc) return rc;
             if (per_step) { rc = mark_launch(h, s.layer, -5, (int64_t)f.S * f.H * f.W, f.N, 0, 0.0, st); if (rc) return rc; }
             HIPCHK(h, launch_finish_upsampled(f, st));
             continue;
@@ -1215,6 +1247,10 @@ static int32_t enqueue_forward(byolo_t* h, const FwdArgs& a, hipStream_t st, boo
         if (!s.is_conv()) { fill_conv(h, s, d_img, ws, B, T, p); rc = run_aux_step(h, s, p, st); if (rc) return rc; continue; }
         int tile = 0; double algo = 0.0;
         rc = prep(si, p, tile, algo); if (rc) return rc;
+        if (h->plan.feed[si] == 1) {                            // the T replays run inside the reader's input transform: raw accumulators, once per image
+            p.flags = EPI_RAW; p.rep = 1; p.scale = h->d_ones; p.shift = h->d_zeros; p.mask_bits = nullptr;
+            p.dst = reinterpret_cast<float*>(ws + h->plan.off[s.raw_tensor]);
+        }
         const ConvSplit& sp = h->plan.split[si];
         if (h->plan.fuse[si]) {
             // back-to-back: the next step (the 1x1 convolution / detection head that alone reads this output) inside this launch
@@ -1228,7 +1264,13 @@ static int32_t enqueue_forward(byolo_t* h, const FwdArgs& a, hipStream_t st, boo
             ++si;                                               // the follower is done
             continue;
         }
-        if (h->plan.wino[si].chunk > 0 && h->precision == 1) { rc = run_wino_split(h, s, l, p, h->plan.wino[si], algo, ws, st); if (rc) return rc; continue; }
+        if (h->plan.wino[si].chunk > 0 && h->precision == 1) {
+            WinoParams fw;
+            const bool fed = h->plan.feed_src[si] >= 0;
+            if (fed) { rc = feed_params((size_t)h->plan.feed_src[si], fw); if (rc) return rc; }
+            rc = run_wino_split(h, s, l, p, h->plan.wino[si], algo, ws, st, fed ? &fw : nullptr); if (rc) return rc;
+            continue;
+        }
         if (h->plan.wino[si].chunk > 0) { rc = run_winograd(h, s, l, p, h->plan.wino[si], tile, algo, ws, st); if (rc) return rc; continue; }
         if (h->plan.stream1x1[si]) {                            // row-streaming 1x1 convolution / detection head
             const int bn = h->plan.stream1x1[si];
@@ -1482,6 +1524,15 @@ static int32_t calibrate_bn_impl(byolo_t* h, const float* d_img, int32_t B, void
     if (!d_img || !d_workspace) return fail(h, BYOLO_ERR_ARG, "byolo_calibrate_bn: null argument");
     make_plan(h, B, 1);
     if (workspace_bytes < h->plan.total) return fail(h, BYOLO_ERR_NOMEM, "byolo_calibrate_bn: workspace %zu < %zu", workspace_bytes, h->plan.total);
+    // Calibration runs every step as a launch of its own and needs the tensors a forward's plan folds away (Plan::feed).  At T = 1 the
+    // operand such a step leaves to its reader has the folded tensor's extent and lifetime -- a STEP_REP's raw accumulators [B, H, W, N],
+    // a STEP_FINISH's per-image partial sums, which its element-wise launch may finish in place -- so the tensor takes that memory
+    // here; the doctored plan is dropped when the calibration returns (byolo_calibrate_bn).
+    for (size_t si = 0; si < h->steps.size(); ++si) {
+        const Step& s = h->steps[si];
+        if (h->plan.feed[si] == 1) h->plan.off[s.out_tensor] = h->plan.off[s.raw_tensor];
+        else if (h->plan.feed[si] == 2) h->plan.off[s.out_tensor] = h->plan.off[s.addend_tensor];
+    }
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     char* ws = reinterpret_cast<char*>(d_workspace);
@@ -1548,7 +1599,11 @@ static int32_t calibrate_bn_impl(byolo_t* h, const float* d_img, int32_t B, void
 }
 extern "C" int32_t byolo_calibrate_bn(byolo_t* h, const float* d_img, int32_t B, void* d_workspace, size_t workspace_bytes,
                                       void* stream) {
-    return guarded(h, "byolo_calibrate_bn", [&] { return calibrate_bn_impl(h, d_img, B, d_workspace, workspace_bytes, stream); });
+    return guarded(h, "byolo_calibrate_bn", [&] {
+        const int32_t rc = calibrate_bn_impl(h, d_img, B, d_workspace, workspace_bytes, stream);
+        if (h) h->plan.B = -1;                                  // (the next call plans again: calibrate_bn_impl gives folded tensors memory)
+        return rc;
+    });
 }
 
 // ------------------------------------------------------------------------------------------------

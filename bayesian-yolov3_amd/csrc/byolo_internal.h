@@ -104,6 +104,8 @@ struct Step {
     int addend_tensor = -1;        // STEP_MAIN / STEP_FINISH: the PARTIAL result
     bool low = false;              // STEP_PARTIAL: the stacked half at the source's resolution (per sample, output H/2 x W/2)
     int low_tensor = -1;           // STEP_FINISH: that launch's result
+    int raw_tensor = -1;           // STEP_REP: the per-image raw accumulators [B, H, W, N] the launch stores instead of its T replays when the plan
+                                   // folds the replay into the reader's Winograd input transform (Plan::feed; memory only in such a plan)
     size_t w_off = 0; int Npad = 0, tile = 0;   // packed weights of this launch
     bool wino_ok = false;          // 3x3 / stride 1 over one plain source: Winograd F(2x2,3x3) is possible
     size_t wino_off = 0;           // the 16 transformed weight matrices U[xi], each packed [Cin/32][Npad][32]
@@ -125,6 +127,12 @@ struct Plan {
     std::vector<WinoPlan> wino;    // per step
     std::vector<int> stream1x1;    // per step: tile width of the row-streaming 1x1 launch (gemm_stream.hip), 0 = conv_igemm
     std::vector<char> fuse;        // per step: the NEXT step (a 1x1 convolution / detection head reading only this output) runs inside this launch
+    // The element-wise pass in front of a split-f16 Winograd convolution folded into that convolution's input transform
+    // (opts.wino_split_feed; wino_split.hip): feed[si] = 1 a STEP_REP whose launch stores raw accumulators once per image (into
+    // Step::raw_tensor), 2 a STEP_FINISH that is not launched at all; the step's own output tensor has no memory in this plan.
+    // feed_src[ri] = that producer step for the reading convolution's step ri, else -1.
+    std::vector<char> feed;
+    std::vector<int> feed_src;
     size_t wino_off = 0;           // scratch for V and M of one chunk (shared by all steps)
 };
 static constexpr int CNT_PER_STEP = 1024;      // >= resident workgroups of any tile configuration

@@ -127,6 +127,16 @@ struct WinoParams {
     int flags; uint32_t k0, k1, thr; uint64_t idx_base;
     FastDiv d_tt, d_tw, d_c4, d_n4;   // th*tw, tw, C/4, N/4
     float vmul;                       // split precision (wino_split.hip): V = vmul * (B^T d B) of the stored hi + lo values
+    // split precision, wino_split.hip: the input transform evaluates the element-wise pass in front of the convolution itself (feed != 0;
+    // byolo_plan.hip Plan::feed) -- x is not read; the value at (sample s, y, x) is that pass's epilogue, with ITS scale / shift /
+    // dropout keys / element index / status words, passed through the hi/lo encoding in registers:
+    //   1  the T-fold replay of a per-image convolution: src_low = its raw accumulators [images, H, W, C], sample s reads image s / src_T
+    //   2  the finish of a 1x1 convolution over an upsampled source (FinishParams): src_low [S, H/2, W/2, C] + src_part [S / src_T, H, W, C] (or null)
+    int feed, src_T;
+    const float* src_low; const float* src_part;
+    const float* src_scale; const float* src_shift;
+    int src_flags; uint32_t src_k0, src_k1, src_thr; uint64_t src_idx_base; const uint32_t* src_mask_bits;
+    unsigned* src_status; int src_layer_idx;
 };
 // Winograd F(2x2,3x3) in split-f16 arithmetic (wino_split.hip): V [16][P_pad x C, K-tile major inside a plane: v_index()] as hi/lo groups -> output [S,H,W,N] as hi/lo
 // groups, GEMM + output transform + epilogue in one launch of P_pad / 128 * N / 128 workgroups

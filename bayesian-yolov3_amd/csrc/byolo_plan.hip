@@ -106,66 +106,6 @@ void make_plan(byolo_t* h, int B, int T, bool inject) {
               p.fuse[si] = 1;
       }
     }
-    for (int si = 0; si < (int)h->steps.size(); ++si) {
-        const Layer& l = h->layers[h->steps[si].layer];
-        const int t = h->steps[si].out_tensor;
-        if (!(si > 0 && p.fuse[si - 1])) p.off[t] = alloc(tensor_bytes(h, t, B, T));      // (a fused follower's output exists since the step before)
-        if (p.fuse[si]) { const int t2 = h->steps[si + 1].out_tensor; p.off[t2] = alloc(tensor_bytes(h, t2, B, T)); }
-        if (h->cfg.keep_all_outputs) continue;
-        for (int k = 0; k < n; ++k)
-            if (p.off[k] >= 0 && h->last_use[k] == si) release(p.off[k], tensor_bytes(h, k, B, T));
-        if (h->last_use[t] < 0 && l.op != OP_DETECTION) release(p.off[t], tensor_bytes(h, t, B, T));   // dead output
-    }
-    // detection raw outputs must survive until their decode (same step) -> they are released one step
-    // late by construction (last_use == -1 handled below): keep them simple: never reuse det outputs.
-    p.arena = align_up((size_t)end, 256);
-    p.boxes_off = p.arena;
-    size_t o = p.boxes_off + align_up((size_t)B * h->n_boxes * h->row_len * sizeof(float), 256);
-    p.nms_off = o; o += align_up(nms_workspace_bytes_ex(B, h->n_boxes, h->cfg.nms_mode == BYOLO_NMS_PER_CLASS, h->cfg.cls_cnt), 256);
-    p.stats_off = o; o += align_up((size_t)1024 * 2 * h->maxC * sizeof(double) + 2 * h->maxC * sizeof(float), 256);
-    p.img_split_off = o; if (h->img_split) o += align_up((size_t)B * h->cfg.img_h * h->cfg.img_w * h->cfg.img_c * sizeof(float), 256);
-    // launch geometry per step: tile configuration and the split-K of the last partial round (shape-only)
-    p.split.assign(h->steps.size(), ConvSplit{0, 0, 0, 1});
-    p.tile.assign(h->steps.size(), 0);
-    size_t slab = 0;
-    for (size_t si = 0; si < h->steps.size(); ++si) {
-        const Step& s = h->steps[si];
-        const Layer& l = h->layers[s.layer];
-        if (!s.is_conv() || l.direct) continue;
-        int M, KT; step_geometry(h, s, B, T, &M, &KT);
-        // Grid fill: a 128x128 tiling of a small-M layer (deep backbone layers at small batch) leaves CUs
-        // idle; the 128x64 tile doubles the block count (the packed weight layout [K/32][Npad][32] does not
-        // depend on BN when N % 128 == 0).
-        int tile = s.tile;
-        if (tile == TILE_128x128 && (l.filters % 128) == 0 && (int64_t)((M + 127) / 128) * (l.filters / 128) < 512) tile = TILE_128x64;
-        // split precision: only the shared-tap 3x3 kernel has a 128-wide tile (the plain kernel would need scratch memory there);
-        // the 1x1 / stride-2 / concat convolutions run on the 64-wide tile, which also keeps twice the workgroups in flight per
-        // byte streamed for the HBM-latency-bound 76x76 head layers (measured at config 4: 0.83 -> 0.56, 0.77 -> 0.67 ms)
-        if (h->precision == 1) tile = conv_split_tile(tile, s.kx3 || s.p1);
-        else if (inject && tile == TILE_128x128) tile = TILE_128x64;      // the fp32 128-wide build has no mask-injection path (conv_igemm.hip)
-        // shared-tap 3x3 with cout % 256 == 0 and enough rows to fill the chip: ONE 8-wave workgroup owns all 256 output channels of
-        // its 128 pixels, so an activation row is fetched and staged once per 256 columns instead of once per 128.  Measured at
-        // config 4 (round 4, gpurun_out/r4b_*): the three 76x76 head convolutions 2.13 -> 2.22 ms each (-4 %): with ONE workgroup per
-        // CU the epilogues of all eight waves coincide and nothing multiplies meanwhile, where two independent 4-wave workgroups
-        // overlap one's epilogue with the other's K loop -- so it is NOT the default.
-        // opts.kx3_wide: 0 never (default), 1 launches of >= 4 rounds of 256 workgroups, 2 every eligible launch (tests)
-        const int kx3_wide = h->opts.kx3_wide;
-        if (h->precision == 1 && s.kx3 && (s.Npad % 256) == 0 && kx3_wide && (l.filters % 128) == 0 &&
-            (kx3_wide >= 2 ? (tile == TILE_128x128 || tile == TILE_128x64)       // (forced: also where the grid-fill rule above went narrow)
-                           : (tile == TILE_128x128 && (int64_t)((M + 127) / 128) * (s.Npad / 256) >= 4 * 256)))
-            tile = TILE_128x256;
-        if (p.fuse[si]) tile = TILE_128x256;                  // (decided before the arena was laid out, above)
-        p.tile[si] = tile;
-        // split precision: a K-tile takes ~0.4 of the fp32 kernel's; a shared-tap launch is scheduled in stages of 3 K-tiles
-        const bool sp = h->precision == 1, kx3 = sp && s.kx3;
-        p.split[si] = conv_plan_split(M, s.Npad, kx3 ? KT / 3 : KT, tile, sp ? (kx3 ? 1.2 : 0.4) : 1.0, h->opts.ksplit, h->opts.streamk);
-        if (s.low) p.split[si] = ConvSplit{((M + 127) / 128) * (s.Npad / conv_tile_bn(tile)), 0, 0, 1};      // whole tiles: the accumulation order of a STEP_MAIN tile
-        if (tile == TILE_128x256) p.split[si] = ConvSplit{((M + 127) / 128) * (s.Npad / 256), 0, 0, 1};      // whole tiles only: its workgroups walk the tile list (conv_igemm.hip WALK); a follower needs a finished tile
-        slab = std::max(slab, conv_split_slab_bytes(p.split[si], tile));
-    }
-    // Winograd F(2x2,3x3) for the large 3x3 / stride-1 convolutions (winograd.hip): samples per chunk such that
-    // the transformed input V (4x the input) and the GEMM result M (4x the output) of a chunk fit the scratch.
-    // BYOLO_WINOGRAD=0 keeps every convolution direct.
     p.wino.assign(h->steps.size(), WinoPlan{});
     size_t wino_scratch = 0;
     // Split precision: Winograd F(2x2,3x3) in split arithmetic (wino_split.hip) for the 3x3 / stride-1 convolutions it is faster on.
@@ -193,7 +133,8 @@ void make_plan(byolo_t* h, int B, int T, bool inject) {
         for (size_t si = 0; on && si < h->steps.size(); ++si) {
             const Step& s = h->steps[si];
             const Layer& l = h->layers[s.layer];
-            if (!s.wino_ok || !s.kx3 || s.mode != STEP_NORMAL || l.wshift_u.empty() || (l.fused_residual >= 0 && l.drop_ordinal >= 0) || p.fuse[si]) continue;   // (the kernel's residual epilogue carries no dropout)
+            if (!s.wino_ok || !s.kx3 || s.mode != STEP_NORMAL || !wino_split_ok(s.c_hi - s.c_lo, l.filters) || s.Npad != l.filters || (l.fused_residual >= 0 && l.drop_ordinal >= 0) || p.fuse[si]) continue;   // (the kernel's residual epilogue carries no dropout)
+            // (the shapes byolo_finalize packs U for, byolo_pack.hip: the plan of a handle is the same before and after byolo_finalize)
             int M, KT; step_geometry(h, s, B, T, &M, &KT);
             const double flops = 2.0 * M * l.filters * 9.0 * l.Cin;
             if (flops < min_flops) continue;
@@ -239,6 +180,96 @@ void make_plan(byolo_t* h, int B, int T, bool inject) {
             wino_scratch = std::max(wino_scratch, w.v_bytes);
         }
     }
+    // The element-wise pass in front of such a convolution inside its input transform (opts.wino_split_feed, wino_split.hip): a
+    // STEP_REP (bit 0) or STEP_FINISH (bit 1) step whose output has exactly ONE reader, that reader a convolution planned onto
+    // wino_split_kernel above which sees the tensor as it is (one plain source: Step::wino_ok).  The tensor in between then gets no
+    // memory: the STEP_REP launch stores its raw accumulators once per image (Step::raw_tensor), the STEP_FINISH launch is not
+    // issued, and the operands they leave behind stay alive until the reader's last transform.
+    p.feed.assign(h->steps.size(), 0); p.feed_src.assign(h->steps.size(), -1);
+    std::vector<int> last_use = h->last_use;                       // of THIS plan: a folded producer's operands live on to its reader
+    if (h->precision == 1 && h->opts.wino_split_feed && !h->cfg.keep_all_outputs) {
+        std::vector<int> readers(n, 0);
+        for (const Step& s : h->steps) {
+            for (int k = 0; k < s.in.n; ++k) if (s.in.s[k].layer >= 0) ++readers[s.in.s[k].layer];
+            if (s.addend_tensor >= 0) ++readers[s.addend_tensor];
+            if (s.low_tensor >= 0) ++readers[s.low_tensor];
+            const Layer& l = h->layers[s.layer];
+            if (s.is_conv() && l.fused_residual >= 0) ++readers[h->layers[l.fused_residual].ref[0]];
+        }
+        for (int si = 0; si < (int)h->steps.size(); ++si) {
+            const Step& s = h->steps[si];
+            const int kind = s.mode == STEP_REP ? 1 : s.mode == STEP_FINISH ? 2 : 0;
+            if (!kind || !(h->opts.wino_split_feed & kind) || (kind == 1 && s.raw_tensor < 0) || (kind == 2 && (s.low_tensor < 0 || s.addend_tensor < 0))) continue;
+            const Layer& l = h->layers[s.layer];
+            const int t = s.out_tensor, ri = h->last_use[t];
+            if (t >= (int)h->layers.size() || l.op != OP_CONV || l.direct || l.fused_residual >= 0 || (l.filters & 3) || readers[t] != 1 || ri <= si) continue;
+            const Step& r = h->steps[ri];
+            if (p.wino[ri].chunk <= 0 || !r.wino_ok || r.in.n != 1 || r.in.s[0].layer != t || r.in.s[0].sh != 0 || r.in.s[0].tile) continue;
+            p.feed[si] = (char)kind; p.feed_src[ri] = si;
+            if (kind == 1) last_use[s.raw_tensor] = ri;
+            else { last_use[s.low_tensor] = ri; if (s.addend_tensor >= 0) last_use[s.addend_tensor] = ri; }
+        }
+    }
+    for (int si = 0; si < (int)h->steps.size(); ++si) {
+        const Layer& l = h->layers[h->steps[si].layer];
+        const int t = p.feed[si] == 1 ? h->steps[si].raw_tensor : h->steps[si].out_tensor;
+        if (!(si > 0 && p.fuse[si - 1]) && p.feed[si] != 2) p.off[t] = alloc(tensor_bytes(h, t, B, T));      // (a fused follower's output exists since the step before; a folded finish writes nothing)
+        if (p.fuse[si]) { const int t2 = h->steps[si + 1].out_tensor; p.off[t2] = alloc(tensor_bytes(h, t2, B, T)); }
+        if (h->cfg.keep_all_outputs) continue;
+        for (int k = 0; k < n; ++k)
+            if (p.off[k] >= 0 && last_use[k] == si) release(p.off[k], tensor_bytes(h, k, B, T));
+        if (last_use[t] < 0 && l.op != OP_DETECTION && p.feed[si] != 2) release(p.off[t], tensor_bytes(h, t, B, T));   // dead output
+    }
+    // detection raw outputs must survive until their decode (same step) -> they are released one step
+    // late by construction (last_use == -1 handled below): keep them simple: never reuse det outputs.
+    p.arena = align_up((size_t)end, 256);
+    p.boxes_off = p.arena;
+    size_t o = p.boxes_off + align_up((size_t)B * h->n_boxes * h->row_len * sizeof(float), 256);
+    p.nms_off = o; o += align_up(nms_workspace_bytes_ex(B, h->n_boxes, h->cfg.nms_mode == BYOLO_NMS_PER_CLASS, h->cfg.cls_cnt), 256);
+    p.stats_off = o; o += align_up((size_t)1024 * 2 * h->maxC * sizeof(double) + 2 * h->maxC * sizeof(float), 256);
+    p.img_split_off = o; if (h->img_split) o += align_up((size_t)B * h->cfg.img_h * h->cfg.img_w * h->cfg.img_c * sizeof(float), 256);
+    // launch geometry per step: tile configuration and the split-K of the last partial round (shape-only)
+    p.split.assign(h->steps.size(), ConvSplit{0, 0, 0, 1});
+    p.tile.assign(h->steps.size(), 0);
+    size_t slab = 0;
+    for (size_t si = 0; si < h->steps.size(); ++si) {
+        const Step& s = h->steps[si];
+        const Layer& l = h->layers[s.layer];
+        if (!s.is_conv() || l.direct) continue;
+        int M, KT; step_geometry(h, s, B, T, &M, &KT);
+        // Grid fill: a 128x128 tiling of a small-M layer (deep backbone layers at small batch) leaves CUs
+        // idle; the 128x64 tile doubles the block count (the packed weight layout [K/32][Npad][32] does not
+        // depend on BN when N % 128 == 0).
+        int tile = s.tile;
+        if (tile == TILE_128x128 && (l.filters % 128) == 0 && (int64_t)((M + 127) / 128) * (l.filters / 128) < 512) tile = TILE_128x64;
+        // split precision: only the shared-tap 3x3 kernel has a 128-wide tile (the plain kernel would need scratch memory there);
+        // the 1x1 / stride-2 / concat convolutions run on the 64-wide tile, which also keeps twice the workgroups in flight per
+        // byte streamed for the HBM-latency-bound 76x76 head layers (measured at config 4: 0.83 -> 0.56, 0.77 -> 0.67 ms)
+        if (h->precision == 1) tile = conv_split_tile(tile, s.kx3 || s.p1);
+        else if (inject && tile == TILE_128x128) tile = TILE_128x64;      // the fp32 128-wide build has no mask-injection path (conv_igemm.hip)
+        // shared-tap 3x3 with cout % 256 == 0 and enough rows to fill the chip: ONE 8-wave workgroup owns all 256 output channels of
+        // its 128 pixels, so an activation row is fetched and staged once per 256 columns instead of once per 128.  Measured at
+        // config 4 (round 4): the three 76x76 head convolutions 2.13 -> 2.22 ms each (-4 %): with ONE workgroup per
+        // CU the epilogues of all eight waves coincide and nothing multiplies meanwhile, where two independent 4-wave workgroups
+        // overlap one's epilogue with the other's K loop -- so it is NOT the default.
+        // opts.kx3_wide: 0 never (default), 1 launches of >= 4 rounds of 256 workgroups, 2 every eligible launch (tests)
+        const int kx3_wide = h->opts.kx3_wide;
+        if (h->precision == 1 && s.kx3 && (s.Npad % 256) == 0 && kx3_wide && (l.filters % 128) == 0 &&
+            (kx3_wide >= 2 ? (tile == TILE_128x128 || tile == TILE_128x64)       // (forced: also where the grid-fill rule above went narrow)
+                           : (tile == TILE_128x128 && (int64_t)((M + 127) / 128) * (s.Npad / 256) >= 4 * 256)))
+            tile = TILE_128x256;
+        if (p.fuse[si]) tile = TILE_128x256;                  // (decided before the arena was laid out, above)
+        p.tile[si] = tile;
+        // split precision: a K-tile takes ~0.4 of the fp32 kernel's; a shared-tap launch is scheduled in stages of 3 K-tiles
+        const bool sp = h->precision == 1, kx3 = sp && s.kx3;
+        p.split[si] = conv_plan_split(M, s.Npad, kx3 ? KT / 3 : KT, tile, sp ? (kx3 ? 1.2 : 0.4) : 1.0, h->opts.ksplit, h->opts.streamk);
+        if (s.low) p.split[si] = ConvSplit{((M + 127) / 128) * (s.Npad / conv_tile_bn(tile)), 0, 0, 1};      // whole tiles: the accumulation order of a STEP_MAIN tile
+        if (tile == TILE_128x256) p.split[si] = ConvSplit{((M + 127) / 128) * (s.Npad / 256), 0, 0, 1};      // whole tiles only: its workgroups walk the tile list (conv_igemm.hip WALK); a follower needs a finished tile
+        slab = std::max(slab, conv_split_slab_bytes(p.split[si], tile));
+    }
+    // Winograd F(2x2,3x3) for the large 3x3 / stride-1 convolutions (winograd.hip): samples per chunk such that
+    // the transformed input V (4x the input) and the GEMM result M (4x the output) of a chunk fit the scratch.
+    // BYOLO_WINOGRAD=0 keeps every convolution direct.
     { const int on = (h->precision == 1 || inject) ? 0 : h->opts.winograd;   // split precision: direct convolutions only (memory-bound transforms do not pay there); injected masks: conv_igemm's epilogue reads them
       // opts.wino_min_gflop: tuning knob: smallest layer (direct GFLOP) to transform
       // (measured at config 4: 100 -> 144.97, 20 -> 147.35, 5 -> 147.32 img/s; at config 2 (416x416, 8 images) the 52x52
@@ -414,11 +445,22 @@ extern "C" int32_t byolo_plan_step(byolo_t* h, int32_t step, int32_t* out_tensor
     const Step& st = h->steps[step];
     const Layer& l = h->layers[st.layer];
     int n = 0;
+    // a convolution whose input transform carries the step in front of it (Plan::feed) reads THAT step's operands: the raw accumulators
+    // of the folded STEP_REP, or what the folded STEP_FINISH would have read
+    const int fs = step < (int32_t)h->plan.feed_src.size() ? h->plan.feed_src[step] : -1;
+    const int fk = step < (int32_t)h->plan.feed.size() ? h->plan.feed[step] : 0;
+    if (fs >= 0) {
+        const Step& ps = h->steps[fs];
+        if (h->plan.feed[fs] == 1) reads[n++] = ps.raw_tensor;
+        else { reads[n++] = ps.low_tensor; if (ps.addend_tensor >= 0) reads[n++] = ps.addend_tensor; }
+    } else
     for (int k = 0; k < st.in.n; ++k) if (st.in.s[k].layer >= 0) reads[n++] = st.in.s[k].layer;      // (< 0: the image)
     if (st.addend_tensor >= 0) reads[n++] = st.addend_tensor;
     if (st.low_tensor >= 0) reads[n++] = st.low_tensor;
     if (st.is_conv() && st.mode != STEP_PARTIAL && l.fused_residual >= 0) reads[n++] = h->layers[l.fused_residual].ref[0];
-    if (out_tensor) *out_tensor = st.out_tensor;
+    // a folded STEP_REP writes its raw accumulators; a folded STEP_FINISH launches nothing and writes nothing: it reports the `low`
+    // operand it hands on to the reader (already written, still alive), never its own output, which has no memory in this plan
+    if (out_tensor) *out_tensor = fk == 1 ? st.raw_tensor : fk == 2 ? st.low_tensor : st.out_tensor;
     if (fuses_next) *fuses_next = (step < (int32_t)h->plan.fuse.size() && h->plan.fuse[step]) ? 1 : 0;
     if (n_reads) *n_reads = n;
     return BYOLO_OK;

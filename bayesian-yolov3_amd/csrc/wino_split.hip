@@ -99,12 +99,34 @@ __device__ __forceinline__ void vstore(float* at, const f32x4 v) {
     if constexpr (BYOLO_WS_NT_STORE != 0) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(at));
     else *reinterpret_cast<f32x4*>(at) = v;
 }
-__global__ __launch_bounds__(256) void wino_split_input2_kernel(const WinoParams p, const FastDiv d_twp, const FastDiv d_ttp, const int twp, const FastDiv d_th) {
+//
+// PRODUCER MODES (FEED; byolo_plan.hip Plan::feed, byolo_plan_opts.wino_split_feed).  Where the tensor this transform reads is written
+// by a purely element-wise pass that has no other reader, the transform evaluates that pass itself and the tensor never exists:
+//   FEED 1  the T-fold replay of a per-image convolution's epilogue (STEP_REP): the source is the convolution's RAW accumulators,
+//           [images, H, W, C] -- T-invariant and cache-resident.  A thread owns (image, slice of the image's T samples, ONE tile,
+//           4 channels): it loads its 4 x 4 patch ONCE and walks the samples of its slice; per sample only the keep bits change.
+//           The slice (BYOLO_WS_FEED_SLICE samples) is sized for occupancy, not for reuse: a walk over all T = 30 samples of config 4
+//           would leave 51 200 threads, less than one wave per SIMD, for a launch that has to keep 6 TB/s of stores in flight.
+//   FEED 2  the finish of a 1x1 convolution over an upsampled source (STEP_FINISH, conv_kernels.hip finish_upsampled_kernel):
+//           low[s, y / 2, x / 2] + part[s / T, y, x], the same two numbers added in the same order, at each of the 24 patch positions
+//           (12 low-resolution loads + 24 of the partial sums instead of 24 of the finished tensor).
+// Both run the producer's epilogue as that launch did -- epi::bn_act4 on the same accumulator, scale, shift and keep bits (the library's
+// hash or the injected bits at the SAME element index: idx_base + the NHWC index in [S, h, w, c] of the sample's pixel), the range check on
+// max |v| before encoding, raised under the PRODUCER's layer index -- and then pass every finished value through split_encode4 /
+// split_decode4 IN REGISTERS: the hi + lo pair the two-launch plan stored and read back.  V is the same bits.  A pixel is finished in
+// up to four patches (3 x the arithmetic of the producer launch); the transform stays bound by its V stores.
+// DROP: 0 no dropout, 1 the library's hash, 2 injected bits.  FEED 0 is the plain transform described above, unchanged.
+#ifndef BYOLO_WS_FEED_SLICE
+#define BYOLO_WS_FEED_SLICE 5
+#endif
+template <int FEED, int DROP>
+__global__ __launch_bounds__(256) void wino_split_input2_kernel(const WinoParams p, const FastDiv d_twp, const FastDiv d_ttp, const int twp, const FastDiv d_th,
+                                                                const uint32_t groups, const uint32_t img_lo, const FastDiv d_nsl, const uint32_t nsl) {
     const uint32_t gid = blockIdx.x * 256u + threadIdx.x;
     const uint32_t c4n = (uint32_t)p.C >> 2;
     const uint32_t q = fdiv(gid, p.d_c4), c4 = gid - q * c4n;
     const size_t xi_stride = (size_t)p.P_pad * p.C;
-    const uint32_t ttp = (uint32_t)(p.th * twp), n_pairs = (uint32_t)(p.P / (p.th * p.tw)) * ttp;
+    const uint32_t ttp = (uint32_t)(p.th * twp), n_pairs = groups * ttp;              // groups: samples of the chunk (FEED 1: images x slices)
     if (q >= n_pairs) {
         const uint32_t t = (uint32_t)p.P + (q - n_pairs);
         if (t >= (uint32_t)p.P_pad) return;
@@ -120,32 +142,16 @@ __global__ __launch_bounds__(256) void wino_split_input2_kernel(const WinoParams
     uint32_t ty, txp;
     if constexpr (BYOLO_WS_IN_COLMAJOR != 0) { txp = fdiv(r, d_th); ty = r - txp * (uint32_t)p.th; }
     else { ty = fdiv(r, d_twp); txp = r - ty * (uint32_t)twp; }
-    const uint32_t tx0 = 2u * txp;
-    const bool two = tx0 + 1u < (uint32_t)p.tw;
-    const float* img = p.x + ((size_t)(p.s0 + s) * p.H * p.W) * p.C + c4 * 4;
+    // (FEED 1: ONE tile per thread, twp = tw -- the pair's shared columns save loads, and that thread loads once per slice; what it
+    //  must not do is hold a 4 x 6 patch AND the transform's 96 registers across its sample loop: 256 registers and scratch)
+    constexpr uint32_t PAIR = FEED == 1 ? 1u : 2u;
+    const uint32_t tx0 = PAIR * txp;
+    const bool two = PAIR == 2u && tx0 + 1u < (uint32_t)p.tw;
     const int y0 = 2 * (int)ty - 1, x0 = 2 * (int)tx0 - 1;
-    f32x4 u[4][6];                                   // B^T d of the six patch columns x0 .. x0 + 5
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        f32x4 d[4];
-        const int x = x0 + j;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int y = y0 + i;
-            const bool ok = (unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W && (j < 4 || two);
-            const f32x4 raw = ok ? *reinterpret_cast<const f32x4*>(img + ((size_t)y * p.W + x) * p.C) : f32x4{0.f, 0.f, 0.f, 0.f};
-            d[i] = epi::split_decode4(raw);
-        }
-        u[0][j] = d[0] - d[2];
-        u[1][j] = d[1] + d[2];
-        u[2][j] = d[2] - d[1];
-        u[3][j] = d[1] - d[3];
-    }
     const float m = p.vmul;
-    const uint32_t t0 = ((s * (uint32_t)p.th + ty) * (uint32_t)p.tw + tx0);
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        if (k == 1 && !two) break;
+    // B^T d B of the patch columns in u -> the two tiles' 2 x 16 stores; sl = the sample inside the chunk
+    auto emit_tile = [&](const uint32_t sl, const f32x4 (&u)[4][6], const int k) __attribute__((always_inline)) {
+        const uint32_t t0 = ((sl * (uint32_t)p.th + ty) * (uint32_t)p.tw + tx0);
         float* v = p.v + v_index(t0 + (uint32_t)k, c4 * 4, (uint32_t)p.C);
         const int o = 2 * k;
 #pragma unroll
@@ -155,15 +161,157 @@ __global__ __launch_bounds__(256) void wino_split_input2_kernel(const WinoParams
             vstore(v + (size_t)(i * 4 + 2) * xi_stride, epi::split_encode4((u[i][o + 2] - u[i][o + 1]) * m));
             vstore(v + (size_t)(i * 4 + 3) * xi_stride, epi::split_encode4((u[i][o + 1] - u[i][o + 3]) * m));
         }
+    };
+    auto emit = [&](const uint32_t sl, const f32x4 (&u)[4][6]) __attribute__((always_inline)) {
+        emit_tile(sl, u, 0);
+        if (two) emit_tile(sl, u, 1);
+    };
+    auto column = [&](f32x4 (&u)[4][6], const int j, const f32x4 (&d)[4]) __attribute__((always_inline)) {
+        u[0][j] = d[0] - d[2];
+        u[1][j] = d[1] + d[2];
+        u[2][j] = d[2] - d[1];
+        u[3][j] = d[1] - d[3];
+    };
+    if constexpr (FEED == 0) {
+        const float* img = p.x + ((size_t)(p.s0 + s) * p.H * p.W) * p.C + c4 * 4;
+        f32x4 u[4][6];                                   // B^T d of the six patch columns x0 .. x0 + 5
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+            f32x4 d[4];
+            const int x = x0 + j;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int y = y0 + i;
+                const bool ok = (unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W && (j < 4 || two);
+                const f32x4 raw = ok ? *reinterpret_cast<const f32x4*>(img + ((size_t)y * p.W + x) * p.C) : f32x4{0.f, 0.f, 0.f, 0.f};
+                d[i] = epi::split_decode4(raw);
+            }
+            column(u, j, d);
+        }
+        emit(s, u);
+    } else {
+        // ---- the producer's epilogue at one position of one sample (gs = the sample's index in the call's [S, H, W, C] tensor) ----
+        const f32x4 sc4 = *reinterpret_cast<const f32x4*>(p.src_scale + c4 * 4), sf4 = *reinterpret_cast<const f32x4*>(p.src_shift + c4 * 4);
+        const float slope = (p.src_flags & EPI_LEAKY) ? 0.1f : 1.f;
+        float vmax = 0.f;
+        // (the element index = the lane's index at patch position (1, 1), always inside the image, + a block-uniform offset per position)
+        auto finish = [&](const f32x4 a4, const uint32_t gs, const int i, const int j) __attribute__((always_inline)) -> f32x4 {
+            bool keep[4] = {true, true, true, true};
+            if constexpr (DROP != 0) {
+                const uint64_t pix = ((uint64_t)gs * p.H + (uint32_t)(y0 + 1)) * p.W + (uint32_t)(x0 + 1);
+                const int64_t off = (int64_t)(((i - 1) * p.W + (j - 1)) * p.C);
+                const epi::DropRow drow(p.src_idx_base + pix * (uint64_t)p.C + (uint64_t)(c4 * 4) + (uint64_t)off, p.src_k1);
+                if constexpr (DROP == 2) {                                  // injected masks (conv_igemm.hip finish_tile)
+                    const uint32_t el = drow.el_lo();
+                    const uint32_t w = p.src_mask_bits[el >> 5] >> (el & 31u);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) keep[k] = (w >> k) & 1u;
+                } else epi::keep4(drow, 0, p.src_k0, p.src_thr, keep);
+            }
+            const f32x4 v = epi::bn_act4(a4, sc4, sf4, keep, slope);
+            vmax = epi::absmax4(vmax, v);
+            return epi::split_decode4(epi::split_encode4(v));               // what the two-launch plan stored and read back
+        };
+        if constexpr (FEED == 1) {
+            // s = (image of the chunk, slice): the slice's samples, clipped to the chunk's sample range (a chunk may start and end inside an image)
+            const uint32_t il = fdiv(s, d_nsl), slice = s - il * nsl, image = img_lo + il, T = (uint32_t)p.src_T;
+            uint32_t ga = image * T + slice * (uint32_t)BYOLO_WS_FEED_SLICE, gb = ga + (uint32_t)BYOLO_WS_FEED_SLICE;
+            gb = gb < (image + 1u) * T ? gb : (image + 1u) * T;
+            ga = ga > (uint32_t)p.s0 ? ga : (uint32_t)p.s0;
+            const uint32_t s_end = (uint32_t)p.s0 + (uint32_t)p.P / (uint32_t)(p.th * p.tw);
+            gb = gb < s_end ? gb : s_end;
+            if (ga >= gb) return;
+            const float* img = p.src_low + ((size_t)image * p.H * p.W) * p.C + c4 * 4;
+            f32x4 acc[4][4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int y = y0 + i, x = x0 + j;
+                    const bool ok = (unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W;
+                    acc[i][j] = ok ? *reinterpret_cast<const f32x4*>(img + ((size_t)y * p.W + x) * p.C) : f32x4{0.f, 0.f, 0.f, 0.f};
+                }
+#pragma unroll 1
+            for (uint32_t gs = ga; gs < gb; ++gs) {
+                f32x4 u[4][6];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    f32x4 d[4];
+                    const int x = x0 + j;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const int y = y0 + i;
+                        const bool ok = (unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W;
+                        d[i] = ok ? finish(acc[i][j], gs, i, j) : f32x4{0.f, 0.f, 0.f, 0.f};
+                    }
+                    column(u, j, d);
+                }
+                emit_tile(gs - (uint32_t)p.s0, u, 0);
+            }
+        } else {
+            // patch rows y0 .. y0 + 3 = 2 ty - 1 .. 2 ty + 2 sit on the low-resolution rows ty - 1, ty, ty, ty + 1 (columns alike)
+            const uint32_t gs = (uint32_t)p.s0 + s, lh = (uint32_t)p.H >> 1, lw = (uint32_t)p.W >> 1;
+            const float* low = p.src_low + ((size_t)gs * lh * lw) * p.C + c4 * 4;
+            const float* part = p.src_part ? p.src_part + ((size_t)(gs / (uint32_t)p.src_T) * p.H * p.W) * p.C + c4 * 4 : nullptr;
+            f32x4 lo[3][4];
+#pragma unroll
+            for (int a = 0; a < 3; ++a)
+#pragma unroll
+                for (int b = 0; b < 4; ++b) {
+                    const int ly = (int)ty - 1 + a, lx = (int)tx0 - 1 + b;
+                    const bool ok = (unsigned)ly < lh && (unsigned)lx < lw && (b < 3 || two);
+                    lo[a][b] = ok ? *reinterpret_cast<const f32x4*>(low + ((size_t)ly * lw + lx) * p.C) : f32x4{0.f, 0.f, 0.f, 0.f};
+                }
+            f32x4 u[4][6];
+#pragma unroll
+            for (int j = 0; j < 6; ++j) {
+                f32x4 d[4];
+                const int x = x0 + j;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int y = y0 + i;
+                    const bool ok = (unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W && (j < 4 || two);
+                    f32x4 a4 = lo[(i + 1) >> 1][(j + 1) >> 1];
+                    if (ok && part) a4 += *reinterpret_cast<const f32x4*>(part + ((size_t)y * p.W + x) * p.C);
+                    d[i] = ok ? finish(a4, gs, i, j) : f32x4{0.f, 0.f, 0.f, 0.f};
+                }
+                column(u, j, d);
+            }
+            emit(s, u);
+        }
+        if (p.src_status && vmax >= 65520.f) { atomicOr(p.src_status, 1u); atomicMin(p.src_status + 1, (unsigned)p.src_layer_idx); }
     }
 }
 
+template <int FEED>
+static void launch_input_feed(const WinoParams& p, unsigned grid, hipStream_t st, int twp, uint32_t groups, uint32_t img_lo, uint32_t nsl) {
+    const FastDiv a = make_fastdiv((uint32_t)twp), b = make_fastdiv((uint32_t)(p.th * twp)), c = make_fastdiv((uint32_t)p.th), d = make_fastdiv(nsl);
+    const int drop = !(p.src_flags & EPI_DROPOUT) ? 0 : (p.src_mask_bits ? 2 : 1);
+    if constexpr (FEED == 0) hipLaunchKernelGGL((wino_split_input2_kernel<0, 0>), dim3(grid), dim3(256), 0, st, p, a, b, twp, c, groups, img_lo, d, nsl);
+    else if (drop == 0) hipLaunchKernelGGL((wino_split_input2_kernel<FEED, 0>), dim3(grid), dim3(256), 0, st, p, a, b, twp, c, groups, img_lo, d, nsl);
+    else if (drop == 1) hipLaunchKernelGGL((wino_split_input2_kernel<FEED, 1>), dim3(grid), dim3(256), 0, st, p, a, b, twp, c, groups, img_lo, d, nsl);
+    else hipLaunchKernelGGL((wino_split_input2_kernel<FEED, 2>), dim3(grid), dim3(256), 0, st, p, a, b, twp, c, groups, img_lo, d, nsl);
+}
+
 hipError_t launch_wino_split_input(const WinoParams& p, hipStream_t st) {
-    const int twp = (p.tw + 1) / 2;
-    const uint64_t rows = (uint64_t)(p.P / (p.th * p.tw)) * p.th * twp + (uint64_t)(p.P_pad - p.P);
+    const int twp = p.feed == 1 ? p.tw : (p.tw + 1) / 2;         // tiles (FEED 1) or tile pairs per tile row
+    const uint32_t ns = (uint32_t)(p.P / (p.th * p.tw));
+    uint32_t groups = ns, img_lo = 0, nsl = 1;
+    if (p.feed < 0 || p.feed > 2) return hipErrorInvalidValue;
+    if (p.feed) {
+        if (!p.src_low || !p.src_scale || !p.src_shift || p.src_T < 1 || ns < 1 || (p.feed == 2 && ((p.H | p.W) & 1))) return hipErrorInvalidValue;
+    }
+    if (p.feed == 1) {                                       // thread groups = (images the chunk touches) x (slices of an image's T samples)
+        img_lo = (uint32_t)p.s0 / (uint32_t)p.src_T;
+        nsl = ((uint32_t)p.src_T + BYOLO_WS_FEED_SLICE - 1) / BYOLO_WS_FEED_SLICE;
+        groups = (((uint32_t)p.s0 + ns - 1) / (uint32_t)p.src_T - img_lo + 1) * nsl;
+    }
+    const uint64_t rows = (uint64_t)groups * p.th * twp + (uint64_t)(p.P_pad - p.P);
     const uint64_t total = rows * (uint64_t)(p.C >> 2);
-    hipLaunchKernelGGL(wino_split_input2_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, p,
-                       make_fastdiv((uint32_t)twp), make_fastdiv((uint32_t)(p.th * twp)), twp, make_fastdiv((uint32_t)p.th));
+    const unsigned grid = (unsigned)((total + 255) / 256);
+    if (p.feed == 0) launch_input_feed<0>(p, grid, st, twp, groups, img_lo, nsl);
+    else if (p.feed == 1) launch_input_feed<1>(p, grid, st, twp, groups, img_lo, nsl);
+    else launch_input_feed<2>(p, grid, st, twp, groups, img_lo, nsl);
     return hipGetLastError();
 }
 

@@ -151,6 +151,11 @@ typedef struct byolo_plan_opts {
     int32_t wino_split_persist;    /* the Winograd GEMM's workgroups walk the unit list themselves, next unit prefetched: 0 one unit per
                                       workgroup (default), 1 a static list, 2 units claimed from a per-XCD counter; the same bits, and
                                       measured SLOWER: +2.5 % / +0.8 % per launch (profiles/r6_wino_persist.md) [BYOLO_WINO_SPLIT_PERSIST] */
+    int32_t wino_split_feed;       /* the split-f16 Winograd input transform evaluates the element-wise pass in front of it itself, when it
+                                      is that pass's only reader: bit 0 = the T-fold replay of a per-image convolution's epilogue (that
+                                      convolution then stores raw accumulators once per image), bit 1 = the finish of a 1x1 convolution
+                                      over an upsampled source (that launch is not issued); the tensor in between gets no memory.  3
+                                      (default), 0 = the two-launch plan; the same bits (profiles/wino_feed.md) [BYOLO_WINO_SPLIT_FEED]  */
     float   wino_split_min_gflop;  /* a floor under the time model: 30 [BYOLO_WINO_SPLIT_MIN_GFLOP]                                   */
     float   wino_split_chunk_mb;   /* V bytes of one chunk: 1500 [BYOLO_WINO_SPLIT_CHUNK_MB]                                          */
     float   wino_min_gflop;        /* fp32 mode: 10 [BYOLO_WINO_MIN_GFLOP]                                                            */
@@ -228,6 +233,9 @@ BYOLO_API int32_t byolo_workspace_bytes(byolo_t* h, int32_t B, int32_t T, size_t
  *   byolo_plan_num     makes the plan (inject != 0: the plan of a call with d_mask_bits); steps, tensors, arena size;
  *   byolo_plan_step    the tensor step `step` writes; fuses_next = 1 when step + 1 runs INSIDE this step's launch (its output is
  *                      written during this step, this step's own output tensor never exists); the tensors the step's launch reads;
+ *                      a step folded into its reader's Winograd input transform (wino_split_feed) reports what it really leaves in
+ *                      memory -- the per-image raw accumulators (an auxiliary tensor), or, launching nothing, the low-resolution
+ *                      operand it hands on -- and that reader reports those operands as what it reads;
  *   byolo_plan_tensor  offset in the workspace (< 0: none in this plan), size, and whether anything reads it after the last step
  *                      (a detection layer's raw output: the decode launch; every layer under keep_all_outputs). */
 BYOLO_API int32_t byolo_plan_num(byolo_t* h, int32_t B, int32_t T, int32_t inject, int32_t* n_steps, int32_t* n_tensors, int64_t* arena_bytes);

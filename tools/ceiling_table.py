@@ -14,7 +14,11 @@ M / N / K, ms).  For every launch
   NOT the nominal 2 500: no instruction mix on this part runs the fp16 matrix pipe faster than that for longer than a launch;
 * bytes = input once + weights once + output once (4 bytes per element: hi/lo pairs), transforms: input + 4 x input written, the
   element-wise finish launches: what they read + write; HBM rate = tools/hbm_probe.py (copy: mixed read/write; fill: pure writes for
-  the write-dominated transform).
+  the write-dominated transform);
+* a transform that evaluates the element-wise pass in front of it (byolo_plan_opts.wino_split_feed, --feed: the option the table was
+  taken with) reads that pass's operands instead of a finished tensor -- the per-image raw accumulators of the convolution before it
+  (bit 0: that layer has ONE launch, on far fewer rows than the transform has pixels), or the low-resolution sums + the per-image
+  partial sums (bit 1: that layer has its two half launches and NO finish launch) -- and the finish family has one launch less.
 """
 import argparse
 import collections
@@ -42,6 +46,7 @@ def main():
     ap.add_argument("--hbm-tbs", type=float, default=4.96)
     ap.add_argument("--write-tbs", type=float, default=6.84)
     ap.add_argument("--ms-per-step", type=float, default=None, help="bench.py's ms_per_step of the same run (wall, pipelined)")
+    ap.add_argument("--feed", type=int, default=3, help="byolo_plan_opts.wino_split_feed of the run (1 = replay, 2 = finish inside the transform)")
     a = ap.parse_args()
     rows = []
     for line in open(a.per_launch):
@@ -49,9 +54,22 @@ def main():
         if m:
             rows.append(tuple(int(x) for x in m.groups()[:6]) + (float(m.group(7)), float(m.group(9)) * 1e12 * float(m.group(7)) * 1e-3))
     fam = collections.OrderedDict()
+    by_layer = collections.defaultdict(list)
+    for r in rows:
+        by_layer[r[1]].append(r)
+
+    def fed_input_bytes(layer, M, N):
+        """Bytes a fed transform reads, or None: the launches of the layer in front of it (see the module text)."""
+        prev = by_layer.get(layer - 1, [])
+        if not prev or any(r[2] == -5 for r in prev) or any(r[4] != N or 3 * r[3] >= 4 * M for r in prev):
+            return None
+        if (len(prev) == 1 and a.feed & 1) or (len(prev) == 2 and a.feed & 2):
+            return sum(r[3] * N * 4 for r in prev)
+        return None
     for idx, layer, variant, M, N, K, ms, algo in rows:
         if variant == -4:                                   # M = output tiles, N = channels: reads the input (4 pixels per tile), writes V = 16 values per tile
-            flops, bytes_, rate = 0.0, M * N * 4 * (4 + 16), a.write_tbs
+            fed = fed_input_bytes(layer, M, N)
+            flops, bytes_, rate = 0.0, (M * N * 4 * 4 if fed is None else fed) + M * N * 4 * 16, a.write_tbs
         elif variant == -5:                                 # M = output pixels, N = channels: reads low (1/4) + partial (1/T) + writes
             flops, bytes_, rate = 0.0, M * N * 4 * 1.3, a.hbm_tbs
         elif variant == -1:                                 # stem (vector FMA): fp32 image in, hi/lo out
