@@ -12,7 +12,7 @@
 //                                                          sample broadcast) of the consuming conv
 //   detection conv (+bias) -> split -> decode             conv_igemm (bias epilogue) + one decode launch
 //                                                          writing rows at their concat_bbox offset
-//   concat_bbox -> non_max_suppression -> gather          sort_keys + nms launches
+//   concat_bbox -> non_max_suppression -> gather          the pc_* launches of launch_sort_nms
 #include "byolo_internal.h"
 
 static thread_local std::string g_err;
@@ -799,7 +799,7 @@ static int32_t run_wino_split(byolo_t* h, const Step& s, const Layer& l, const C
         f.C = c.C0; f.N = c.N; f.KT = c.C0 / 32; f.n_tiles = c.N / wp.bn; f.bn = wp.bn;
         f.H = l.H; f.W = l.W; f.th = wp.th; f.tw = wp.tw; f.s0 = s0; f.P = w.P; f.P_pad = w.P_pad;
         f.bm = wp.bm; f.units = (w.P_pad / wp.bm) * f.n_tiles;
-        // (persist 2 claims units from 8 words of this step's ticket area, zeroed by the forward's memset: one set per chunk)
+        // (persist 2 claims units from 8 words of this step's ticket area, zeroed by the forward's launch_zero_words: one set per chunk)
         const int chunk_idx = s0 / wp.chunk;
         f.persist = (h->opts.wino_split_persist == 2 && c.counters && chunk_idx < CNT_PER_STEP / 8) ? 2 : (h->opts.wino_split_persist ? 1 : 0);
         f.claims = c.counters ? c.counters + 8 * chunk_idx : nullptr;
@@ -1044,7 +1044,7 @@ static int32_t forward_piece(byolo_t* h, const float* d_img, int32_t B, int32_t 
 
 // One forward as ONE hipGraphLaunch.  The first call with a given argument set runs eagerly (function attributes are set, one-off
 // shapes never pay for a capture); the second captures the launch sequence of enqueue_forward on the caller's stream (thread-local
-// capture mode: the memset node + the kernel nodes, a linear chain), instantiates it and launches it; later calls replay.  A call that
+// capture mode: kernel nodes only, a linear chain -- every clear is a launch_zero_words kernel), instantiates it and launches it; later calls replay.  A call that
 // differs only in what the dropout masks are drawn from (seed, byolo_set_first_image) is captured anew and the executable graph is
 // UPDATED in place (hipGraphExecUpdate: same topology, other kernel arguments).  *done = false: nothing was enqueued, run eagerly.
 static int32_t forward_graph(byolo_t* h, const FwdArgs& a, hipStream_t st, bool* done) {
@@ -1117,7 +1117,7 @@ static int32_t finish_forward(byolo_t* h, hipStream_t st, void* stream) {
     return BYOLO_OK;
 }
 
-// Everything one forward puts on the stream, in order: the split-K tickets' memset, the image's hi/lo copy, the convolution stack,
+// Everything one forward puts on the stream, in order: the split-K tickets' clear, the image's hi/lo copy, the convolution stack,
 // decode, sort + NMS.  `capturing`: the stream is in capture mode (forward_graph) -- no event is recorded or waited for in here.
 static int32_t enqueue_forward(byolo_t* h, const FwdArgs& a, hipStream_t st, bool capturing, bool wait_convs, bool heads_only) {
     const float* d_img = a.d_img; const int32_t B = a.B, T = a.T; const uint64_t seed = a.seed; const int32_t dropout_on = a.dropout_on;
@@ -1310,11 +1310,10 @@ static int32_t enqueue_forward(byolo_t* h, const FwdArgs& a, hipStream_t st, boo
     if (d_rows) {
         NmsParams n; memset(&n, 0, sizeof n);
         n.boxes = boxes; n.B = B; n.N = h->n_boxes; n.D = h->row_len; n.obj_idx = h->obj_idx; n.cls_start = h->cls_start;
-        n.two_class = h->cfg.nms_mode == BYOLO_NMS_TWO_CLASS; n.max_out = h->cfg.max_out; n.iou_thr = h->cfg.iou_thresh;
-        n.per_class = h->cfg.nms_mode == BYOLO_NMS_PER_CLASS; n.C = h->cfg.cls_cnt;
-        n.ws = ws + h->plan.nms_off; n.ws_bytes = nms_workspace_bytes_ex(B, h->n_boxes, n.per_class, n.C);
+        n.C = nms_classes(h->cfg.nms_mode, h->cfg.cls_cnt); n.max_out = h->cfg.max_out; n.iou_thr = h->cfg.iou_thresh;
+        n.ws = ws + h->plan.nms_off; n.ws_bytes = nms_workspace_bytes_ex(B, h->n_boxes, h->cfg.nms_mode, h->cfg.cls_cnt);
         n.rows = d_rows; n.kept = d_kept; n.count = d_count; n.general_only = h->opts.nms_general != 0;
-        if (n.two_class && h->cfg.cls_cnt != 2) return fail(h, BYOLO_ERR_ARG, "byolo_forward: 2-class NMS needs cls_cnt == 2");
+        if (h->cfg.nms_mode == BYOLO_NMS_TWO_CLASS && h->cfg.cls_cnt != 2) return fail(h, BYOLO_ERR_ARG, "byolo_forward: 2-class NMS needs cls_cnt == 2");
         HIPCHK(h, launch_sort_nms(n, st));
     }
     if (h->profiling) { HIPCHK(h, hipEventRecord(h->wslot().ev[4], st)); h->wslot().ev_valid = true; }
@@ -1405,11 +1404,11 @@ extern "C" int32_t byolo_epistemic_stats(byolo_t* h, const float* d_raw, int32_t
     return BYOLO_OK;
 }
 
-extern "C" size_t byolo_nms_workspace_bytes(int32_t B, int64_t N) { return nms_workspace_bytes(B, N); }
+extern "C" size_t byolo_nms_workspace_bytes(int32_t B, int64_t N) { return nms_workspace_bytes(B, N, 2); }   // modes 0 and 1
 extern "C" size_t byolo_nms_workspace_bytes_ex(int32_t B, int64_t N, int32_t nms_mode, int32_t cls_cnt) {
     if (B < 1 || N < 1) return 0;
     if (nms_mode == BYOLO_NMS_PER_CLASS && (cls_cnt < 1 || cls_cnt > BYOLO_NMS_MAX_CLASSES)) return 0;
-    return nms_workspace_bytes_ex(B, N, nms_mode == BYOLO_NMS_PER_CLASS, cls_cnt);
+    return nms_workspace_bytes_ex(B, N, nms_mode, cls_cnt);
 }
 
 extern "C" int32_t byolo_sort_nms(byolo_t* h, const float* d_boxes, int32_t B, int64_t N, int32_t D, int32_t obj_idx,
@@ -1425,14 +1424,13 @@ extern "C" int32_t byolo_sort_nms(byolo_t* h, const float* d_boxes, int32_t B, i
     const int32_t C = h->cfg.cls_cnt;                        // the class count of the per-class mode is the handle's
     if (per_class && (C < 1 || C > BYOLO_NMS_MAX_CLASSES)) return fail(h, BYOLO_ERR_ARG, "byolo_sort_nms: per-class NMS takes 1 .. %d classes", BYOLO_NMS_MAX_CLASSES);
     if (per_class && (cls_start_idx < 0 || (int64_t)cls_start_idx + C > D)) return fail(h, BYOLO_ERR_ARG, "byolo_sort_nms: bad cls_start_idx (class columns outside the row)");
-    if (per_class && N >= (1ll << 31)) return fail(h, BYOLO_ERR_ARG, "byolo_sort_nms: bad shape");
-    if (ws_bytes < nms_workspace_bytes_ex(B, N, per_class, C)) return fail(h, BYOLO_ERR_NOMEM, "byolo_sort_nms: workspace too small");
+    if (N >= (1ll << 31)) return fail(h, BYOLO_ERR_ARG, "byolo_sort_nms: bad shape");
+    if (ws_bytes < nms_workspace_bytes_ex(B, N, nms_mode, C)) return fail(h, BYOLO_ERR_NOMEM, "byolo_sort_nms: workspace too small");
     HIPCHK(h, hipSetDevice(h->device));
     NmsParams n; memset(&n, 0, sizeof n);
     n.boxes = d_boxes; n.B = B; n.N = N; n.D = D; n.obj_idx = obj_idx; n.cls_start = cls_start_idx;
-    n.two_class = nms_mode == BYOLO_NMS_TWO_CLASS; n.max_out = max_out; n.iou_thr = iou_thresh;
+    n.C = nms_classes(nms_mode, C); n.max_out = max_out; n.iou_thr = iou_thresh;
     n.ws = d_sort_ws; n.ws_bytes = ws_bytes; n.rows = d_rows; n.kept = d_kept; n.count = d_count; n.general_only = h->opts.nms_general != 0;
-    n.per_class = per_class; n.C = C;
     HIPCHK(h, launch_sort_nms(n, reinterpret_cast<hipStream_t>(stream)));
     if (per_class) { h->pc_counts = nms_class_counts_ptr(d_sort_ws, B, N, C); h->pc_B = B; h->pc_C = C; }
     return BYOLO_OK;

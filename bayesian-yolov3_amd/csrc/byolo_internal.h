@@ -142,6 +142,15 @@ static constexpr int CNT_PER_STEP = 1024;      // >= resident workgroups of any 
 // exactly.  (Measured at 608x608, T=4 against the float64 oracle: scale 1, 4, 16 are indistinguishable -- DESIGN.md 5.)
 static constexpr float ACT_SCALE = 4.f;
 
+// The three NMS modes are one pipeline over a class count (NmsParams::C): the classes a BYOLO_NMS_* mode runs one NMS for ...
+static inline int nms_classes(int nms_mode, int cls_cnt) {
+    return nms_mode == BYOLO_NMS_PER_CLASS ? cls_cnt : nms_mode == BYOLO_NMS_TWO_CLASS ? 2 : 1;
+}
+// ... and its workspace.  BYOLO_NMS_AGNOSTIC takes the two-class size as well: byolo_nms_workspace_bytes(B, N) knows no mode and
+// is documented as enough for both (the size grows with the class count).
+static inline size_t nms_workspace_bytes_ex(int B, int64_t N, int nms_mode, int cls_cnt) {
+    return nms_workspace_bytes(B, N, nms_mode == BYOLO_NMS_PER_CLASS ? cls_cnt : 2);
+}
 
 }  // namespace byi
 using namespace byi;

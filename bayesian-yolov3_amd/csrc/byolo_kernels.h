@@ -269,19 +269,20 @@ hipError_t launch_decode(int kind, const DecodeParams& p, hipStream_t st);
 // decode_epistemic's dict entries outside the box row: ev_loc [B,lh,lw,3,4], covar [B,lh,lw,3,4,4], obj / cls samples
 hipError_t launch_epi_stats(const DecodeParams& p, float* ev_loc, float* covar, float* obj_s, float* cls_s, hipStream_t st);
 
-size_t nms_workspace_bytes(int B, int64_t N);
-size_t nms_workspace_bytes_ex(int B, int64_t N, int per_class, int C);   // per_class: BYOLO_NMS_PER_CLASS with C classes
+size_t nms_workspace_bytes(int B, int64_t N, int C);     // enough for any class count up to C
+// (the BYOLO_NMS_* mode -> C mapping, for C below and for the workspace: nms_classes / nms_workspace_bytes_ex, byolo_internal.h)
 struct NmsParams {
     const float* boxes;      // [B, N, D]
     int B; int64_t N; int D, obj_idx, cls_start;
-    int two_class, max_out; float iou_thr;
+    int C;                   // classes, one NMS each, side by side (1 .. BYOLO_MAX_CLASSES) on columns cls_start .. cls_start + C - 1:
+                             // 1 = BYOLO_NMS_AGNOSTIC (every candidate row, no class column is read, cls_start unused), 2 =
+                             // BYOLO_NMS_TWO_CLASS, cls_cnt = BYOLO_NMS_PER_CLASS; rows / kept hold C * max_out per image
+    int max_out; float iou_thr;
     void* ws; size_t ws_bytes;
     float* rows; int32_t* kept; int32_t* count;
-    int general_only;        // byolo_plan_opts.nms_general: the general path for every image (tests)
-    int per_class, C;        // BYOLO_NMS_PER_CLASS: one NMS per class, C = class count (1 .. BYOLO_MAX_CLASSES); ws_bytes >=
-                             // nms_workspace_bytes_ex(B, N, 1, C), rows / kept hold C * max_out per image
+    int general_only;        // byolo_plan_opts.nms_general: the general path for every class (tests)
 };
-const int32_t* nms_class_counts_ptr(void* ws, int B, int64_t N, int C);   // per_class: the kept-per-class counts [B, C] inside ws
+const int32_t* nms_class_counts_ptr(void* ws, int B, int64_t N, int C);   // the kept-per-class counts [B, C] of a run with C classes, inside ws
 hipError_t launch_sort_nms(const NmsParams& p, hipStream_t st);
 
 // ---- ground-truth encoding and training loss (train_kernels.hip) ------------------------

@@ -1,12 +1,12 @@
-// tail_kernels.hip -- anchor decode (K6), MC-sample aggregation + decode (K7), score sort (K8) and
+// tail_kernels.hip -- anchor decode (K6), MC-sample aggregation + decode (K7), score order (K8) and
 // greedy NMS + gather (K9) of SURVEY.md section 2.1, as wavefront-level gfx950 kernels.
 //
 //   decode_std / decode_ale : lib_yolo/layers.py:11-84 (split) + :191-346 (decode) + :349-358 (entropies)
 //   decode_epi              : lib_yolo/layers.py:361-411 (T-reduction) + :414-502 (decode)
 //   all three write rows straight at their concat_bbox position (inference_epistemic.py:173-184,
 //   inference_aleatoric.py:181-192): n = base(layer) + prior*lh*lw + row*lw + col
-//   sort_keys + nms         : tf.image.non_max_suppression(boxes[:, :4], boxes[:, obj_idx], 1000) + tf.gather
-//                             (inference_epistemic.py:99-128 incl. the commented 2-class variant)
+//   pc_* (one NMS per class): tf.image.non_max_suppression(boxes[:, :4], boxes[:, obj_idx], 1000) + tf.gather
+//                             (inference_epistemic.py:99-128 incl. the commented 2-class variant), for 1, 2 or cls_cnt classes
 // HBM-bound / dependency-bound byte work: no MFMA here.
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -377,17 +377,10 @@ hipError_t launch_decode(int kind, const DecodeParams& p, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// K8: per-image sort of (score desc, index asc) as 64-bit keys, bitonic, one 1024-thread
-// workgroup per image; sub-sequences of SORT_CH keys are sorted in LDS, only strides >= SORT_CH go
-// through global memory (L2-resident).
+// K8 / K9: score order, greedy NMS and gather.  One pipeline serves every mode (the pc_* kernels at the end of this
+// file); what follows first are the device functions its kernels share.  A sort key is 64 bits, (score key, row index):
+// ascending keys == (score descending, index ascending), the order TensorFlow's kernel visits the boxes in.
 // ------------------------------------------------------------------------------------------------
-static constexpr int SORT_THREADS = 1024;
-static constexpr int SORT_CH = 4096;                        // u64 keys per LDS chunk (32 KiB)
-
-static inline int64_t next_pow2(int64_t n) { int64_t p = 1; while (p < n) p <<= 1; return p; }
-static inline int64_t sort_np(int64_t N) { const int64_t p = next_pow2(N); return p < SORT_CH ? SORT_CH : p; }
-
-
 __device__ __forceinline__ unsigned int score_key(float f) {
     // ascending key == descending score; NaN and scores <= -FLT_MAX are not candidates
     // (TF: `score > std::numeric_limits<float>::lowest()`), they sort last.
@@ -401,77 +394,9 @@ __device__ __forceinline__ void ce(unsigned long long& a, unsigned long long& b,
     if ((a > b) == up) { const unsigned long long t = a; a = b; b = t; }
 }
 
-__global__ __launch_bounds__(SORT_THREADS) void sort_keys_kernel(const float* boxes, int64_t N, int D, int obj_idx,
-                                                                 int64_t NP, unsigned long long* keys_all,
-                                                                 int* n_valid_all, const int* need) {
-    __shared__ unsigned long long sk[SORT_CH];
-    __shared__ int s_valid;
-    const int b = blockIdx.x, tid = threadIdx.x;
-    if (need && !need[b]) return;                            // the fast path already finished this image
-    unsigned long long* keys = keys_all + (size_t)b * NP;
-    const float* bx = boxes + (size_t)b * N * D;
-    if (tid == 0) s_valid = 0;
-    __syncthreads();
-    int local_valid = 0;
-    const int64_t nch = NP / SORT_CH;
-    // phase 1: build keys and fully sort each chunk in LDS (direction by global index)
-    for (int64_t ch = 0; ch < nch; ++ch) {
-        for (int i = tid; i < SORT_CH; i += SORT_THREADS) {
-            const int64_t g = ch * SORT_CH + i;
-            unsigned long long k = ~0ull;
-            if (g < N) {
-                const unsigned int sk32 = score_key(bx[(size_t)g * D + obj_idx]);
-                if (sk32 != 0xFFFFFFFFu) { k = ((unsigned long long)sk32 << 32) | (unsigned int)g; ++local_valid; }
-            }
-            sk[i] = k;
-        }
-        __syncthreads();
-        for (int k = 2; k <= SORT_CH; k <<= 1) {
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                for (int t = tid; t < SORT_CH / 2; t += SORT_THREADS) {
-                    const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-                    const bool up = (((ch * SORT_CH + i) & k) == 0);
-                    ce(sk[i], sk[i + j], up);
-                }
-                __syncthreads();
-            }
-        }
-        for (int i = tid; i < SORT_CH; i += SORT_THREADS) keys[ch * SORT_CH + i] = sk[i];
-        __syncthreads();
-    }
-    // phase 2: merge across chunks
-    for (int64_t k = 2 * (int64_t)SORT_CH; k <= NP; k <<= 1) {
-        for (int64_t j = k >> 1; j >= SORT_CH; j >>= 1) {
-            for (int64_t t = tid; t < NP / 2; t += SORT_THREADS) {
-                const int64_t i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-                const bool up = ((i & k) == 0);
-                unsigned long long a = keys[i], c = keys[i + j];
-                if ((a > c) == up) { keys[i] = c; keys[i + j] = a; }
-            }
-            __syncthreads();
-        }
-        for (int64_t ch = 0; ch < nch; ++ch) {
-            for (int i = tid; i < SORT_CH; i += SORT_THREADS) sk[i] = keys[ch * SORT_CH + i];
-            __syncthreads();
-            const bool up = (((ch * SORT_CH) & k) == 0);
-            for (int j = SORT_CH >> 1; j > 0; j >>= 1) {
-                for (int t = tid; t < SORT_CH / 2; t += SORT_THREADS) {
-                    const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-                    ce(sk[i], sk[i + j], up);
-                }
-                __syncthreads();
-            }
-            for (int i = tid; i < SORT_CH; i += SORT_THREADS) keys[ch * SORT_CH + i] = sk[i];
-            __syncthreads();
-        }
-    }
-    atomicAdd(&s_valid, local_valid);
-    __syncthreads();
-    if (tid == 0) n_valid_all[b] = s_valid;
-}
-
 // ------------------------------------------------------------------------------------------------
-// K9: greedy NMS, one 1024-thread workgroup per image, candidates in sorted order, 1024 per round:
+// The exact walk (pc_general_kernel): one 1024-thread workgroup per class of an image, candidates in sorted order,
+// 1024 per round:
 //   phase A  every lane tests its candidate against all boxes kept in earlier rounds (LDS broadcast)
 //   phase B  the 16 waves take turns: intra-wave 64x64 suppression bit-matrix, serial resolve over
 //            the 64 candidates with readlane, kept boxes appended to the LDS list, the later waves
@@ -480,7 +405,7 @@ __global__ __launch_bounds__(SORT_THREADS) void sort_keys_kernel(const float* bo
 // (__f*_rn: no FMA contraction), std::min/std::max NaN semantics -> kept indices bit-exact.
 // ------------------------------------------------------------------------------------------------
 static constexpr int NMS_THREADS = 1024;
-static constexpr int NMS_MAXK = 2048;                        // max_out limit per class pass
+static constexpr int NMS_MAXK = 2048;                        // max_out limit per class
 
 struct NBox { float y0, x0, y1, x1, area; };
 
@@ -510,11 +435,11 @@ struct WalkLds {
     int s_nk;
 };
 
-// One greedy pass of the whole workgroup over the score-ordered `keys[0 .. n_valid)`: member(row) says whether the
-// row is a candidate of this pass, emit(pos, idx) receives the pos-th kept box.  Returns the number kept (uniform).
-template <class Member, class Emit>
+// One greedy pass of the whole workgroup over the score-ordered `keys[0 .. n_valid)`: emit(pos, idx) receives the
+// pos-th kept box.  Returns the number kept (uniform).
+template <class Emit>
 __device__ __forceinline__ int greedy_walk(WalkLds& L, const float* bx, int D, const unsigned long long* keys, int n_valid,
-                                           int max_out, float thr, Member member, Emit emit) {
+                                           int max_out, float thr, Emit emit) {
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     if (tid == 0) L.s_nk = 0;
     __syncthreads();
@@ -528,7 +453,6 @@ __device__ __forceinline__ int greedy_walk(WalkLds& L, const float* bx, int D, c
             idx = (int)(keys[i] & 0xFFFFFFFFull);
             const float* r = bx + (size_t)idx * D;
             me = make_box(r[0], r[1], r[2], r[3]);
-            alive = member(r);
         }
         // phase A: against everything kept in earlier rounds
         for (int k = 0; k < nk_cur; ++k) {
@@ -584,170 +508,20 @@ __device__ __forceinline__ int greedy_walk(WalkLds& L, const float* bx, int D, c
     return nk_cur;
 }
 
-__global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const float* boxes, int64_t N, int D, int obj_idx,
-                                                          int cls_start, int two_class, int max_out, float thr,
-                                                          int64_t NP, const unsigned long long* keys_all,
-                                                          const int* n_valid_all, float* rows, int32_t* kept,
-                                                          int32_t* count, const int* need) {
-    __shared__ WalkLds L;
-    __shared__ int k_idx[2 * NMS_MAXK];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    if (need && !need[b]) return;                            // the fast path already finished this image
-    const float* bx = boxes + (size_t)b * N * D;
-    const unsigned long long* keys = keys_all + (size_t)b * NP;
-    const int n_valid = n_valid_all[b];
-    const int npass = two_class ? 2 : 1;
-    int out_base = 0, first_cnt = 0;
-
-    for (int pass = 0; pass < npass; ++pass) {
-        const int nk = greedy_walk(L, bx, D, keys, n_valid, max_out, thr,
-            [&](const float* r) {
-                if (!two_class) return true;
-                const float c0 = r[cls_start], c1 = r[cls_start + 1];
-                return (pass == 0) ? (c0 > c1) : (c1 > c0);               // strict; ties dropped (:108-110)
-            },
-            [&](int pos, int idx) { k_idx[out_base + pos] = idx; });
-        if (pass == 0) first_cnt = nk;
-        out_base += nk;
-        __syncthreads();
-    }
-    // gather rows (tf.gather) + zero fill
-    const int cap = max_out * npass;
-    float* ro = rows + (size_t)b * cap * D;
-    int32_t* ko = kept + (size_t)b * cap;
-    for (int e = tid; e < cap * D; e += NMS_THREADS) {
-        const int k = e / D, c = e - k * D;
-        ro[e] = (k < out_base) ? bx[(size_t)k_idx[k] * D + c] : 0.f;
-    }
-    for (int k = tid; k < cap; k += NMS_THREADS) ko[k] = (k < out_base) ? k_idx[k] : -1;
-    if (tid == 0) { count[2 * b] = out_base; count[2 * b + 1] = first_cnt; }
-}
-
 // ------------------------------------------------------------------------------------------------
-// Fast path of K8/K9: greedy NMS only ever looks at a PREFIX of the score order (until max_out boxes
-// are kept), and on that prefix it is a bit-matrix problem that the whole chip can work on:
-//   topk_select   per image, one workgroup: 3-level radix select (11+11+10 bits of the score key) of
-//                 the best >= NMS_TOPK candidates, compaction, bitonic sort in LDS  -> sorted prefix
-//   nms_matrix    suppression bit matrix of the prefix (row r, bit c: c later than r and IoU > thr),
-//                 64x64 tiles on ALL CUs (upper triangle only)
-//   nms_scan      per image: serial greedy scan over the prefix, 64 candidates per step from LDS,
-//                 the 4096-bit "removed" set lives in one wave's registers (lane w = word w)
-//   nms_finish    gather rows (tf.gather) + counts
-// Same result as the sequential definition.  If the prefix is exhausted before max_out boxes are kept
-// while more candidates exist (pathological clustering), or scores tie en masse, the image is flagged
-// and the exact general kernels above (full sort + nms_kernel) redo it -- decided on the device, no
-// host round trip.
+// The prefix path: greedy NMS only ever looks at a PREFIX of the score order (until max_out boxes are kept), and on
+// that prefix it is a bit-matrix problem that the whole chip can work on:
+//   matrix_tile   suppression bit matrix of the sorted prefix (row r, bit c: c later than r and IoU > thr), in 64 x 64
+//                 tiles, upper triangle only
+//   scan_prefix   serial greedy scan over the prefix, 64 candidates per step from LDS, the 4096-bit "removed" set
+//                 lives in one wave's registers (lane w = word w)
+// Same result as the sequential definition.  If the prefix is exhausted before max_out boxes are kept while more
+// candidates exist (pathological clustering), or scores tie en masse, the class is flagged and the exact walk above
+// redoes it after a full sort -- decided on the device, no host round trip.
 // ------------------------------------------------------------------------------------------------
 static constexpr int NMS_TOPK = 4096;                        // prefix length / matrix dimension
 static constexpr int NMS_CAP = 8192;                         // LDS sort capacity (prefix + score ties)
 static constexpr int NMS_WORDS = NMS_TOPK / 64;
-
-struct NmsWs {                                               // carve-up of the workspace
-    unsigned long long* keys; int* n_valid;                  // general path
-    unsigned long long* cand; int* n_cand; int* more; int* need; int* cnt;   // cnt [B][2]
-    unsigned long long* mask; int* kidx;
-};
-static size_t nms_ws_layout(int B, int64_t N, char* base, NmsWs* w) {
-    size_t o = 0;
-    auto take = [&](size_t bytes) { char* p = base ? base + o : nullptr; o += (bytes + 255) / 256 * 256; return p; };
-    char* a = take((size_t)B * sort_np(N) * 8); char* b = take((size_t)B * 4);
-    char* c = take((size_t)B * NMS_CAP * 8); char* d = take((size_t)B * 4); char* e = take((size_t)B * 4);
-    char* f = take((size_t)B * 4); char* g = take((size_t)B * 8);
-    char* hh = take((size_t)B * NMS_TOPK * NMS_WORDS * 8); char* i = take((size_t)B * 2 * NMS_MAXK * 4);
-    if (w) { w->keys = (unsigned long long*)a; w->n_valid = (int*)b; w->cand = (unsigned long long*)c; w->n_cand = (int*)d;
-             w->more = (int*)e; w->need = (int*)f; w->cnt = (int*)g; w->mask = (unsigned long long*)hh; w->kidx = (int*)i; }
-    return o;
-}
-size_t nms_workspace_bytes(int B, int64_t N) { return nms_ws_layout(B, N, nullptr, nullptr); }
-
-__global__ __launch_bounds__(1024) void topk_select_kernel(const float* boxes, int64_t N, int D, int obj_idx, int cls_start,
-                                                           int two_class, int pass, unsigned long long* cand_all,
-                                                           int* n_cand_all, int* more_all, int* need) {
-    extern __shared__ __attribute__((aligned(16))) unsigned long long sbuf[];      // NMS_CAP keys
-    __shared__ int hist[2048];
-    __shared__ int part[32];
-    __shared__ int s_digit, s_below, s_le, s_cnt;
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const float* bx = boxes + (size_t)b * N * D;
-    if (pass == 0 && tid == 0) need[b] = 0;
-    auto key_of = [&](int64_t i) -> unsigned int {
-        const float* r = bx + (size_t)i * D;
-        if (two_class) {
-            const float c0 = r[cls_start], c1 = r[cls_start + 1];
-            if (!((pass == 0) ? (c0 > c1) : (c1 > c0))) return 0xFFFFFFFFu;       // strict; ties dropped
-        }
-        return score_key(r[obj_idx]);
-    };
-    unsigned int prefix = 0, pmask = 0;
-    int below = 0, n_valid = 0, C = 0;
-    bool ties_overflow = false;
-    const int shifts[3] = {21, 10, 0}, widths[3] = {11, 11, 10};
-    for (int level = 0; level < 3; ++level) {
-        const int shift = shifts[level], nd = 1 << widths[level];
-        for (int i = tid; i < 2048; i += 1024) hist[i] = 0;
-        __syncthreads();
-        for (int64_t i = tid; i < N; i += 1024) {
-            const unsigned int k = key_of(i);
-            if (k != 0xFFFFFFFFu && (k & pmask) == prefix) atomicAdd(&hist[(k >> shift) & (nd - 1)], 1);
-        }
-        __syncthreads();
-        if (tid < 32) { int s = 0; for (int d = tid * 64; d < tid * 64 + 64; ++d) s += hist[d]; part[tid] = s; }
-        __syncthreads();
-        if (tid == 0) {
-            int total = 0;
-            for (int q = 0; q < 32; ++q) total += part[q];
-            s_cnt = total;                                   // level 0: nothing filtered yet = #valid scores
-        }
-        __syncthreads();
-        if (level == 0) n_valid = s_cnt;
-        const int target = n_valid < NMS_TOPK ? n_valid : NMS_TOPK;
-        if (tid == 0) {                                      // smallest digit d with below + #(digit <= d) >= target
-            int cum = below, q = 0;
-            while (q < 31 && cum + part[q] < target) { cum += part[q]; ++q; }
-            int d = q * 64;
-            while (d < q * 64 + 63 && cum + hist[d] < target) { cum += hist[d]; ++d; }
-            s_digit = d; s_below = cum; s_le = cum + hist[d];
-        }
-        __syncthreads();
-        prefix |= (unsigned int)s_digit << shift;
-        pmask |= (unsigned int)(nd - 1) << shift;
-        below = s_below;
-        C = s_le;
-        __syncthreads();
-        if (C <= NMS_CAP) break;                             // every key <= this (partial) threshold fits
-        if (level == 2) ties_overflow = true;                // > NMS_CAP boxes share one exact score
-    }
-    if (n_valid == 0) C = 0;
-    if (ties_overflow) { C = 0; if (tid == 0) need[b] = 1; }
-    // compaction of the keys <= threshold, then sort
-    if (tid == 0) s_cnt = 0;
-    __syncthreads();
-    if (C > 0) {
-        for (int64_t i = tid; i < N; i += 1024) {
-            const unsigned int k = key_of(i);
-            if (k != 0xFFFFFFFFu && (k & pmask) <= prefix) {
-                const int pos = atomicAdd(&s_cnt, 1);
-                sbuf[pos] = ((unsigned long long)k << 32) | (unsigned int)i;
-            }
-        }
-    }
-    __syncthreads();
-    int P2 = 64;
-    while (P2 < C) P2 <<= 1;
-    for (int i = C + tid; i < P2; i += 1024) sbuf[i] = ~0ull;
-    __syncthreads();
-    for (int k = 2; k <= P2; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < P2 / 2; t += 1024) {
-                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-                ce(sbuf[i], sbuf[i + j], (i & k) == 0);
-            }
-            __syncthreads();
-        }
-    unsigned long long* cand = cand_all + (size_t)b * NMS_CAP;
-    for (int i = tid; i < C; i += 1024) cand[i] = sbuf[i];
-    if (tid == 0) { n_cand_all[b] = C; more_all[b] = n_valid > C ? 1 : 0; }
-}
 
 // One 64 x 64 tile of a suppression matrix: rows rb*64.., bit columns w*64.. of the Kc-long sorted prefix `cand`;
 // `mask` holds NMS_WORDS words per row.  One wave.
@@ -775,18 +549,6 @@ __device__ __forceinline__ void matrix_tile(const float* bx, int D, float thr, c
         }
         mask[(size_t)r * NMS_WORDS + w] = bits;
     }
-}
-
-__global__ __launch_bounds__(64) void nms_matrix_kernel(const float* boxes, int64_t N, int D, float thr,
-                                                        const unsigned long long* cand_all, const int* n_cand_all,
-                                                        unsigned long long* mask_all) {
-    const int w = blockIdx.x, rb = blockIdx.y, b = blockIdx.z;
-    if (w < rb) return;                                      // lower triangle is never read
-    int Kc = n_cand_all[b];
-    if (Kc > NMS_TOPK) Kc = NMS_TOPK;
-    if (rb * 64 >= Kc) return;
-    matrix_tile(boxes + (size_t)b * N * D, D, thr, cand_all + (size_t)b * NMS_CAP, Kc, rb, w,
-                mask_all + (size_t)b * NMS_TOPK * NMS_WORDS);
 }
 
 // Serial greedy scan of one sorted prefix (`cand`, n_cand keys, its matrix `mask`) by one 256-thread workgroup:
@@ -865,46 +627,18 @@ __device__ __forceinline__ void scan_prefix(int max_out, const unsigned long lon
     }
 }
 
-
-__global__ __launch_bounds__(256) void nms_scan_kernel(int max_out, int pass, const unsigned long long* cand_all,
-                                                       const int* n_cand_all, const int* more_all,
-                                                       const unsigned long long* mask_all, int* kidx_all, int* cnt_all,
-                                                       int* need) {
-    const int b = blockIdx.x;
-    const int n_cand = n_cand_all[b];
-    const int base = pass ? cnt_all[2 * b] : 0;
-    scan_prefix(max_out, cand_all + (size_t)b * NMS_CAP, n_cand, &more_all[b], mask_all + (size_t)b * NMS_TOPK * NMS_WORDS,
-                kidx_all + (size_t)b * 2 * NMS_MAXK + base, &cnt_all[2 * b + pass], &need[b]);
-}
-
-__global__ __launch_bounds__(1024) void nms_finish_kernel(const float* boxes, int64_t N, int D, int max_out, int npass,
-                                                         const int* kidx_all, const int* cnt_all, const int* need,
-                                                         float* rows, int32_t* kept, int32_t* count) {
-    const int b = blockIdx.x, tid = threadIdx.x;
-    if (need[b]) return;                                     // the general kernels write this image
-    const float* bx = boxes + (size_t)b * N * D;
-    const int* kidx = kidx_all + (size_t)b * 2 * NMS_MAXK;
-    const int first = cnt_all[2 * b], total = first + (npass > 1 ? cnt_all[2 * b + 1] : 0);
-    const int cap = max_out * npass;
-    float* ro = rows + (size_t)b * cap * D;
-    int32_t* ko = kept + (size_t)b * cap;
-    for (int e = tid; e < cap * D; e += 1024) {
-        const int k = e / D, c = e - k * D;
-        ro[e] = (k < total) ? bx[(size_t)kidx[k] * D + c] : 0.f;
-    }
-    for (int k = tid; k < cap; k += 1024) ko[k] = (k < total) ? kidx[k] : -1;
-    if (tid == 0) { count[2 * b] = total; count[2 * b + 1] = first; }
-}
-
 // ------------------------------------------------------------------------------------------------
-// Per-class mode (BYOLO_NMS_PER_CLASS): the classes of an image run side by side.
+// The NMS pipeline of every mode: one NMS per class, the classes of an image side by side.  The modes differ in the class
+// count C alone (NmsParams::C): BYOLO_NMS_AGNOSTIC is one class that every candidate row belongs to (no class column is
+// read), BYOLO_NMS_TWO_CLASS two, BYOLO_NMS_PER_CLASS the model's cls_cnt.
 //   pc_classify   every row: its class (the strict unique maximum of the C class scores, else none) as one byte --
 //                 the digit above the score bits of the sort key -- and the per-image class histogram (two kernels:
 //                 rows read in place for few classes, class scores staged through LDS for many)
 //   pc_offsets    per image: segment / matrix-row / tile offsets of the classes (prefix sums of the histogram)
 //   pc_scatter    counting sort on the class digit: (score key, index) of every member into its class segment
 //   pc_select     grid (class, image): sorted prefix of the segment -- the whole segment where it fits LDS (NMS_CAP),
-//                 else the 3-level radix select of topk_select over the segment's keys
+//                 else a 3-level radix select (11 + 11 + 10 bits of the score key) of the best >= NMS_TOPK keys, then
+//                 compaction and a bitonic sort in LDS
 //   pc_matrix     the 64 x 64 tiles of all classes' suppression matrices, as one linear list per image
 //   pc_scan       grid (class, image): scan_prefix; a class whose prefix cannot prove its result sets need[b][c]
 //   pc_general    grid (class, image), flagged classes only: full sort of the segment + greedy_walk
@@ -935,7 +669,7 @@ static size_t pc_ws_layout(int B, int64_t N, int C, char* base, PcWs* w) {
     size_t o = 0;
     auto take = [&](size_t bytes) { char* p = base ? base + o : nullptr; o += (bytes + 255) / 256 * 256; return p; };
     const size_t ci = (size_t)B * (C + 1) * 4;
-    char* hc = take(2 * ci);                                 // hist + cursor: cleared by one memset
+    char* hc = take(2 * ci);                                 // hist + cursor: cleared by one launch_zero_words
     char* so = take(ci); char* ro = take(ci); char* to = take(ci); char* nc = take(ci); char* mo = take(ci); char* ne = take(ci);
     char* cn = take((size_t)B * C * 4);
     char* cl = take((size_t)B * N);
@@ -953,17 +687,17 @@ const int32_t* nms_class_counts_ptr(void* ws, int B, int64_t N, int C) {
     pc_ws_layout(B, N, C, reinterpret_cast<char*>(ws), &w);
     return w.cnt;
 }
-size_t nms_workspace_bytes_ex(int B, int64_t N, int per_class, int C) {
-    return per_class ? pc_ws_layout(B, N, C, nullptr, nullptr) : nms_workspace_bytes(B, N);
-}
+size_t nms_workspace_bytes(int B, int64_t N, int C) { return pc_ws_layout(B, N, C, nullptr, nullptr); }   // grows with C
 
 // The class of one row from its C class scores `t` (global memory or LDS) and its score: class c iff cls[c] > cls[k] for every
 // k != c -- a maximum attained twice or any NaN leaves no such c; a score that is no NMS candidate leaves none either.
+// One class: every candidate is a member and `t` is not read (the rows of BYOLO_NMS_AGNOSTIC need not have class columns).
 __device__ __forceinline__ int classify_row(const float* t, int C, float score) {
     if (score_key(score) == 0xFFFFFFFFu) return PC_NONE;
+    if (C == 1) return 0;
     float best = t[0];
     int arg = 0;
-    bool uniq = true, nan = C > 1 && best != best;
+    bool uniq = true, nan = best != best;
     for (int c = 1; c < C; ++c) {
         const float v = t[c];
         nan |= v != v;
@@ -1072,7 +806,7 @@ __global__ __launch_bounds__(1024) void pc_select_kernel(int64_t N, int C, PcWs 
     bool ties_overflow = false;
     if (n <= NMS_CAP) {
         for (int i = tid; i < n; i += 1024) sbuf[i] = seg[i];
-    } else {                                                 // radix select of the best >= NMS_TOPK keys, as topk_select_kernel
+    } else {                                                 // radix select of the best >= NMS_TOPK keys
         unsigned int prefix = 0, pmask = 0;
         int below = 0;
         const int shifts[3] = {21, 10, 0}, widths[3] = {11, 11, 10};
@@ -1191,7 +925,7 @@ __global__ __launch_bounds__(NMS_THREADS) void pc_general_kernel(const float* bo
         }
     int* kidx = w.kidx + ((size_t)b * C + c) * NMS_MAXK;
     const int nk = greedy_walk(L, boxes + (size_t)b * N * D, D, keys, n, max_out, thr,
-                               [](const float*) { return true; }, [&](int pos, int idx) { kidx[pos] = idx; });
+                               [&](int pos, int idx) { kidx[pos] = idx; });
     if (tid == 0) w.cnt[(size_t)b * C + c] = nk;
 }
 
@@ -1228,15 +962,17 @@ __global__ __launch_bounds__(256) void pc_finish_kernel(const float* boxes, int6
     if (blockIdx.x == 0 && tid == 0) { count[2 * b] = total; count[2 * b + 1] = cnt[0]; }
 }
 
-static hipError_t launch_per_class_nms(const NmsParams& p, hipStream_t st) {
+hipError_t launch_sort_nms(const NmsParams& p, hipStream_t st) {
     const int C = p.C;
-    if (C < 1 || C > BYOLO_MAX_CLASSES || p.cls_start < 0 || p.cls_start + C > p.D) return hipErrorInvalidValue;
+    if (p.max_out > NMS_MAXK || p.max_out < 1 || C < 1 || C > BYOLO_MAX_CLASSES) return hipErrorInvalidValue;
+    if (C > 1 && (p.cls_start < 0 || p.cls_start + C > p.D)) return hipErrorInvalidValue;
     if (p.N >= (1ll << 31) || p.ws_bytes < pc_ws_layout(p.B, p.N, C, nullptr, nullptr)) return hipErrorInvalidValue;
     PcWs w;
     pc_ws_layout(p.B, p.N, C, reinterpret_cast<char*>(p.ws), &w);
     const int64_t R = pc_mask_rows(p.N, C);
     const dim3 by_row((unsigned)((p.N + 255) / 256), p.B), by_tile((unsigned)((p.N + PC_TILE - 1) / PC_TILE), p.B), by_class(C, p.B);
-    if (hipError_t e = hipMemsetAsync(w.hist, 0, (size_t)2 * p.B * (C + 1) * 4, st); e != hipSuccess) return e;
+    // (a kernel, not a memset node: a forward captured as a launch graph replays this sequence -- see launch_zero_words)
+    if (hipError_t e = launch_zero_words(w.hist, (int64_t)2 * p.B * (C + 1), st); e != hipSuccess) return e;
     if (C <= PC_DIRECT_C)
         hipLaunchKernelGGL(pc_classify_kernel, by_row, dim3(256), 0, st, p.boxes, p.N, p.D, p.obj_idx, p.cls_start, C, w.cls, w.hist);
     else
@@ -1259,43 +995,6 @@ static hipError_t launch_per_class_nms(const NmsParams& p, hipStream_t st) {
     hipLaunchKernelGGL(pc_general_kernel, by_class, dim3(NMS_THREADS), 0, st, p.boxes, p.N, p.D, C, p.max_out, p.iou_thr, w);
     hipLaunchKernelGGL(pc_finish_kernel, dim3((unsigned)(((int64_t)C * p.max_out + PC_ROWS - 1) / PC_ROWS), p.B), dim3(256), 0, st,
                        p.boxes, p.N, p.D, C, p.max_out, w, p.rows, p.kept, p.count);
-    return hipGetLastError();
-}
-
-hipError_t launch_sort_nms(const NmsParams& p, hipStream_t st) {
-    if (p.max_out > NMS_MAXK || p.max_out < 1) return hipErrorInvalidValue;
-    if (p.per_class) return launch_per_class_nms(p, st);
-    const int64_t NP = sort_np(p.N);
-    if (p.ws_bytes < nms_workspace_bytes(p.B, p.N)) return hipErrorInvalidValue;
-    NmsWs w;
-    nms_ws_layout(p.B, p.N, reinterpret_cast<char*>(p.ws), &w);
-    const bool general_only = p.general_only != 0;            // byolo_plan_opts.nms_general
-    const int* need = nullptr;
-    if (!general_only) {
-        static std::atomic<uint64_t> attr_done{0};
-        const size_t lds = (size_t)NMS_CAP * sizeof(unsigned long long);
-        if (hipError_t e = set_dynamic_lds_once(reinterpret_cast<const void*>(topk_select_kernel), lds, attr_done); e != hipSuccess) return e;
-        static std::atomic<uint64_t> scan_attr_done{0};
-        const size_t scan_lds = (size_t)2 * 64 * NMS_WORDS * sizeof(unsigned long long);      // 64 KiB
-        if (hipError_t e = set_dynamic_lds_once(reinterpret_cast<const void*>(nms_scan_kernel), scan_lds, scan_attr_done); e != hipSuccess) return e;
-        const int npass = p.two_class ? 2 : 1;
-        for (int pass = 0; pass < npass; ++pass) {
-            hipLaunchKernelGGL(topk_select_kernel, dim3(p.B), dim3(1024), lds, st, p.boxes, p.N, p.D, p.obj_idx, p.cls_start,
-                               p.two_class, pass, w.cand, w.n_cand, w.more, w.need);
-            hipLaunchKernelGGL(nms_matrix_kernel, dim3(NMS_WORDS, NMS_WORDS, p.B), dim3(64), 0, st, p.boxes, p.N, p.D,
-                               p.iou_thr, w.cand, w.n_cand, w.mask);
-            hipLaunchKernelGGL(nms_scan_kernel, dim3(p.B), dim3(256), scan_lds, st, p.max_out, pass, w.cand, w.n_cand, w.more,
-                               w.mask, w.kidx, w.cnt, w.need);
-        }
-        hipLaunchKernelGGL(nms_finish_kernel, dim3(p.B), dim3(1024), 0, st, p.boxes, p.N, p.D, p.max_out, npass, w.kidx,
-                           w.cnt, w.need, p.rows, p.kept, p.count);
-        need = w.need;
-    }
-    // general path (exact for every input); a no-op per image unless flagged by the fast path
-    hipLaunchKernelGGL(sort_keys_kernel, dim3(p.B), dim3(SORT_THREADS), 0, st, p.boxes, p.N, p.D, p.obj_idx, NP, w.keys,
-                       w.n_valid, need);
-    hipLaunchKernelGGL(nms_kernel, dim3(p.B), dim3(NMS_THREADS), 0, st, p.boxes, p.N, p.D, p.obj_idx, p.cls_start,
-                       p.two_class, p.max_out, p.iou_thr, NP, w.keys, w.n_valid, p.rows, p.kept, p.count, need);
     return hipGetLastError();
 }
 

@@ -47,8 +47,11 @@ enum { BYOLO_DET_STANDARD = 0, BYOLO_DET_ALEATORIC = 1, BYOLO_DET_EPISTEMIC = 2 
  * variant for any class count: row i belongs to class c iff cls[i][c] > cls[i][k] for every k != c (float32, strictly: a
  * maximum attained twice or a NaN class score leaves the row in no class; with one class every row is in class 0), one
  * tf.image.non_max_suppression per class over its members, the kept rows of class 0, 1, ... back to back.  Two classes give
- * BYOLO_NMS_TWO_CLASS bit for bit, one class BYOLO_NMS_AGNOSTIC.  Limits of the mode: 1 .. BYOLO_NMS_MAX_CLASSES classes (the
- * class is one byte above the score bits of the sort key, 255 = no class; the decode kernels stop at 128), N < 2^31. */
+ * BYOLO_NMS_TWO_CLASS bit for bit, one class BYOLO_NMS_AGNOSTIC -- the three modes are ONE device pipeline that runs the
+ * classes of an image side by side: BYOLO_NMS_AGNOSTIC is one class (every row whose score is a candidate; no class column is
+ * read, the rows need not have any), BYOLO_NMS_TWO_CLASS two classes on the columns cls_start, cls_start + 1 (whatever the
+ * handle's cls_cnt; byolo_forward insists on cls_cnt == 2).  Limits: 1 .. BYOLO_NMS_MAX_CLASSES classes (the class is one byte
+ * above the score bits of the sort key, 255 = no class; the decode kernels stop at 128), N < 2^31 in every mode. */
 enum { BYOLO_NMS_AGNOSTIC = 0, BYOLO_NMS_TWO_CLASS = 1, BYOLO_NMS_PER_CLASS = 2 };
 #define BYOLO_NMS_MAX_CLASSES 128
 /* normaliser list of lib_yolo/layers.py:556-571 */
@@ -334,8 +337,9 @@ BYOLO_API int32_t byolo_epistemic_stats(byolo_t* h, const float* d_raw, int32_t 
                                         float* d_ev_loc, float* d_epi_covar, float* d_obj_samples, float* d_cls_samples,
                                         void* stream);
 /* tf.image.non_max_suppression + tf.gather per image on d_boxes [B,N,D] (scores = column obj_idx).
- * d_sort_ws: >= byolo_nms_workspace_bytes(B, N); BYOLO_NMS_PER_CLASS: >= byolo_nms_workspace_bytes_ex(B, N, nms_mode, cls_cnt)
- * (the other modes: the same value as byolo_nms_workspace_bytes; 0 for arguments the mode refuses).  The per-class mode takes
+ * d_sort_ws: >= byolo_nms_workspace_bytes(B, N), the size of two classes, enough for BYOLO_NMS_AGNOSTIC and BYOLO_NMS_TWO_CLASS;
+ * BYOLO_NMS_PER_CLASS: >= byolo_nms_workspace_bytes_ex(B, N, nms_mode, cls_cnt) (the other modes: the same value as
+ * byolo_nms_workspace_bytes; 0 for arguments the mode refuses).  BYOLO_NMS_AGNOSTIC ignores cls_start_idx.  The per-class mode takes
  * its class count from the handle (byolo_cfg.cls_cnt), reads the class scores in columns cls_start_idx .. cls_start_idx +
  * cls_cnt - 1 and sizes d_rows / d_kept by cls_cnt * max_out per image (see byolo_forward).  Refused with BYOLO_ERR_ARG before
  * anything is launched: an unknown mode, class columns outside the row, max_out above 2048 (the limit PER CLASS).

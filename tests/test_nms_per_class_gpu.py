@@ -22,11 +22,11 @@ def _torch():
     return torch
 
 
-def _sort_nms(rows, cls_cnt, mode=2, max_out=1000):
+def _sort_nms(rows, cls_cnt, mode=2, max_out=1000, obj_idx=OBJ_IDX, cls_start_idx=CLS_START):
     torch = _torch()
     from byolo import Engine
     eng = Engine((64, 64, 3), cls_cnt, nms_mode=mode, max_out=max_out)
-    res = eng.sort_nms(torch.from_numpy(rows).cuda(), obj_idx=OBJ_IDX, cls_start_idx=CLS_START)
+    res = eng.sort_nms(torch.from_numpy(rows).cuda(), obj_idx=obj_idx, cls_start_idx=cls_start_idx)
     torch.cuda.synchronize()
     return res
 
@@ -204,3 +204,72 @@ def test_refusals():
     res = eng.sort_nms(rows, obj_idx=OBJ_IDX, cls_start_idx=CLS_START)      # the handle still works
     torch.cuda.synchronize()
     pcr.check_against_ref(rows.cpu().numpy(), res, 3)
+
+
+def _assert_images_equal(res, refs, cap):
+    """The device's rows / kept / count == refs, a (kept rows, kept indices, kept of class 0) per image, bit for bit, with the
+    padding behind them."""
+    rows, kept, count = res["rows"].cpu().numpy(), res["kept"].cpu().numpy(), res["count"].cpu().numpy()
+    assert rows.shape[:2] == (len(refs), cap) and kept.shape == (len(refs), cap) and count.shape == (len(refs), 2)
+    for b, (r_rows, r_keep, n0) in enumerate(refs):
+        n = len(r_keep)
+        assert count[b].tolist() == [n, n0], "image %d: counts %s, reference %s" % (b, count[b].tolist(), [n, n0])
+        assert np.array_equal(kept[b, :n], r_keep), "image %d: kept indices differ" % b
+        assert np.array_equal(rows[b, :n].view(np.uint32), r_rows.view(np.uint32)), "image %d: gathered rows differ" % b
+        assert (kept[b, n:] == -1).all() and (rows[b, n:].view(np.uint32) == 0).all(), "image %d: padding" % b
+
+
+@pytest.mark.parametrize("N,boxes", [(300, "clustered"), (9000, "spread")])
+def test_agnostic_rows_without_class_columns(N, boxes):
+    """BYOLO_NMS_AGNOSTIC reads no class column: rows of box + score alone (D = 5, cls_start_idx behind the row).  300
+    clustered rows sit under every threshold of the pipeline; 9000 are more than the select holds in LDS (8192)."""
+    from oracle import nms_ref
+    full = pcr.random_rows(np.random.default_rng(8), 2, N, 1, boxes=boxes)
+    rows = np.ascontiguousarray(np.concatenate([full[..., 0:4], full[..., OBJ_IDX:OBJ_IDX + 1]], axis=2))
+    assert rows.shape == (2, N, 5)
+    refs = []
+    for b in range(2):
+        r_rows, r_keep = nms_ref.nms_agnostic(rows[b], 4, 1000)
+        print("image %d: the reference keeps %d of %d" % (b, len(r_keep), N))
+        if N == 300:
+            assert len(r_keep) == 39                         # suppression at work, far from max_out
+        else:                                                # max_out filled, and not by the 1000 best scores
+            assert len(r_keep) == 1000 and set(r_keep.tolist()) != set(nms_ref.sort_order(rows[b, :, 4])[:1000].tolist())
+        refs.append((r_rows, r_keep, len(r_keep)))
+    res = _sort_nms(rows, 1, mode=0, obj_idx=4, cls_start_idx=5)
+    _assert_images_equal(res, refs, 1000)
+    count = res["count"].cpu().numpy()
+    assert (count[:, 0] == count[:, 1]).all()
+
+
+def test_agnostic_ignores_class_columns():
+    """BYOLO_NMS_AGNOSTIC on rows that have class columns: a NaN there does not drop the row."""
+    from oracle import nms_ref
+    rows = pcr.random_rows(np.random.default_rng(8), 2, 9000, 2)
+    rows[:, ::7, CLS_START] = np.nan
+    refs = []
+    for b in range(2):
+        r_rows, r_keep = nms_ref.nms_agnostic(rows[b], OBJ_IDX, 1000)
+        nan_kept = int(np.isnan(r_rows[:, CLS_START]).sum())
+        print("image %d: %d of the %d kept rows have a NaN class score" % (b, nan_kept, len(r_keep)))
+        assert nan_kept > 0 and len(r_keep) == 1000
+        refs.append((r_rows, r_keep, len(r_keep)))
+    _assert_images_equal(_sort_nms(rows, 2, mode=0), refs, 1000)
+
+
+def test_two_class_mode_on_three_class_handle():
+    """BYOLO_NMS_TWO_CLASS reads the columns cls_start, cls_start + 1 whatever the handle's cls_cnt: the third class score
+    of these rows takes no part."""
+    from oracle import nms_ref
+    rows = pcr.random_rows(np.random.default_rng(7), 2, 9000, 3)
+    refs = []
+    for b in range(2):
+        r_rows, r_keep, n0 = nms_ref.nms_two_class(rows[b], OBJ_IDX, CLS_START, 1000)
+        p_keep, p_cnt = pcr.nms_per_class(rows[b], OBJ_IDX, CLS_START, 3, 1000)[1:]
+        three = set(p_keep[:int(p_cnt[0] + p_cnt[1])].tolist())
+        missing = sum(1 for k in r_keep.tolist() if k not in three)
+        print("image %d: %d kept (%d of class 0), %d of them not among the first two classes of the 3-class result"
+              % (b, len(r_keep), n0, missing))
+        assert missing > 0 and len(r_keep) > n0 > 0
+        refs.append((r_rows, r_keep, n0))
+    _assert_images_equal(_sort_nms(rows, 3, mode=1), refs, 2000)
