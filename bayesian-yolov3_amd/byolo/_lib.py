@@ -43,6 +43,21 @@ class AugPlan(ctypes.Structure):
                [("color_param", ctypes.c_float), ("noise_param", ctypes.c_float), ("noise_key", ctypes.c_uint64)]
 
 
+EVAL_MAX_GT, EVAL_MAX_UNC, EVAL_RECORD_HEAD = 1024, 16, 7          # BYOLO_EVAL_*
+
+
+class EvalCfg(ctypes.Structure):
+    """include/byolo.h byolo_eval_cfg (field for field; tests/test_eval_cpu.py compares the two)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("struct_bytes", "row_len", "obj_idx", "cls_start_idx", "cls_cnt", "n_unc")] + \
+               [("unc_cols", ctypes.c_int32 * EVAL_MAX_UNC), ("iou_thresh", ctypes.c_float), ("min_score", ctypes.c_float)]
+
+
+class EvalSummary(ctypes.Structure):
+    """include/byolo.h byolo_eval_summary."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("struct_bytes", "overflow", "record_words", "reserved")] + \
+               [(n, ctypes.c_int64) for n in ("n_records", "n_seen", "n_images")]
+
+
 _i32, _i64, _f32 = ctypes.c_int32, ctypes.c_int64, ctypes.c_float
 _vp, _cp, _sz, _u64 = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint64
 _P = ctypes.POINTER
@@ -132,6 +147,14 @@ PROTOTYPES = {
     "byolo_trainer_export": (_i32, [_vp, _vp]),
     "byolo_trainer_taps": (_i32, [_vp, _P(_i32), _i32]),
     "byolo_trainer_layer_output": (_i32, [_vp, _i32, _vp, _i64, _P(_i64), _vp]),
+    "byolo_eval_state_bytes": (_sz, [_i32]),
+    "byolo_eval_create": (_i32, [_P(EvalCfg), _vp, _i64, _vp, _P(_vp)]),
+    "byolo_eval_destroy": (_i32, [_vp]),
+    "byolo_eval_last_error": (_cp, [_vp]),
+    "byolo_eval_reset": (_i32, [_vp, _vp]),
+    "byolo_eval_add": (_i32, [_vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _i32, _vp]),
+    "byolo_eval_finish": (_i32, [_vp, _P(EvalSummary), _P(_i64), _i32, _vp]),
+    "byolo_eval_records": (_i32, [_vp, _vp, _i64, _i64, _vp]),
 }
 
 

@@ -29,7 +29,7 @@ PLAN_DTYPE = np.dtype({'names': [n for n, _ in _lib.AugPlan._fields_],
                                    for _, t in _lib.AugPlan._fields_],
                        'offsets': [getattr(_lib.AugPlan, n).offset for n, _ in _lib.AugPlan._fields_],
                        'itemsize': ctypes.sizeof(_lib.AugPlan)})
-SPLITS = {'train': 1, 'val': 2}
+SPLITS = {'train': 1, 'val': 2, 'eval': 3}
 COLOR_OPS = (_lib.AUG_SATURATION, _lib.AUG_BRIGHTNESS, _lib.AUG_HUE)
 NOISE_OPS = (_lib.AUG_COLORED_SALT_N_PEPPER, _lib.AUG_SALT_N_PEPPER, _lib.AUG_GAUSSIAN)
 
@@ -110,10 +110,13 @@ def draw_augment(rng, plan):
 
 def draw(config, split, epoch, pos, plan):
     """All draws of one image of the stream into `plan` (a PLAN_DTYPE record); returns its crop window (fractions, float32) or
-    None when config['crop'] is False."""
+    None when config['crop'] is False.  split 'eval' draws nothing: the centre crop (ValDataset + ImageCropper.center_crop) or the
+    full frame, no augmentation."""
     rng = rng_for(config.get('seed', 0), split, epoch, pos)
     Hf, Wf = config['full_img_size'][:2]
-    if config['crop']:
+    if config['crop'] and split == 'eval':
+        box = center_crop(plan, config['crop_img_size'][:2], (Hf, Wf))
+    elif config['crop']:
         box = draw_crop(rng, plan, config['crop_img_size'][:2], (Hf, Wf))
     else:
         full_frame(plan, Hf, Wf)
@@ -121,7 +124,7 @@ def draw(config, split, epoch, pos, plan):
     plan['row0'] = 0
     if split == 'train':
         draw_augment(rng, plan)
-    else:                                                                    # val: no augmentation
+    else:                                                                    # val, eval: no augmentation
         for f in ('flip', 'blur_k', 'color_op', 'noise_op', 'color_param', 'noise_param', 'noise_key'):
             plan[f] = 0
     return box

@@ -1,0 +1,271 @@
+"""Scoring a checkpoint on labelled frames: AP, log-average miss rate, score calibration and what the uncertainty columns say
+about true and false positives (include/byolo.h byolo_eval_*; INTEGRATION.md "Evaluation" has the definitions).
+
+Per batch, `Evaluator.add` launches ONE kernel (csrc/eval_kernels.hip) on the current stream that matches the kept rows of
+`Model.run` against the frames' ground truth and appends a record per detection to a device table: no allocation, no host wait.
+`Evaluator.finish` is the only host wait: it orders the table on the device (per class: descending score, then image, then
+row), accumulates true and false positives as integers there, and reduces those integers to the metrics in float64 on the
+host, every sum taken in ascending order so that the figures are reproducible to the last bit."""
+import ctypes
+
+import numpy as np
+
+from . import _lib
+from ._lib import ByoloError, lib
+
+FPPI_REFS = np.logspace(-2, 0, 9)          # the nine reference points of the log-average miss rate
+N_BINS = 10
+
+
+def variant_of(row_len, cls_cnt):
+    """The model variant a row of `row_len` columns belongs to."""
+    for variant, fixed in (('yolov3', 5), ('yolov3_aleatoric', 14), ('bayesian_yolov3_aleatoric', 21)):
+        if row_len == fixed + cls_cnt:
+            return variant
+    raise ValueError('no model variant has rows of %d columns with %d classes' % (row_len, cls_cnt))
+
+
+def uncertainty_columns(variant, cls_cnt):
+    """{name: column} of the uncertainty values of a row, in record order."""
+    C = int(cls_cnt)
+    if variant == 'yolov3':
+        return {}
+    if variant == 'yolov3_aleatoric':
+        return {'ale_x': 4, 'ale_y': 5, 'ale_w': 6, 'ale_h': 7, 'ale_total': 8, 'obj_entropy': 10, 'cls_entropy': 11 + C}
+    if variant == 'bayesian_yolov3_aleatoric':
+        return {'epi_x': 4, 'epi_y': 5, 'epi_w': 6, 'epi_h': 7, 'ale_x': 8, 'ale_y': 9, 'ale_w': 10, 'ale_h': 11, 'epi_total': 12,
+                'ale_total': 13, 'obj_mutual_info': 15, 'obj_entropy': 16, 'cls_mutual_info': 17 + C, 'cls_entropy': 18 + C}
+    raise ValueError('unknown variant %r' % (variant,))
+
+
+def record_dtype(n_unc):
+    """numpy view of one record of the table (include/byolo.h byolo_eval_add)."""
+    fields = [('img', np.int32), ('row', np.int32), ('cls', np.int32), ('score', np.float32), ('tp', np.int32), ('gt', np.int32),
+              ('iou', np.float32)]
+    if n_unc:
+        fields.append(('unc', np.float32, (int(n_unc),)))
+    return np.dtype(fields)
+
+
+def _seq_sum(x):
+    """Sum in ascending index order (np.sum adds pairwise)."""
+    x = np.asarray(x, dtype=np.float64)
+    return float(np.cumsum(x)[-1]) if x.size else 0.0
+
+
+def ap_lamr(cum_tp, cum_fp, n_gt, n_images):
+    """AP (area under the precision envelope over recall, all points) and the log-average miss rate over nine FPPI references
+    from the cumulative integers of one class's detections in score order.  float64; NaN without ground truth."""
+    if n_gt == 0:
+        return float('nan'), float('nan')
+    tp = np.asarray(cum_tp, dtype=np.float64)
+    fp = np.asarray(cum_fp, dtype=np.float64)
+    if tp.size == 0:
+        return 0.0, 1.0
+    r = tp / np.float64(n_gt)
+    p = tp / (tp + fp)
+    env = np.maximum.accumulate(p[::-1])[::-1]
+    ap = _seq_sum((r - np.concatenate([[0.0], r[:-1]])) * env)
+    fppi = fp / np.float64(n_images)
+    last = np.searchsorted(fppi, FPPI_REFS, side='right') - 1
+    mr = np.where(last >= 0, 1.0 - r[np.maximum(last, 0)], 1.0)
+    lamr = float(np.exp(_seq_sum(np.log(np.maximum(1e-10, mr))) / np.float64(len(FPPI_REFS))))
+    return ap, lamr
+
+
+def calibration(score, tp):
+    """10 equal-width score bins of one class: per bin the count, the true positives and the float64 sum of the scores, and
+    ECE = sum_b n_b / n * |tp_b / n_b - mean score_b|."""
+    score = np.asarray(score, dtype=np.float32)
+    tp = np.asarray(tp, dtype=np.int64)
+    bins = np.minimum(N_BINS - 1, (score * np.float32(10.0)).astype(np.int32))
+    count = np.bincount(bins, minlength=N_BINS).astype(np.int64)
+    n_tp = np.bincount(bins, weights=tp, minlength=N_BINS).astype(np.int64)
+    ssum = np.zeros(N_BINS, np.float64)
+    np.add.at(ssum, bins, score.astype(np.float64))
+    n = int(count.sum())
+    ece = 0.0
+    for b in range(N_BINS):
+        if count[b]:
+            ece += count[b] / np.float64(n) * abs(n_tp[b] / np.float64(count[b]) - ssum[b] / np.float64(count[b]))
+    return {'count': count.tolist(), 'tp': n_tp.tolist(), 'score_sum': ssum.tolist(), 'ece': float(ece) if n else float('nan')}
+
+
+class Evaluator:
+    """Evaluator(model_or_layout): a lib_yolo Model, or a dict with row_len, obj_idx, cls_start_idx, cls_cnt and optionally
+    unc_cols ({name: column}; default: the variant's table above).  capacity: records the device table holds (28 + 4 per
+    uncertainty column bytes each); detections beyond it are dropped and `finish` raises ByoloError(ERR_NOMEM)."""
+
+    def __init__(self, model_or_layout, iou_thresh=0.5, min_score=0.0, capacity=1 << 20, device=None, table=None):
+        import torch
+        lay = model_or_layout
+        if not isinstance(lay, dict):
+            lay = dict(row_len=int(lay.engine.num_boxes()[1]), obj_idx=int(lay.obj_idx), cls_start_idx=int(lay.cls_start_idx),
+                       cls_cnt=int(lay.cls_cnt))
+            if device is None:
+                device = model_or_layout.engine.torch_device
+        self.row_len, self.obj_idx, self.cls_start_idx, self.cls_cnt = (int(lay[k]) for k in ('row_len', 'obj_idx', 'cls_start_idx', 'cls_cnt'))
+        unc = lay.get('unc_cols')
+        if unc is None:
+            unc = uncertainty_columns(variant_of(self.row_len, self.cls_cnt), self.cls_cnt)
+        self.unc_names, self.unc_cols = list(unc.keys()), [int(v) for v in unc.values()]
+        if len(self.unc_cols) > _lib.EVAL_MAX_UNC:
+            raise ValueError('at most %d uncertainty columns' % _lib.EVAL_MAX_UNC)
+        self.iou_thresh, self.min_score, self.capacity = float(iou_thresh), float(min_score), int(capacity)
+        self.record_words = _lib.EVAL_RECORD_HEAD + len(self.unc_cols)
+        self.dtype = record_dtype(len(self.unc_cols))
+        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        # `table`: a caller's int32 tensor to hold the records (tests put a guard region behind it)
+        self.table = torch.empty((self.capacity, self.record_words), dtype=torch.int32, device=self.device) if table is None else table
+        assert self.table.is_cuda and self.table.dtype == torch.int32 and self.table.is_contiguous() and \
+            self.table.numel() >= self.capacity * self.record_words
+        self._state = torch.zeros(lib.byolo_eval_state_bytes(self.cls_cnt) // 4, dtype=torch.int32, device=self.device)
+        cfg = _lib.EvalCfg(struct_bytes=ctypes.sizeof(_lib.EvalCfg), row_len=self.row_len, obj_idx=self.obj_idx, cls_start_idx=self.cls_start_idx,
+                           cls_cnt=self.cls_cnt, n_unc=len(self.unc_cols), iou_thresh=self.iou_thresh, min_score=self.min_score)
+        for k, c in enumerate(self.unc_cols):
+            cfg.unc_cols[k] = c
+        self._h = ctypes.c_void_p()
+        self._check(lib.byolo_eval_create(ctypes.byref(cfg), ctypes.c_void_p(self.table.data_ptr()), self.capacity,
+                                          ctypes.c_void_p(self._state.data_ptr()), ctypes.byref(self._h)), handle=False)
+        self.sorted = None
+        self.reset()
+
+    def _check(self, rc, handle=True):
+        if rc < 0:
+            msg = lib.byolo_eval_last_error(self._h if handle else None)
+            raise ByoloError(rc, msg.decode('utf-8', 'replace') if msg else '?')
+        return rc
+
+    def _stream(self):
+        import torch
+        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def close(self):
+        if getattr(self, '_h', None):
+            lib.byolo_eval_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        self._check(lib.byolo_eval_reset(self._h, self._stream()))
+        self.sorted = None
+
+    def _gt(self, x, dtype, shape_tail):
+        import torch
+        if isinstance(x, torch.Tensor):
+            t = x.to(device=self.device, dtype=dtype, non_blocking=True).contiguous()
+        else:
+            host = torch.from_numpy(np.ascontiguousarray(np.asarray(x), dtype={torch.float32: np.float32, torch.int32: np.int32}[dtype]))
+            t = host.pin_memory().to(self.device, non_blocking=True)
+        assert tuple(t.shape[1:]) == shape_tail, (tuple(t.shape), shape_tail)
+        return t
+
+    def add(self, rows, count, gt_boxes, gt_labels, gt_counts):
+        """rows [B, cap, D] float32 and count ([B] or a strided view such as out['count'][:, 0]) int32 as Model.run fills them;
+        gt_boxes [B, gmax, 4] normalised (ymin, xmin, ymax, xmax), gt_labels [B, gmax] 0-based, gt_counts [B]: device tensors
+        on the current stream, or numpy arrays (copied asynchronously).  The tensors may be dropped right after the call: the
+        allocator hands their memory out again in stream order only."""
+        import torch
+        assert rows.is_cuda and rows.dtype == torch.float32 and rows.is_contiguous() and rows.dim() == 3 and rows.shape[2] == self.row_len
+        B, cap = int(rows.shape[0]), int(rows.shape[1])
+        assert count.is_cuda and count.dtype == torch.int32 and count.dim() == 1 and count.shape[0] == B
+        gmax = int(np.shape(gt_boxes)[1]) if not isinstance(gt_boxes, torch.Tensor) else int(gt_boxes.shape[1])
+        if gmax == 0:                         # a batch without any box: one padding slot, counts are 0
+            gt_boxes, gt_labels, gmax = np.zeros((B, 1, 4), np.float32), np.zeros((B, 1), np.int32), 1
+        gb = self._gt(gt_boxes, torch.float32, (gmax, 4))
+        gl = self._gt(gt_labels, torch.int32, (gmax,))
+        gc = self._gt(gt_counts, torch.int32, ())
+        assert gb.shape[0] == B and gl.shape[0] == B and gc.shape[0] == B
+        p = lambda t: ctypes.c_void_p(t.data_ptr())
+        self._check(lib.byolo_eval_add(self._h, p(rows), B, cap, p(count), int(count.stride(0)), p(gb), p(gl), p(gc), gmax, self._stream()))
+        self.sorted = None
+
+    # ---- the dataset-level reduction ------------------------------------------------------------------------------------
+    def finish(self):
+        """The metrics of everything added since reset() (waits for the stream).  Raises ByoloError(ERR_NOMEM) when detections
+        were dropped for lack of capacity; `records()` then still returns the table's records."""
+        import torch
+        summ = _lib.EvalSummary(struct_bytes=ctypes.sizeof(_lib.EvalSummary))
+        class_gt = (ctypes.c_int64 * self.cls_cnt)()
+        rc = lib.byolo_eval_finish(self._h, ctypes.byref(summ), class_gt, self.cls_cnt, self._stream())
+        self.n_records, self.n_images = int(summ.n_records), int(summ.n_images)
+        self._check(rc)
+        n, C = self.n_records, self.cls_cnt
+        t = self.table.view(-1)[:n * self.record_words].view(n, self.record_words)
+        tf = t.view(torch.float32)
+        key = (t[:, 0].to(torch.int64) << 32) | t[:, 1].to(torch.int64)
+        order = torch.sort(key, stable=True)[1]
+        order = order[torch.sort(tf[:, 3][order], descending=True, stable=True)[1]]
+        order = order[torch.sort(t[:, 2][order], stable=True)[1]]
+        ts = t[order]
+        cls_s, tp_s = ts[:, 2].to(torch.int64), ts[:, 4].to(torch.int64)
+        start = torch.searchsorted(cls_s, torch.arange(C + 1, device=self.device, dtype=torch.int64))
+        ctp = torch.cumsum(tp_s, 0)
+        cfp = torch.cumsum(1 - tp_s, 0)
+        zero = torch.zeros(1, dtype=torch.int64, device=self.device)
+        ctp0, cfp0 = torch.cat([zero, ctp]), torch.cat([zero, cfp])
+        seg = torch.repeat_interleave(torch.arange(C, device=self.device), start[1:] - start[:-1])
+        cum_tp = ctp - ctp0[start[:-1]][seg]
+        cum_fp = cfp - cfp0[start[:-1]][seg]
+        # uncertainty columns: finite / non-finite counts and the float64 sum of the finite ones, over TPs and over FPs
+        U = len(self.unc_cols)
+        unc = tf[order][:, _lib.EVAL_RECORD_HEAD:].to(torch.float64)
+        fin = torch.isfinite(unc)
+        is_tp = (tp_s == 1)[:, None]
+        ustat = torch.stack([(fin & is_tp).sum(0), (~fin & is_tp).sum(0), (fin & ~is_tp).sum(0), (~fin & ~is_tp).sum(0)]).to(torch.float64)
+        usum = torch.stack([torch.where(fin & is_tp, unc, 0.0).sum(0), torch.where(fin & ~is_tp, unc, 0.0).sum(0)])
+        host = torch.cat([start.to(torch.float64), ustat.reshape(-1), usum.reshape(-1)]).cpu().numpy()      # the host wait
+        ints = torch.stack([cum_tp, cum_fp]).cpu().numpy()
+        table = ts.cpu().numpy()
+        start_h = host[:C + 1].astype(np.int64)
+        ustat_h = host[C + 1:C + 1 + 4 * U].reshape(4, U).astype(np.int64)
+        usum_h = host[C + 1 + 4 * U:].reshape(2, U)
+        recs = np.ascontiguousarray(table).view(self.dtype).reshape(-1)
+        self.sorted = {'records': recs, 'cum_tp': ints[0], 'cum_fp': ints[1], 'class_start': start_h}
+        classes = []
+        for c in range(C):
+            a, b = int(start_h[c]), int(start_h[c + 1])
+            n_gt = int(class_gt[c])
+            ap, lamr = ap_lamr(ints[0, a:b], ints[1, a:b], n_gt, self.n_images)
+            cal = calibration(recs['score'][a:b], recs['tp'][a:b])
+            classes.append({'class': c, 'n_gt': n_gt, 'n_det': b - a, 'n_tp': int(ints[0, b - 1]) if b > a else 0, 'ap': ap, 'lamr': lamr,
+                            'ece': cal.pop('ece'), 'calibration': cal})
+        uncertainty = {}
+        for u, name in enumerate(self.unc_names):
+            uncertainty[name] = {
+                'column': self.unc_cols[u],
+                'tp': {'finite': int(ustat_h[0, u]), 'nonfinite': int(ustat_h[1, u]),
+                       'mean': float(usum_h[0, u] / ustat_h[0, u]) if ustat_h[0, u] else float('nan')},
+                'fp': {'finite': int(ustat_h[2, u]), 'nonfinite': int(ustat_h[3, u]),
+                       'mean': float(usum_h[1, u] / ustat_h[2, u]) if ustat_h[2, u] else float('nan')}}
+        return {'n_images': self.n_images, 'n_detections': n, 'iou_thresh': self.iou_thresh, 'min_score': self.min_score,
+                'classes': classes, 'uncertainty': uncertainty}
+
+    def records(self, sorted=False):
+        """The record table as a numpy structured array (`record_dtype`): in the order the kernel wrote it, or
+        (sorted=True, after finish()) a dict with the table in evaluation order, the cumulative TP / FP integers and the class
+        boundaries."""
+        if sorted:
+            if self.sorted is None:
+                raise RuntimeError('records(sorted=True) needs finish() first')
+            return self.sorted
+        summ = _lib.EvalSummary(struct_bytes=ctypes.sizeof(_lib.EvalSummary))
+        class_gt = (ctypes.c_int64 * self.cls_cnt)()
+        lib.byolo_eval_finish(self._h, ctypes.byref(summ), class_gt, self.cls_cnt, self._stream())   # overflow: the table is still valid
+        n = int(summ.n_records)
+        out = np.zeros(n, dtype=self.dtype)
+        if n:
+            self._check(lib.byolo_eval_records(self._h, out.ctypes.data_as(ctypes.c_void_p), 0, n, self._stream()))
+        return out
+
+    def class_gt(self):
+        """Eligible ground-truth boxes per class and the image count so far (waits for the stream)."""
+        summ = _lib.EvalSummary(struct_bytes=ctypes.sizeof(_lib.EvalSummary))
+        class_gt = (ctypes.c_int64 * self.cls_cnt)()
+        lib.byolo_eval_finish(self._h, ctypes.byref(summ), class_gt, self.cls_cnt, self._stream())
+        return [int(v) for v in class_gt], int(summ.n_images)

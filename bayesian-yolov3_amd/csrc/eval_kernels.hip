@@ -1,0 +1,328 @@
+// eval_kernels.hip -- scoring a checkpoint on labelled frames (include/byolo.h byolo_eval_*): the kept rows of a batch
+// (byolo_sort_nms) are matched against the frames' ground truth on the forward's stream, one launch per batch, and appended
+// as records to a device-resident table.  No allocation, no host wait: the running record offset, the per-class ground-truth
+// counters and the image counter live in a small device state that only byolo_eval_finish reads back.
+//
+// Matching is the Dollar / ECP / COCO rule: per image, detections in descending score (ties: lower row), each takes the
+// not-yet-matched ground-truth box OF ITS CLASS with the largest IoU (ties: lower box index); a true positive iff that IoU
+// >= iou_thresh, and only then is the box marked.  IoU is nms_box.h's: the float32 operations of the NMS, in the same order.
+//
+// eval_match_kernel: one wave64 per image.
+//   1  the image's ground truth -> LDS as NBox + label (label outside [0, C) = not eligible), class counters += eligible
+//   2  rows -> (score, row, class) keys of the surviving rows in LDS (ballot compaction); class = first index of the largest
+//      class score, score = obj * cls[class] (one float32 multiply), dropped when NaN or below min_score
+//   3  where the image's records start: the device's running offset + the survivors of the images before it in the batch,
+//      which every wave counts for itself (a few thousand rows; cheaper than a second launch or a wait between workgroups)
+//   4  bitonic sort of the keys (LDS)
+//   5  64 detections per round, one per lane (box, class, uncertainty columns in registers); the round walks them in order:
+//      the detection is broadcast, every lane scores the ground-truth boxes lane, lane + 64, ... against it, a cross-lane
+//      arg-max picks the box; the matched set is one bit per pass in a per-lane word
+//   6  every lane writes its detection's record
+// Float arithmetic here is restated operation by operation (tests/_eval_ref.py): built with -ffp-contract=off.
+#include <hip/hip_runtime.h>
+
+#include <cstdarg>
+#include <cstdio>
+#include <new>
+#include <string>
+
+#include "../../include/byolo.h"
+#include "nms_box.h"
+
+namespace byk {
+
+static constexpr int EV_MAX_DET = 4096;                      // rows per image (cap): the keys of one image sort in LDS
+static constexpr int EV_MAX_GT = BYOLO_EVAL_MAX_GT;          // ground-truth boxes per image staged in LDS
+static constexpr int EV_HEAD = BYOLO_EVAL_RECORD_HEAD;       // record words before the uncertainty columns
+static constexpr int EV_MAX_UNC = BYOLO_EVAL_MAX_UNC;
+// device state (int32 words): the running record offset twice (a launch reads one and its last image writes the other: the
+// images of a launch run concurrently), the sticky overflow word, the image counter, then one counter per class
+enum { ST_TOTAL0 = 0, ST_TOTAL1 = 1, ST_OVERFLOW = 2, ST_IMAGES = 3, ST_CLASS0 = 8 };
+
+struct EvalArgs {
+    const float* rows; const int32_t* count; int64_t count_stride;
+    const float* gt_boxes; const int32_t* gt_labels; const int32_t* gt_counts;
+    int32_t* table; int32_t* state; int64_t capacity;
+    int32_t B, cap, D, obj_idx, cls_start, C, gmax, n_unc, parity, img_base;
+    float iou_thresh, min_score;
+    int32_t unc[EV_MAX_UNC];
+};
+
+struct EvalLds {
+    unsigned long long key[EV_MAX_DET];
+    float y0[EV_MAX_GT], x0[EV_MAX_GT], y1[EV_MAX_GT], x1[EV_MAX_GT], ar[EV_MAX_GT];
+    int label[EV_MAX_GT];
+};
+
+// class (first index of the maximum, as np.argmax: a NaN class score wins and makes the score NaN) and score of a row;
+// false: the row is dropped
+__device__ __forceinline__ bool ev_score(const float* r, const EvalArgs& a, float& score, int& cls) {
+    float best = r[a.cls_start];
+    bool nan = best != best;
+    int bi = 0;
+    for (int c = 1; c < a.C; ++c) {
+        const float v = r[a.cls_start + c];
+        nan |= v != v;
+        if (v > best) { best = v; bi = c; }
+    }
+    score = __fmul_rn(r[a.obj_idx], best);
+    cls = bi;
+    return !nan && score >= a.min_score;                     // a NaN score fails the comparison
+}
+
+__device__ __forceinline__ int ev_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+__device__ __forceinline__ void ev_ce(unsigned long long& x, unsigned long long& y, bool up) {
+    if ((x > y) == up) { const unsigned long long t = x; x = y; y = t; }
+}
+
+__global__ __launch_bounds__(64) void eval_match_kernel(const EvalArgs a) {
+    __shared__ EvalLds L;
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const unsigned long long lt_mask = (1ull << lane) - 1ull;
+
+    // 1 -- ground truth
+    const int G = ev_clampi(a.gt_counts[b], 0, a.gmax);
+    for (int g = lane; g < G; g += 64) {
+        const float* q = a.gt_boxes + ((size_t)b * a.gmax + g) * 4;
+        const NBox o = make_box(q[0], q[1], q[2], q[3]);
+        int lab = a.gt_labels[(size_t)b * a.gmax + g];
+        if (lab < 0 || lab >= a.C) lab = -1;
+        L.y0[g] = o.y0; L.x0[g] = o.x0; L.y1[g] = o.y1; L.x1[g] = o.x1; L.ar[g] = o.area; L.label[g] = lab;
+        if (lab >= 0) atomicAdd(&a.state[ST_CLASS0 + lab], 1);
+    }
+    if (lane == 0) atomicAdd(&a.state[ST_IMAGES], 1);
+
+    // 2 -- keys of the surviving rows
+    const int n = ev_clampi(a.count[(size_t)b * a.count_stride], 0, a.cap);
+    const float* rows = a.rows + (size_t)b * a.cap * a.D;
+    int ns = 0;
+    for (int i0 = 0; i0 < n; i0 += 64) {
+        const int i = i0 + lane;
+        float s = 0.f; int c = 0;
+        const bool ok = i < n && ev_score(rows + (size_t)i * a.D, a, s, c);
+        const unsigned long long m = __ballot(ok);
+        if (ok) {
+            if (s == 0.f) s = 0.f;                           // -0 orders as +0
+            unsigned int u = __float_as_uint(s);
+            u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // ascending in u = ascending in s
+            L.key[ns + __popcll(m & lt_mask)] = ((unsigned long long)(~u) << 32) | ((unsigned int)i << 8) | (unsigned int)c;
+        }
+        ns += __popcll(m);
+    }
+
+    // 3 -- survivors of the images before this one
+    int before = 0;
+    for (int pb = 0; pb < b; ++pb) {
+        const int pn = ev_clampi(a.count[(size_t)pb * a.count_stride], 0, a.cap);
+        const float* pr = a.rows + (size_t)pb * a.cap * a.D;
+        for (int i0 = 0; i0 < pn; i0 += 64) {
+            const int i = i0 + lane;
+            float s; int c;
+            before += __popcll(__ballot(i < pn && ev_score(pr + (size_t)i * a.D, a, s, c)));
+        }
+    }
+    const long long base = (long long)a.state[ST_TOTAL0 + a.parity] + before;
+    if (b == a.B - 1 && lane == 0) {
+        const long long t = base + ns;
+        a.state[ST_TOTAL0 + (a.parity ^ 1)] = t > 0x7fffffffll ? 0x7fffffff : (int)t;
+    }
+
+    // 4 -- sort: descending score, then ascending row
+    int P2 = 64;
+    while (P2 < ns) P2 <<= 1;
+    for (int i = ns + lane; i < P2; i += 64) L.key[i] = ~0ull;
+    __syncthreads();
+    for (int k = 2; k <= P2; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = lane; t < P2 / 2; t += 64) {
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+                ev_ce(L.key[i], L.key[i + j], (i & k) == 0);
+            }
+            __syncthreads();
+        }
+
+    // 5, 6 -- match and write
+    const int passes = (G + 63) >> 6;                        // <= EV_MAX_GT / 64 = 16 bits of `matched`
+    unsigned int matched = 0;                                // bit p: ground-truth box p * 64 + lane is taken
+    for (int d0 = 0; d0 < ns; d0 += 64) {
+        const int d = d0 + lane;
+        const bool have = d < ns;
+        const unsigned int lo = have ? (unsigned int)L.key[d] : 0u;
+        const int my_row = (int)(lo >> 8), my_cls = (int)(lo & 255u);
+        const float* r = rows + (size_t)my_row * a.D;
+        NBox me = make_box(0.f, 0.f, 0.f, 0.f);
+        if (have) me = make_box(r[0], r[1], r[2], r[3]);
+        int my_tp = 0, my_gt = -1;
+        float my_iou = 0.f;
+        const int nd = min(64, ns - d0);
+        for (int j = 0; j < nd; ++j) {
+            NBox o;
+            o.y0 = __shfl(me.y0, j); o.x0 = __shfl(me.x0, j); o.y1 = __shfl(me.y1, j); o.x1 = __shfl(me.x1, j);
+            o.area = __shfl(me.area, j);
+            const int oc = __shfl(my_cls, j);
+            float bi = -1.f;                                 // best of this lane's boxes: strictly larger wins, so the lower pass
+            int bg = 0x7fffffff;
+            for (int p = 0; p < passes; ++p) {
+                const int g = (p << 6) + lane;
+                if (g < G && L.label[g] == oc && !((matched >> p) & 1u)) {
+                    NBox q; q.y0 = L.y0[g]; q.x0 = L.x0[g]; q.y1 = L.y1[g]; q.x1 = L.x1[g]; q.area = L.ar[g];
+                    float v = iou_value(o, q);
+                    if (!(v >= 0.f)) v = 0.f;                // non-finite coordinates: no overlap
+                    if (v > bi) { bi = v; bg = g; }
+                }
+            }
+#pragma unroll
+            for (int sft = 1; sft < 64; sft <<= 1) {         // arg-max over the lanes: larger IoU, then lower index
+                const float vi = __shfl_xor(bi, sft);
+                const int vg = __shfl_xor(bg, sft);
+                if (vi > bi || (vi == bi && vg < bg)) { bi = vi; bg = vg; }
+            }
+            const bool any = bg != 0x7fffffff;
+            const bool tp = any && bi >= a.iou_thresh;
+            if (tp && (bg & 63) == lane) matched |= 1u << (bg >> 6);
+            if (lane == j) { my_tp = tp ? 1 : 0; my_gt = tp ? bg : -1; my_iou = any ? bi : 0.f; }
+        }
+        const long long pos = base + d;
+        if (have) {
+            if (pos < a.capacity) {
+                int32_t* w = a.table + (size_t)pos * (EV_HEAD + a.n_unc);
+                w[0] = a.img_base + b; w[1] = my_row; w[2] = my_cls;
+                w[3] = __float_as_int(__fmul_rn(r[a.obj_idx], r[a.cls_start + my_cls]));
+                w[4] = my_tp; w[5] = my_gt; w[6] = __float_as_int(my_iou);
+#pragma unroll
+                for (int u = 0; u < EV_MAX_UNC; ++u)
+                    if (u < a.n_unc) w[EV_HEAD + u] = __float_as_int(r[a.unc[u]]);
+            } else {
+                a.state[ST_OVERFLOW] = 1;                    // sticky: nothing clears it but byolo_eval_reset
+            }
+        }
+    }
+}
+
+}  // namespace byk
+
+// ---- C-ABI --------------------------------------------------------------------------------------------------------------
+struct byolo_eval {
+    byolo_eval_cfg cfg;
+    int32_t* d_table = nullptr;
+    int32_t* d_state = nullptr;
+    int64_t capacity = 0;
+    int32_t launches = 0;
+    int64_t images = 0;
+    std::string err;
+};
+
+static thread_local std::string g_eval_err;
+
+static int32_t efail(byolo_eval_t* ev, int32_t code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
+    if (ev) ev->err = buf; else g_eval_err = buf;
+    return code;
+}
+#define EVHIP(ev, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) \
+    return efail(ev, BYOLO_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); } while (0)
+
+static int state_words(int C) { return byk::ST_CLASS0 + C; }
+static int record_words(const byolo_eval_cfg& c) { return byk::EV_HEAD + c.n_unc; }
+
+extern "C" const char* byolo_eval_last_error(const byolo_eval_t* ev) { return ev ? ev->err.c_str() : g_eval_err.c_str(); }
+
+extern "C" size_t byolo_eval_state_bytes(int32_t cls_cnt) {
+    return cls_cnt < 1 ? 0 : sizeof(int32_t) * (size_t)state_words(cls_cnt);
+}
+
+extern "C" int32_t byolo_eval_create(const byolo_eval_cfg* cfg, void* d_table, int64_t capacity, void* d_state, byolo_eval_t** out) {
+    if (!cfg || !out || !d_table || !d_state) return efail(nullptr, BYOLO_ERR_ARG, "byolo_eval_create: null argument");
+    if (cfg->struct_bytes != (int32_t)sizeof(byolo_eval_cfg))
+        return efail(nullptr, BYOLO_ERR_ARG, "byolo_eval_create: struct_bytes %d, this library's byolo_eval_cfg has %d", cfg->struct_bytes, (int)sizeof(byolo_eval_cfg));
+    if (cfg->cls_cnt < 1 || cfg->cls_cnt > BYOLO_NMS_MAX_CLASSES) return efail(nullptr, BYOLO_ERR_ARG, "byolo_eval_create: cls_cnt outside 1 .. %d", BYOLO_NMS_MAX_CLASSES);
+    if (cfg->row_len < 5 || cfg->obj_idx < 4 || cfg->obj_idx >= cfg->row_len || cfg->cls_start_idx < 4 ||
+        (int64_t)cfg->cls_start_idx + cfg->cls_cnt > cfg->row_len)
+        return efail(nullptr, BYOLO_ERR_ARG, "byolo_eval_create: score columns outside the row");
+    if (cfg->n_unc < 0 || cfg->n_unc > BYOLO_EVAL_MAX_UNC) return efail(nullptr, BYOLO_ERR_ARG, "byolo_eval_create: n_unc outside 0 .. %d", BYOLO_EVAL_MAX_UNC);
+    for (int u = 0; u < cfg->n_unc; ++u)
+        if (cfg->unc_cols[u] < 0 || cfg->unc_cols[u] >= cfg->row_len) return efail(nullptr, BYOLO_ERR_ARG, "byolo_eval_create: uncertainty column %d outside the row", cfg->unc_cols[u]);
+    if (!(cfg->iou_thresh >= 0.f && cfg->iou_thresh <= 1.f)) return efail(nullptr, BYOLO_ERR_ARG, "byolo_eval_create: iou_thresh outside [0, 1]");
+    if (cfg->min_score != cfg->min_score) return efail(nullptr, BYOLO_ERR_ARG, "byolo_eval_create: min_score is NaN");
+    if (capacity < 1 || capacity > 0x7fffffffll) return efail(nullptr, BYOLO_ERR_ARG, "byolo_eval_create: capacity outside 1 .. 2^31 - 1 records");
+    if ((reinterpret_cast<uintptr_t>(d_table) | reinterpret_cast<uintptr_t>(d_state)) & 3) return efail(nullptr, BYOLO_ERR_ARG, "byolo_eval_create: d_table / d_state must be 4-byte aligned");
+    byolo_eval_t* ev = new (std::nothrow) byolo_eval();
+    if (!ev) return efail(nullptr, BYOLO_ERR_NOMEM, "byolo_eval_create: out of host memory");
+    ev->cfg = *cfg;
+    ev->d_table = static_cast<int32_t*>(d_table);
+    ev->d_state = static_cast<int32_t*>(d_state);
+    ev->capacity = capacity;
+    *out = ev;
+    return BYOLO_OK;
+}
+
+extern "C" int32_t byolo_eval_destroy(byolo_eval_t* ev) { delete ev; return BYOLO_OK; }
+
+extern "C" int32_t byolo_eval_reset(byolo_eval_t* ev, void* stream) {
+    if (!ev) return efail(nullptr, BYOLO_ERR_ARG, "byolo_eval_reset: null handle");
+    EVHIP(ev, hipMemsetAsync(ev->d_state, 0, sizeof(int32_t) * (size_t)state_words(ev->cfg.cls_cnt), static_cast<hipStream_t>(stream)));
+    ev->launches = 0;
+    ev->images = 0;
+    return BYOLO_OK;
+}
+
+extern "C" int32_t byolo_eval_add(byolo_eval_t* ev, const float* d_rows, int32_t B, int32_t cap, const int32_t* d_count, int64_t count_stride,
+                                  const float* d_gt_boxes, const int32_t* d_gt_labels, const int32_t* d_gt_counts, int32_t gmax, void* stream) {
+    if (!ev) return efail(nullptr, BYOLO_ERR_ARG, "byolo_eval_add: null handle");
+    if (!d_rows || !d_count || !d_gt_boxes || !d_gt_labels || !d_gt_counts) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_add: null argument");
+    if (B < 1 || B > 65535) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_add: B outside 1 .. 65535");
+    if (cap < 1 || cap > byk::EV_MAX_DET) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_add: cap outside 1 .. %d rows per image", byk::EV_MAX_DET);
+    if (gmax < 1 || gmax > BYOLO_EVAL_MAX_GT) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_add: gmax outside 1 .. %d boxes per image", BYOLO_EVAL_MAX_GT);
+    if (count_stride < 1) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_add: count_stride below 1");
+    if (ev->images + B > 0x7fffffffll) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_add: more than 2^31 - 1 images");
+    byk::EvalArgs a;
+    a.rows = d_rows; a.count = d_count; a.count_stride = count_stride;
+    a.gt_boxes = d_gt_boxes; a.gt_labels = d_gt_labels; a.gt_counts = d_gt_counts;
+    a.table = ev->d_table; a.state = ev->d_state; a.capacity = ev->capacity;
+    a.B = B; a.cap = cap; a.D = ev->cfg.row_len; a.obj_idx = ev->cfg.obj_idx; a.cls_start = ev->cfg.cls_start_idx; a.C = ev->cfg.cls_cnt;
+    a.gmax = gmax; a.n_unc = ev->cfg.n_unc; a.parity = ev->launches & 1; a.img_base = (int32_t)ev->images;
+    a.iou_thresh = ev->cfg.iou_thresh; a.min_score = ev->cfg.min_score;
+    for (int u = 0; u < BYOLO_EVAL_MAX_UNC; ++u) a.unc[u] = u < ev->cfg.n_unc ? ev->cfg.unc_cols[u] : 0;
+    hipLaunchKernelGGL(byk::eval_match_kernel, dim3(B), dim3(64), 0, static_cast<hipStream_t>(stream), a);
+    EVHIP(ev, hipGetLastError());
+    ev->launches += 1;
+    ev->images += B;
+    return BYOLO_OK;
+}
+
+extern "C" int32_t byolo_eval_finish(byolo_eval_t* ev, byolo_eval_summary* out, int64_t* h_class_gt, int32_t n_classes, void* stream) {
+    if (!ev) return efail(nullptr, BYOLO_ERR_ARG, "byolo_eval_finish: null handle");
+    if (!out || !h_class_gt) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_finish: null argument");
+    if (out->struct_bytes != (int32_t)sizeof(byolo_eval_summary))
+        return efail(ev, BYOLO_ERR_ARG, "byolo_eval_finish: struct_bytes %d, this library's byolo_eval_summary has %d", out->struct_bytes, (int)sizeof(byolo_eval_summary));
+    if (n_classes != ev->cfg.cls_cnt) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_finish: h_class_gt has %d entries, the evaluator %d classes", n_classes, ev->cfg.cls_cnt);
+    int32_t st[byk::ST_CLASS0 + BYOLO_NMS_MAX_CLASSES];
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    EVHIP(ev, hipMemcpyAsync(st, ev->d_state, sizeof(int32_t) * (size_t)state_words(n_classes), hipMemcpyDeviceToHost, s));
+    EVHIP(ev, hipStreamSynchronize(s));
+    const int64_t seen = st[byk::ST_TOTAL0 + (ev->launches & 1)];
+    out->n_seen = seen;
+    out->n_records = seen < ev->capacity ? seen : ev->capacity;
+    out->n_images = st[byk::ST_IMAGES];
+    out->overflow = st[byk::ST_OVERFLOW];
+    out->record_words = record_words(ev->cfg);
+    for (int c = 0; c < n_classes; ++c) h_class_gt[c] = st[byk::ST_CLASS0 + c];
+    if (out->overflow || seen > ev->capacity)
+        return efail(ev, BYOLO_ERR_NOMEM, "byolo_eval_finish: %lld detections, the record table holds %lld: the rest were dropped",
+                     (long long)seen, (long long)ev->capacity);
+    return BYOLO_OK;
+}
+
+extern "C" int32_t byolo_eval_records(byolo_eval_t* ev, int32_t* h_dst, int64_t first, int64_t n_records, void* stream) {
+    if (!ev) return efail(nullptr, BYOLO_ERR_ARG, "byolo_eval_records: null handle");
+    if (first < 0 || n_records < 0 || first + n_records > ev->capacity) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_records: records outside the table");
+    if (n_records == 0) return BYOLO_OK;
+    if (!h_dst) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_records: null argument");
+    const size_t rw = (size_t)record_words(ev->cfg);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    EVHIP(ev, hipMemcpyAsync(h_dst, ev->d_table + (size_t)first * rw, sizeof(int32_t) * rw * (size_t)n_records, hipMemcpyDeviceToHost, s));
+    EVHIP(ev, hipStreamSynchronize(s));
+    return BYOLO_OK;
+}

@@ -12,6 +12,7 @@
 #include <algorithm>
 #include <float.h>
 #include "byolo_kernels.h"
+#include "nms_box.h"
 
 namespace byk {
 
@@ -406,27 +407,6 @@ __device__ __forceinline__ void ce(unsigned long long& a, unsigned long long& b,
 // ------------------------------------------------------------------------------------------------
 static constexpr int NMS_THREADS = 1024;
 static constexpr int NMS_MAXK = 2048;                        // max_out limit per class
-
-struct NBox { float y0, x0, y1, x1, area; };
-
-__device__ __forceinline__ float smin_(float a, float b) { return (b < a) ? b : a; }
-__device__ __forceinline__ float smax_(float a, float b) { return (a < b) ? b : a; }
-
-__device__ __forceinline__ NBox make_box(float b0, float b1, float b2, float b3) {
-    NBox r;
-    r.y0 = smin_(b0, b2); r.x0 = smin_(b1, b3);
-    r.y1 = smax_(b0, b2); r.x1 = smax_(b1, b3);
-    r.area = __fmul_rn(__fsub_rn(r.y1, r.y0), __fsub_rn(r.x1, r.x0));
-    return r;
-}
-__device__ __forceinline__ bool iou_gt(const NBox& i, const NBox& j, float thr) {
-    if (i.area <= 0.f || j.area <= 0.f) return false;        // IoU = 0
-    const float iy0 = smax_(i.y0, j.y0), ix0 = smax_(i.x0, j.x0);
-    const float iy1 = smin_(i.y1, j.y1), ix1 = smin_(i.x1, j.x1);
-    const float inter = __fmul_rn(smax_(__fsub_rn(iy1, iy0), 0.f), smax_(__fsub_rn(ix1, ix0), 0.f));
-    const float iou = __fdiv_rn(inter, __fsub_rn(__fadd_rn(i.area, j.area), inter));
-    return iou > thr;
-}
 
 // LDS of one walk: the kept boxes so far, the staging of the wave whose turn it is, the kept count.
 struct WalkLds {

@@ -1,0 +1,189 @@
+"""
+Evaluation script: scores a checkpoint of any of the three models on LABELLED TFRecord shards (the records
+create_tf_records_*.py writes for training) -- per class AP, log-average miss rate and score calibration, and what the
+uncertainty columns say about true and false positives.  The reference has no counterpart: its inference scripts write
+ECP-JSON for an external toolkit.
+
+    python evaluate.py --model standard|aleatoric|bayesian        (edit the config in `main()`)
+
+Same config keys as `inference_*.py` (`data.file_pattern` names the labelled shards; `crop: True` evaluates the centre crop of
+`crop_img_size`, the reference's ValDataset), plus the optional `iou_thresh` (0.5), `min_score` (0.0), `eval_capacity`
+(records the device table holds, default 2^20) and `eval_batches` (stop after that many batches).  `weights='synthetic'`,
+`seed` and `engine_options` as in the inference scripts.
+
+`Model.run` -> `Evaluator.add` per batch (byolo/evaluate.py: one matching kernel per batch on the forward's stream); batches
+run one after the other (`Model.run` re-runs a batch that leaves the split-f16 range in fp32 by itself).  One process, one
+GPU: multi-GPU evaluation is out of scope.  Writes `<out_path>_<step>/metrics.json`: the dict of `Evaluator.finish`, the
+config and the image count.  INTEGRATION.md ("Evaluation") defines every figure.
+"""
+import argparse
+import json
+import logging
+import os
+import time
+
+import numpy as np
+
+MODELS = {'standard': 'yolov3', 'aleatoric': 'yolov3_aleatoric', 'bayesian': 'bayesian_yolov3_aleatoric'}
+REQUIRED = ('full_img_size', 'cls_cnt', 'batch_size', 'crop', 'priors', 'implicit_background_class', 'data', 'out_path')
+
+
+def check_config(config, model='bayesian'):
+    """A copy of `config` with the evaluation defaults filled in; raises ValueError on what cannot be evaluated."""
+    if model not in MODELS:
+        raise ValueError('model must be one of {}, not {!r}'.format(sorted(MODELS), model))
+    missing = [k for k in REQUIRED if k not in config]
+    if missing:
+        raise ValueError('config lacks {}'.format(missing))
+    cfg = dict(config)
+    if not isinstance(cfg['data'], dict) or not cfg['data'].get('file_pattern'):
+        raise ValueError("config['data']['file_pattern'] must name the labelled shards")
+    if cfg['crop'] and 'crop_img_size' not in cfg:
+        raise ValueError("crop: True needs crop_img_size")
+    if cfg.get('weights') != 'synthetic':
+        lacking = [k for k in ('checkpoint_path', 'run_id', 'step') if k not in cfg]
+        if lacking:
+            raise ValueError("config lacks {} (or set weights='synthetic')".format(lacking))
+    if int(cfg['batch_size']) < 1:
+        raise ValueError('batch_size must be at least 1')
+    cfg.setdefault('iou_thresh', 0.5)
+    cfg.setdefault('min_score', 0.0)
+    cfg.setdefault('eval_capacity', 1 << 20)
+    cfg.setdefault('eval_batches', None)
+    cfg.setdefault('seed', 0)
+    cfg.setdefault('cpu_thread_cnt', 1)
+    cfg.setdefault('T', 1)
+    if not 0.0 <= float(cfg['iou_thresh']) <= 1.0:
+        raise ValueError('iou_thresh outside [0, 1]')
+    cfg['training'] = False
+    cfg['aleatoric_loss'] = False
+    cfg['inference_mode'] = True
+    cfg['model'] = model
+    return cfg
+
+
+def build_model(cfg):
+    """The inference model of cfg['model'] at the evaluation size, with the checkpoint's (or synthetic) weights."""
+    import torch
+    from byolo import inference as _inf
+    from lib_yolo import model as _model, yolov3
+    variant = MODELS[cfg['model']]
+    factory = getattr(yolov3, variant)(cfg)
+    h, w = (cfg['crop_img_size'] if cfg['crop'] else cfg['full_img_size'])[:2]
+    m = factory.init_model(inputs=_model.Placeholder((cfg['batch_size'], h, w, 3)), training=False).get_model()
+    if cfg.get('weights') == 'synthetic':
+        from byolo import synth
+        eng = m.engine
+        eng.set_params(synth.base_params(eng.param_shapes(), variant, m.cls_cnt, seed=7))
+        eng.finalize()
+        eng.calibrate_bn(torch.from_numpy(synth.synthetic_images(2, h, w, 3, seed=999)).to(eng.torch_device))
+        checkpoint = 'synthetic-0'
+    else:
+        checkpoint = _inf.find_checkpoint(cfg)
+        _inf.restore(m, checkpoint)
+    return m, checkpoint
+
+
+def score(model, feed, evaluator, seed=0, max_batches=None, points=None):
+    """Model.run -> Evaluator.add over the batches of `feed` (the 'eval' split of lib_yolo.dataset_utils._Feed); returns the
+    number of images.  points: a list that receives (time, images so far) after every batch."""
+    images = 0
+    for step, b in enumerate(feed):
+        if max_batches is not None and step >= max_batches:
+            break
+        res = model.run(b['img'], seed=seed + step, want_boxes=False)
+        evaluator.add(res['rows'], res['count'][:, 0], b['boxes'], b['labels'], b['counts'])
+        images += int(b['img'].shape[0])
+        if points is not None:
+            points.append((time.perf_counter(), images))
+    return images
+
+
+def steady_rate(points):
+    """img/s after the pipeline's fill, as byolo.inference.InferenceLoop counts it: the first quarter of the batches (at least
+    two) is left out.  None when there are too few batches."""
+    k = min(len(points) - 1, max(2, len(points) // 4))
+    if k >= 1 and len(points) > k and points[-1][0] > points[k][0]:
+        return (points[-1][1] - points[k][1]) / (points[-1][0] - points[k][0])
+    return None
+
+
+def class_line(c):
+    return 'class {:3d}: n_gt {:6d}, n_det {:7d}, n_tp {:6d}, AP {:.4f}, LAMR {:.4f}, ECE {:.4f}'.format(
+        c['class'], c['n_gt'], c['n_det'], c['n_tp'], c['ap'], c['lamr'], c['ece'])
+
+
+def evaluate(config, model='bayesian'):
+    """Scores the checkpoint and writes <out_path>_<step>/metrics.json; returns its content."""
+    from byolo import inference as _inf
+    from byolo.evaluate import Evaluator
+    from lib_yolo import dataset_utils
+    cfg = check_config(config, model)
+    logging.info(json.dumps(cfg, indent=4, default=lambda x: str(x)))
+    logging.info('----- START -----')
+    start = time.time()
+    m, checkpoint = build_model(cfg)
+    out_path = '{}_{}'.format(cfg['out_path'], _inf.step_of(checkpoint))
+    os.makedirs(out_path)                                 # like the inference scripts: refuses to overwrite an existing run
+    ev = Evaluator(m, iou_thresh=cfg['iou_thresh'], min_score=cfg['min_score'], capacity=cfg['eval_capacity'])
+    feed = dataset_utils._Feed(cfg, 'data', 'eval', device=m.engine.torch_device)
+    try:
+        t0 = time.time()
+        points = []
+        images = score(m, feed, ev, seed=int(cfg['seed']), max_batches=cfg['eval_batches'], points=points)
+        metrics = ev.finish()
+        loop_seconds = time.time() - t0
+    finally:
+        feed.close()
+        ev.close()
+    for c in metrics['classes']:
+        logging.info(class_line(c))
+    for name, u in metrics['uncertainty'].items():
+        logging.info('{:16s}: mean over TP {:.6g} ({} finite, {} not), over FP {:.6g} ({} finite, {} not)'.format(
+            name, u['tp']['mean'], u['tp']['finite'], u['tp']['nonfinite'], u['fp']['mean'], u['fp']['finite'], u['fp']['nonfinite']))
+    metrics.update(images=images, checkpoint=checkpoint, model=MODELS[cfg['model']], loop_seconds=loop_seconds,
+                   steady_img_s=steady_rate(points),
+                   config=json.loads(json.dumps(cfg, default=lambda x: str(x))))
+    with open(os.path.join(out_path, 'metrics.json'), 'w') as f:
+        json.dump(metrics, f, indent=1)
+    elapsed = int(time.time() - start)
+    logging.info('----- FINISHED in {:02d}:{:02d}:{:02d} -----'.format(elapsed // 3600, (elapsed // 60) % 60, elapsed % 60))
+    m.engine.close()
+    return metrics
+
+
+def main(argv=None):
+    from lib_yolo import yolov3
+    ap = argparse.ArgumentParser(description=__doc__.split('\n\n')[0])
+    ap.add_argument('--model', choices=sorted(MODELS), default='bayesian')
+    args = ap.parse_args(argv)
+    config = {
+        'checkpoint_path': './checkpoints',  # edit
+        'run_id': {'standard': 'yolov3', 'aleatoric': 'aleatoric', 'bayesian': 'epi_ale'}[args.model],  # edit
+        'step': 'last',  # edit: int or 'last'
+        'full_img_size': [1024, 1920, 3],  # edit if not ECP dataset
+        'cls_cnt': 2,  # edit if not ECP dataset
+        'batch_size': 8,
+        'T': 50,  # bayesian only
+        'cpu_thread_cnt': 24,
+        'crop': False,  # True: the centre crop of crop_img_size
+        'priors': yolov3.ECP_9_PRIORS,  # edit
+        'implicit_background_class': True,
+        'iou_thresh': 0.5,
+        'min_score': 0.0,
+        'data': {
+            'path': '$HOME/data/ecp/tfrecords',  # edit
+            'file_pattern': 'ecp-day-val-*-of-*',  # edit: LABELLED shards
+        }
+    }
+    config['data']['file_pattern'] = os.path.join(os.path.expandvars(config['data']['path']), config['data']['file_pattern'])
+    config['out_path'] = os.path.join('./evaluation', config['run_id'])  # edit
+    evaluate(config, args.model)
+
+
+if __name__ == '__main__':
+    np.set_printoptions(suppress=True, formatter={'float_kind': '{:5.3}'.format})
+    logging.basicConfig(level=logging.DEBUG,
+                        format='%(asctime)s, pid: %(process)d, %(levelname)-8s %(message)s',
+                        datefmt='%a, %d %b %Y %H:%M:%S')
+    main()

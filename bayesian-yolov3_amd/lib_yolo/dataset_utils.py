@@ -560,6 +560,8 @@ class RecordStream:
         return self._recs[path]
 
     def epoch(self, e):
+        if self.split == 'eval':                  # the files in sorted order, their records in file order: no shuffle
+            return ((p, k) for p in self.files for k in range(len(self.records(p))))
         files = list(shuffle_buffer(self.files, self.num_shards, self._rng(e, 1)))
 
         def interleaved():                        # interleave(TFRecordDataset, cycle_length=2, block_length=1)
@@ -580,6 +582,8 @@ class RecordStream:
         while True:
             for pos, ref in enumerate(self.epoch(e)):
                 yield e, pos, ref
+            if self.split == 'eval':              # one pass
+                return
             e += 1
 
     def payload(self, ref):
@@ -629,6 +633,7 @@ class _Feed:
         self._slot = 0
         self._side = torch.cuda.Stream(self.device)
         self._pending = None                              # (host batch, device slot, copy event)
+        self._done = False                                # split 'eval': the stream has ended
         self.host_seconds = {'augment': 0.0, 'copy': 0.0}  # host time of next(): event wait + augment launch / issuing copies
         self._returning = []
         self._ready = queue.Queue(maxsize=self.prefetch)
@@ -710,6 +715,20 @@ class _Feed:
                         pass
                 if self._stop.is_set():
                     return
+            if self.split == 'eval':                     # one pass: the last short batch is kept, then the stream ends
+                tail = []
+                while items and not tail and not self._stop.is_set():
+                    try:
+                        tail = [pool.submit(self._load, items, self._free.get(timeout=0.1), per_call)]
+                    except queue.Empty:
+                        pass
+                for item in tail + [StopIteration()]:
+                    while not self._stop.is_set():
+                        try:
+                            self._ready.put(item, timeout=0.1)
+                            break
+                        except queue.Full:
+                            pass
         except BaseException as err:                     # framing errors reach the consumer in order
             self._ready.put(err)
         finally:
@@ -721,6 +740,9 @@ class _Feed:
         try:
             item = self._ready.get(block=block)
         except queue.Empty:
+            return
+        if isinstance(item, StopIteration):              # the 'eval' split's one pass is over
+            self._done = True
             return
         if isinstance(item, BaseException):
             raise item
@@ -750,8 +772,10 @@ class _Feed:
             ev.synchronize()
             self._free.put(buf)
         self._returning = []
-        if self._pending is None:
+        if self._pending is None and not self._done:
             self._start_copy(block=True)
+        if self._pending is None:
+            raise StopIteration
         hb, slot, ev = self._pending
         self._pending = None
         t0 = time.perf_counter()
@@ -767,7 +791,8 @@ class _Feed:
         t1 = time.perf_counter()
         self._dev_free[slot] = done
         self._returning.append((hb.buf, ev))
-        self._start_copy(block=False)                    # the next batch's copy overlaps the caller's step
+        if not self._done:
+            self._start_copy(block=False)                # the next batch's copy overlaps the caller's step
         self.host_seconds['augment'] += t1 - t0
         self.host_seconds['copy'] += time.perf_counter() - t1
         plans['row0'] = 0

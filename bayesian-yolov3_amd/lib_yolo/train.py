@@ -194,23 +194,79 @@ def run(model_cls, config):
     return start(model_cls, config)
 
 
+class EvalHook:
+    """config['eval_interval'] (absent: no hook, the run is what it was): every that many steps the trained heads are handed
+    to an inference model (built once, at the evaluation size: the centre crop when config['crop'], else the full frame) and
+    config['eval_batches'] (default 4) batches of the 'val' shards are scored through the feed's 'eval' split
+    (byolo/evaluate.py).  Logs '{step} eval  >>> class c: LAMR .., AP ..; ...'.  Reads the trainer, never writes it; the
+    'eval' split draws no random number, so the training and validation streams are what they are without the hook."""
+
+    def __init__(self, model_cls, config):
+        self.model_cls = model_cls
+        # building a cropped model rescales the prior table it is given in place (lib_yolo/model.py): a table of its own
+        self.config = dict(config, priors=dict(config['priors']), training=False, aleatoric_loss=False)
+        self.config.setdefault('T', 10)
+        self.model = None
+        self.last = None
+
+    def _build(self):
+        from lib_yolo import yolov3
+        cfg = self.config
+        if self.model_cls is yolov3.bayesian_yolov3_aleatoric:
+            cfg['inference_mode'] = True
+        factory = self.model_cls(cfg)
+        h, w = (cfg['crop_img_size'] if cfg['crop'] else cfg['full_img_size'])[:2]
+        self.model = factory.init_model(inputs=_model.Placeholder((cfg['batch_size'], h, w, 3)), training=False).get_model()
+        self.model.engine.set_params(initial_params(self.model.engine.param_shapes(), cfg.get('seed', 0)))
+        factory.load_darknet53_weights(cfg['darknet53_weights'])
+
+    def __call__(self, trainer, step):
+        from byolo.evaluate import Evaluator
+        if self.model is None:
+            self._build()
+        trainer.apply_to(self.model)
+        ev = Evaluator(self.model, capacity=int(self.config.get('eval_capacity', 1 << 18)))
+        feed = dataset_utils._Feed(self.config, 'val', 'eval', device=self.model.engine.torch_device)
+        try:
+            for k, b in enumerate(feed):
+                if k >= int(self.config.get('eval_batches', 4)):
+                    break
+                res = self.model.run(b['img'], seed=int(self.config.get('seed', 0)) + k, want_boxes=False)
+                ev.add(res['rows'], res['count'][:, 0], b['boxes'], b['labels'], b['counts'])
+            self.last = ev.finish()
+        finally:
+            feed.close()
+            ev.close()
+        logging.info('{:5d} eval  >>> '.format(step) + '; '.join(
+            'class {}: LAMR {:.4f}, AP {:.4f}'.format(c['class'], c['lamr'], c['ap']) for c in self.last['classes']))
+        return self.last
+
+    def close(self):
+        if self.model is not None:
+            self.model.engine.close()
+            self.model = None
+
+
 def start(model_cls, config):
     """lib_yolo/train.py:24-47.  Returns the trainer (trainer.apply_to(model) hands the heads to an inference model)."""
     if config['crop']:
         data_augmentation.ImageCropper(config)          # the aspect-ratio assertion, before anything is built
+    hook = EvalHook(model_cls, config) if config.get('eval_interval') else None
     factory, model, trainer = build(model_cls, config)
     dataset = dataset_utils.TrainValDataset(model_blueprint=factory.blueprint, config=config)
     try:
-        train(trainer, dataset, config)
+        train(trainer, dataset, config, eval_hook=hook)
     except BaseException:
         logging.exception('ERROR')
         raise
     finally:
         dataset.close()
+        if hook is not None:
+            hook.close()
     return trainer
 
 
-def train(trainer, dataset, config):
+def train(trainer, dataset, config, eval_hook=None):
     seed = int(config.get('seed', 0))
 
     def train_loop_body():
@@ -226,6 +282,8 @@ def train(trainer, dataset, config):
             v = next(dataset.val)
             vl = trainer.losses(v['img'], v['boxes'], v['labels'], v['counts'], seed=seed + step)
             logging.info('{:5d} val   >>> '.format(step) + _losses_line(vl))
+        if eval_hook is not None and step % int(config['eval_interval']) == 0:
+            eval_hook(trainer, step)
         if step % config['checkpoint_interval'] == 0:
             saver.save(step)
         return True

@@ -563,6 +563,58 @@ BYOLO_API int32_t byolo_trainer_taps(const byolo_trainer_t* tr, int32_t* layers,
 BYOLO_API int32_t byolo_trainer_layer_output(byolo_trainer_t* tr, int32_t layer, float* d_dst, int64_t count, int64_t shape[4],
                                              void* stream);
 
+/* ---- evaluation: detections against ground truth (no counterpart in the reference, whose ECP-JSON goes to an external
+ * toolkit) ---------------------------------------------------------------------------------------------------------------
+ * An evaluator is its own handle (no byolo_t): it scores the kept rows of byolo_sort_nms / byolo_forward (d_rows, d_count) on
+ * labelled frames, one kernel launch per batch on the caller's stream, with no allocation and no host wait, and appends one
+ * record per surviving detection to a CALLER-OWNED device table.  INTEGRATION.md ("Evaluation") has the definitions in full.
+ *   class of a row   first index of the largest class score;  score = obj * cls[class], one float32 multiply; rows whose score
+ *                    is NaN or below min_score are dropped
+ *   ground truth     d_gt_boxes [B, gmax, 4] normalised (ymin, xmin, ymax, xmax), d_gt_labels [B, gmax] 0-based, d_gt_counts
+ *                    [B]; a box whose label is outside [0, cls_cnt) is neither counted nor matchable
+ *   matching         per image, rows in descending score (ties: lower row), each takes the not-yet-matched box of its class
+ *                    with the largest IoU (ties: lower box index; the NMS's float32 IoU, a non-finite one counts as 0): a
+ *                    true positive iff that IoU >= iou_thresh, and only then is the box marked
+ *   record           record_words = BYOLO_EVAL_RECORD_HEAD + n_unc 32-bit words: int32 image sequence number (0 for the first
+ *                    image after byolo_eval_reset), int32 row, int32 class, float score, int32 tp, int32 matched box or -1,
+ *                    float best IoU (0 without an eligible box), then the row's columns unc_cols[0 .. n_unc) as floats.  The
+ *                    records of an image are in matching order, images in the order they were added.
+ * d_table holds `capacity` records, d_state byolo_eval_state_bytes(cls_cnt) bytes (running offset, per-class counts of eligible
+ * boxes, image count, a sticky overflow word); both stay the caller's and must outlive the handle's use.  Records beyond the
+ * capacity are dropped -- nothing is written outside the table -- and byolo_eval_finish then returns BYOLO_ERR_NOMEM (the
+ * summary is filled all the same).  Limits: cap <= 4096 rows per image, gmax <= BYOLO_EVAL_MAX_GT.
+ * byolo_eval_reset must run once before the first byolo_eval_add.  byolo_eval_finish and byolo_eval_records wait for `stream`. */
+#define BYOLO_EVAL_MAX_GT 1024
+#define BYOLO_EVAL_MAX_UNC 16
+#define BYOLO_EVAL_RECORD_HEAD 7
+typedef struct byolo_eval byolo_eval_t;
+typedef struct byolo_eval_cfg {
+    int32_t struct_bytes;          /* sizeof(byolo_eval_cfg) of the caller's header: a mismatch is BYOLO_ERR_ARG */
+    int32_t row_len, obj_idx, cls_start_idx, cls_cnt;
+    int32_t n_unc;
+    int32_t unc_cols[BYOLO_EVAL_MAX_UNC];
+    float iou_thresh, min_score;
+} byolo_eval_cfg;
+typedef struct byolo_eval_summary {
+    int32_t struct_bytes;          /* set by the caller, as above */
+    int32_t overflow;              /* the sticky word: detections were dropped */
+    int32_t record_words;
+    int32_t reserved;
+    int64_t n_records;             /* records in the table: min(n_seen, capacity) */
+    int64_t n_seen;                /* surviving detections of every image added */
+    int64_t n_images;
+} byolo_eval_summary;
+BYOLO_API size_t byolo_eval_state_bytes(int32_t cls_cnt);
+BYOLO_API int32_t byolo_eval_create(const byolo_eval_cfg* cfg, void* d_table, int64_t capacity, void* d_state, byolo_eval_t** out);
+BYOLO_API int32_t byolo_eval_destroy(byolo_eval_t* ev);
+BYOLO_API const char* byolo_eval_last_error(const byolo_eval_t* ev);
+BYOLO_API int32_t byolo_eval_reset(byolo_eval_t* ev, void* stream);
+BYOLO_API int32_t byolo_eval_add(byolo_eval_t* ev, const float* d_rows, int32_t B, int32_t cap, const int32_t* d_count,
+                                 int64_t count_stride, const float* d_gt_boxes, const int32_t* d_gt_labels,
+                                 const int32_t* d_gt_counts, int32_t gmax, void* stream);
+BYOLO_API int32_t byolo_eval_finish(byolo_eval_t* ev, byolo_eval_summary* out, int64_t* h_class_gt, int32_t n_classes, void* stream);
+BYOLO_API int32_t byolo_eval_records(byolo_eval_t* ev, int32_t* h_dst, int64_t first, int64_t n_records, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
