@@ -52,6 +52,16 @@ class EvalCfg(ctypes.Structure):
                [("unc_cols", ctypes.c_int32 * EVAL_MAX_UNC), ("iou_thresh", ctypes.c_float), ("min_score", ctypes.c_float)]
 
 
+EVAL_LOC_WORDS, EVAL_LOC_MAX_LAYERS, EVAL_LOC_MAX_PRIORS = 6, 8, 16      # BYOLO_EVAL_LOC_*
+
+
+class EvalLocCfg(ctypes.Structure):
+    """include/byolo.h byolo_eval_loc_cfg (field for field; tests/test_eval_loc_cpu.py compares the two)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("struct_bytes", "layer_col", "prior_col", "n_layers")] + \
+               [(n, ctypes.c_int32 * EVAL_LOC_MAX_LAYERS) for n in ("lh", "lw", "n_priors")] + \
+               [(n, (ctypes.c_float * EVAL_LOC_MAX_PRIORS) * EVAL_LOC_MAX_LAYERS) for n in ("prior_w", "prior_h")]
+
+
 class EvalSummary(ctypes.Structure):
     """include/byolo.h byolo_eval_summary."""
     _fields_ = [(n, ctypes.c_int32) for n in ("struct_bytes", "overflow", "record_words", "reserved")] + \
@@ -155,6 +165,9 @@ PROTOTYPES = {
     "byolo_eval_add": (_i32, [_vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _i32, _vp]),
     "byolo_eval_finish": (_i32, [_vp, _P(EvalSummary), _P(_i64), _i32, _vp]),
     "byolo_eval_records": (_i32, [_vp, _vp, _i64, _i64, _vp]),
+    "byolo_eval_loc_bytes": (_sz, [_i64]),
+    "byolo_eval_set_loc": (_i32, [_vp, _P(EvalLocCfg), _vp]),
+    "byolo_eval_loc_records": (_i32, [_vp, _vp, _i64, _i64, _vp]),
 }
 
 

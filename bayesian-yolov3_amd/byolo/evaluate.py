@@ -5,12 +5,16 @@ Per batch, `Evaluator.add` launches ONE kernel (csrc/eval_kernels.hip) on the cu
 `Model.run` against the frames' ground truth and appends a record per detection to a device table: no allocation, no host wait.
 `Evaluator.finish` is the only host wait: it orders the table on the device (per class: descending score, then image, then
 row), accumulates true and false positives as integers there, and reduces those integers to the metrics in float64 on the
-host, every sum taken in ascending order so that the figures are reproducible to the last bit."""
+host, every sum taken in ascending order so that the figures are reproducible to the last bit.
+
+With localisation on (the two uncertainty variants), `add` launches a second kernel behind the first that takes every true
+positive and its matched box back to the raw location values at the detection's cell and prior and records the residuals;
+`finish` then says whether the predicted variances explain them (byolo/eval_loc.py)."""
 import ctypes
 
 import numpy as np
 
-from . import _lib
+from . import _lib, eval_loc
 from ._lib import ByoloError, lib
 
 FPPI_REFS = np.logspace(-2, 0, 9)          # the nine reference points of the log-average miss rate
@@ -94,14 +98,17 @@ def calibration(score, tp):
 class Evaluator:
     """Evaluator(model_or_layout): a lib_yolo Model, or a dict with row_len, obj_idx, cls_start_idx, cls_cnt and optionally
     unc_cols ({name: column}; default: the variant's table above).  capacity: records the device table holds (28 + 4 per
-    uncertainty column bytes each); detections beyond it are dropped and `finish` raises ByoloError(ERR_NOMEM)."""
+    uncertainty column bytes each); detections beyond it are dropped and `finish` raises ByoloError(ERR_NOMEM).
+    loc: the localisation residuals (24 more bytes per record).  None: on for a Model of the two uncertainty variants, with the
+    geometry of model.det_layers, and for a dict layout with a 'det_layers' entry ([(lh, lw, [(prior_h, prior_w), ...]), ...] or
+    DetLayer objects) whose rows carry the ids and variances; off otherwise.  True where it cannot be: ValueError."""
 
-    def __init__(self, model_or_layout, iou_thresh=0.5, min_score=0.0, capacity=1 << 20, device=None, table=None):
+    def __init__(self, model_or_layout, iou_thresh=0.5, min_score=0.0, capacity=1 << 20, device=None, table=None, loc=None, loc_table=None):
         import torch
         lay = model_or_layout
         if not isinstance(lay, dict):
             lay = dict(row_len=int(lay.engine.num_boxes()[1]), obj_idx=int(lay.obj_idx), cls_start_idx=int(lay.cls_start_idx),
-                       cls_cnt=int(lay.cls_cnt))
+                       cls_cnt=int(lay.cls_cnt), det_layers=lay.det_layers)
             if device is None:
                 device = model_or_layout.engine.torch_device
         self.row_len, self.obj_idx, self.cls_start_idx, self.cls_cnt = (int(lay[k]) for k in ('row_len', 'obj_idx', 'cls_start_idx', 'cls_cnt'))
@@ -129,6 +136,43 @@ class Evaluator:
                                           ctypes.c_void_p(self._state.data_ptr()), ctypes.byref(self._h)), handle=False)
         self.sorted = None
         self.reset()
+        self.loc_table = None
+        self._setup_loc(lay, loc, loc_table)
+
+    def _setup_loc(self, lay, loc, loc_table):
+        """Decides whether the residuals are recorded, and hands the geometry table and the loc table to the library."""
+        import torch
+        ids = lay.get('id_cols')
+        try:
+            variant = variant_of(self.row_len, self.cls_cnt)
+        except ValueError:
+            variant = None
+        if ids is None and variant is not None:
+            ids = eval_loc.id_columns(variant, self.cls_cnt)
+        why = None
+        if ids is None:
+            why = 'the rows carry no layer_id / prior_id columns'
+        elif lay.get('det_layers') is None:
+            why = "the layout has no 'det_layers' entry"
+        else:
+            try:
+                self._loc_kinds = eval_loc.variance_kinds(self.unc_names)
+            except ValueError as e:
+                why = str(e)
+        if loc is None:
+            loc = why is None
+        if not loc:
+            return
+        if why is not None:
+            raise ValueError('loc=True: ' + why)
+        cfg = eval_loc.loc_cfg(ids[0], ids[1], eval_loc.geometry(lay['det_layers']))
+        words = _lib.EVAL_LOC_WORDS
+        assert lib.byolo_eval_loc_bytes(self.capacity) == 4 * words * self.capacity
+        # `loc_table`: a caller's int32 tensor, as `table`
+        self.loc_table = torch.empty((self.capacity, words), dtype=torch.int32, device=self.device) if loc_table is None else loc_table
+        assert self.loc_table.is_cuda and self.loc_table.dtype == torch.int32 and self.loc_table.is_contiguous() and \
+            self.loc_table.numel() >= self.capacity * words
+        self._check(lib.byolo_eval_set_loc(self._h, ctypes.byref(cfg), ctypes.c_void_p(self.loc_table.data_ptr())))
 
     def _check(self, rc, handle=True):
         if rc < 0:
@@ -214,12 +258,21 @@ class Evaluator:
         cum_fp = cfp - cfp0[start[:-1]][seg]
         # uncertainty columns: finite / non-finite counts and the float64 sum of the finite ones, over TPs and over FPs
         U = len(self.unc_cols)
-        unc = tf[order][:, _lib.EVAL_RECORD_HEAD:].to(torch.float64)
+        unc32 = tf[order][:, _lib.EVAL_RECORD_HEAD:]
+        unc = unc32.to(torch.float64)
         fin = torch.isfinite(unc)
         is_tp = (tp_s == 1)[:, None]
         ustat = torch.stack([(fin & is_tp).sum(0), (~fin & is_tp).sum(0), (fin & ~is_tp).sum(0), (~fin & ~is_tp).sum(0)]).to(torch.float64)
         usum = torch.stack([torch.where(fin & is_tp, unc, 0.0).sum(0), torch.where(fin & ~is_tp, unc, 0.0).sum(0)])
+        # how well a column separates false from true positives: 2U = sum over FP of (2 #TP below + #TP equal), an integer
+        two_u = torch.zeros(max(U, 1), dtype=torch.int64, device=self.device)
+        for u in range(U):
+            tpv = torch.sort(unc32[:, u][fin[:, u] & is_tp[:, 0]])[0].contiguous()
+            fpv = unc32[:, u][fin[:, u] & ~is_tp[:, 0]].contiguous()
+            two_u[u] = torch.searchsorted(tpv, fpv, right=False).sum() + torch.searchsorted(tpv, fpv, right=True).sum()
+        loc_dev = self._loc_device(t, tf) if self.loc_table is not None else None
         host = torch.cat([start.to(torch.float64), ustat.reshape(-1), usum.reshape(-1)]).cpu().numpy()      # the host wait
+        two_u_h = two_u.cpu().numpy()
         ints = torch.stack([cum_tp, cum_fp]).cpu().numpy()
         table = ts.cpu().numpy()
         start_h = host[:C + 1].astype(np.int64)
@@ -242,9 +295,80 @@ class Evaluator:
                 'tp': {'finite': int(ustat_h[0, u]), 'nonfinite': int(ustat_h[1, u]),
                        'mean': float(usum_h[0, u] / ustat_h[0, u]) if ustat_h[0, u] else float('nan')},
                 'fp': {'finite': int(ustat_h[2, u]), 'nonfinite': int(ustat_h[3, u]),
-                       'mean': float(usum_h[1, u] / ustat_h[2, u]) if ustat_h[2, u] else float('nan')}}
-        return {'n_images': self.n_images, 'n_detections': n, 'iou_thresh': self.iou_thresh, 'min_score': self.min_score,
-                'classes': classes, 'uncertainty': uncertainty}
+                       'mean': float(usum_h[1, u] / ustat_h[2, u]) if ustat_h[2, u] else float('nan')},
+                'auroc_fp': eval_loc.auroc_from(two_u_h[u], ustat_h[2, u], ustat_h[0, u])}
+        out = {'n_images': self.n_images, 'n_detections': n, 'iou_thresh': self.iou_thresh, 'min_score': self.min_score,
+               'classes': classes, 'uncertainty': uncertainty}
+        if loc_dev is not None:
+            out['localisation'] = self._loc_host(loc_dev)
+        return out
+
+    # ---- localisation: residuals against predicted variances ---------------------------------------------------------------
+    def _loc_device(self, t, tf):
+        """The device half: the true positives of the table in table order; per variance kind z = r / sqrt(var), the coverage
+        integers and the order by variance (then table position) of every coordinate.  Returns device tensors."""
+        import torch
+        n = self.n_records
+        lt = self.loc_table.view(-1)[:n * _lib.EVAL_LOC_WORDS].view(n, _lib.EVAL_LOC_WORDS)
+        flags = lt[:, 4]
+        sel = (flags & eval_loc.FLAG_TP) != 0
+        flags_tp = flags[sel]
+        r = lt.view(torch.float32)[:, :4][sel].to(torch.float64)
+        bits = torch.arange(4, device=self.device, dtype=torch.int32)
+        valid = ((flags_tp[:, None] >> bits) & 1) != 0
+        unc = tf[:, _lib.EVAL_RECORD_HEAD:][sel].to(torch.float64)
+        q = torch.tensor(eval_loc.COVERAGE_Q, dtype=torch.float64, device=self.device)
+        var_of = {k: unc[:, idx] for k, idx in self._loc_kinds.items()}
+        if 'epi' in var_of:
+            var_of['total'] = var_of['epi'] + var_of['ale']
+        kinds = {}
+        for kind, var in var_of.items():
+            ok = valid & torch.isfinite(var) & (var > 0)
+            z = torch.where(ok, r / torch.sqrt(torch.where(ok, var, 1.0)), 0.0)
+            cov = ((z.abs()[:, :, None] <= q) & ok[:, :, None]).sum(0)
+            key = torch.where(ok, var, float('inf'))
+            kinds[kind] = (var, ok, z, cov, torch.sort(key, dim=0, stable=True)[1])
+        return {'flags': flags_tp, 'cls': t[:, 2][sel], 'r': r, 'valid': valid, 'kinds': kinds}
+
+    def _loc_host(self, dev):
+        """The host half (byolo/eval_loc.py): float64 sums in ascending index order."""
+        h = lambda x: x.cpu().numpy()
+        flags, cls, r, valid = h(dev['flags']), h(dev['cls']), h(dev['r']), h(dev['valid'])
+        ids = (flags & eval_loc.FLAG_IDS) != 0
+        out = {}
+        per_class = [{'class': c} for c in range(self.cls_cnt)]
+        for kind in eval_loc.KINDS:
+            if kind not in dev['kinds']:
+                continue
+            var, ok, z, cov, order = (h(x) for x in dev['kinds'][kind])
+            out[kind] = {}
+            for pc in per_class:
+                pc[kind] = {}
+            for k, c in enumerate(eval_loc.COORDS):
+                m = ok[:, k]
+                n = int(m.sum())
+                pos = np.cumsum(m) - 1                             # index among the entries that count, of a table position
+                out[kind][c] = eval_loc.stats_from(r[m, k], var[m, k], z[m, k], cov[k], pos[order[:n, k]],
+                                                   n_bad_var=int((valid[:, k] & ~m).sum()), n_outside=int((ids & ~valid[:, k]).sum()))
+                for pc in per_class:
+                    mc = m & (cls == pc['class'])
+                    pc[kind][c] = eval_loc.class_stats(var[mc, k], z[mc, k])
+        out['per_class'] = per_class
+        out['flags'] = {'n_tp': int(len(flags)), 'n_ids_invalid': int((~ids).sum())}
+        return out
+
+    def loc_records(self):
+        """The loc table as a numpy structured array (`eval_loc.LOC_DTYPE`), one entry per record of `records()`."""
+        if self.loc_table is None:
+            raise RuntimeError('localisation is off for this evaluator')
+        summ = _lib.EvalSummary(struct_bytes=ctypes.sizeof(_lib.EvalSummary))
+        class_gt = (ctypes.c_int64 * self.cls_cnt)()
+        lib.byolo_eval_finish(self._h, ctypes.byref(summ), class_gt, self.cls_cnt, self._stream())
+        n = int(summ.n_records)
+        out = np.zeros(n, dtype=eval_loc.LOC_DTYPE)
+        if n:
+            self._check(lib.byolo_eval_loc_records(self._h, out.ctypes.data_as(ctypes.c_void_p), 0, n, self._stream()))
+        return out
 
     def records(self, sorted=False):
         """The record table as a numpy structured array (`record_dtype`): in the order the kernel wrote it, or

@@ -19,6 +19,11 @@
 //      arg-max picks the box; the matched set is one bit per pass in a per-lane word
 //   6  every lane writes its detection's record
 // Float arithmetic here is restated operation by operation (tests/_eval_ref.py): built with -ffp-contract=off.
+//
+// eval_loc_kernel (byolo_eval_set_loc): right behind the match kernel on the same stream, one thread per record of the launch.
+// A true positive's box and its matched ground-truth box are taken back to the raw location values t_x, t_y, t_w, t_h at the
+// detection's own cell and prior (the row's layer_id / prior_id columns), in float64, one operation per line as
+// tests/_eval_loc_ref.py restates them; the residuals t(ground truth) - t(detection) go to a second table, six words per record.
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
@@ -200,6 +205,97 @@ __global__ __launch_bounds__(64) void eval_match_kernel(const EvalArgs a) {
     }
 }
 
+// ---- localisation residuals --------------------------------------------------------------------------------------------------
+static constexpr int LOC_WORDS = BYOLO_EVAL_LOC_WORDS;
+static constexpr int LOC_L = BYOLO_EVAL_LOC_MAX_LAYERS, LOC_P = BYOLO_EVAL_LOC_MAX_PRIORS;
+
+struct LocArgs {
+    const float* rows; const float* gt_boxes; const int32_t* table; const int32_t* state; int32_t* loc; int64_t capacity;
+    int32_t B, cap, D, gmax, rec_words, parity, img_base, layer_col, prior_col, n_layers;
+    int32_t lh[LOC_L], lw[LOC_L], n_priors[LOC_L];
+    float pw[LOC_L][LOC_P], ph[LOC_L][LOC_P];
+};
+
+// an id column: finite, integral and inside [0, n)
+__device__ __forceinline__ bool loc_id(float v, int n, int& id) {
+    const bool ok = v >= 0.f && v < (float)n && floorf(v) == v;      // NaN and inf fail the comparisons
+    id = ok ? (int)v : 0;
+    return ok;
+}
+
+// centre coordinate: the cell and the detection's and the ground truth's offsets inside it (float64, one operation per line)
+__device__ __forceinline__ void loc_centre(double lo, double hi, double glo, double ghi, int n, int& cell, double& p, double& q) {
+    const double c = (lo + hi) * 0.5;
+    const double s = c * (double)n;
+    double f = floor(s);
+    if (!(f >= 0.0)) f = 0.0;                                         // NaN lands in cell 0 and fails the validity test
+    if (f > (double)(n - 1)) f = (double)(n - 1);
+    cell = (int)f;
+    p = s - f;
+    const double g = (glo + ghi) * 0.5;
+    q = g * (double)n - f;
+}
+
+__device__ __forceinline__ double loc_logit(double p) {
+    const double m = 1.0 - p;
+    const double r = p / m;
+    return log(r);
+}
+
+__global__ __launch_bounds__(256) void eval_loc_kernel(const LocArgs a) {
+    constexpr double EPS = 1e-7;
+    const long long first = a.state[ST_TOTAL0 + a.parity];
+    long long last = a.state[ST_TOTAL0 + (a.parity ^ 1)];
+    if (last > a.capacity) last = a.capacity;
+    const long long pos = first + (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (pos < 0 || pos >= last) return;
+    const int32_t* w = a.table + (size_t)pos * a.rec_words;
+    const int b = w[0] - a.img_base, row = w[1], tp = w[4], gt = w[5];
+    float r[4] = {0.f, 0.f, 0.f, 0.f};
+    int flags = 0, cell = 0;
+    if (b >= 0 && b < a.B && row >= 0 && row < a.cap) {
+        const float* d = a.rows + ((size_t)b * a.cap + row) * a.D;
+        int layer, prior = 0;
+        bool ids = loc_id(d[a.layer_col], a.n_layers, layer);
+        if (ids) ids = loc_id(d[a.prior_col], a.n_priors[layer], prior);
+        if (tp == 1) flags |= 16;
+        if (ids) flags |= 32 | (layer << 8) | (prior << 16);
+        if (ids && tp == 1 && gt >= 0 && gt < a.gmax) {
+            const float* g = a.gt_boxes + ((size_t)b * a.gmax + gt) * 4;
+            const int lh = a.lh[layer], lw = a.lw[layer];
+            const double pw = (double)a.pw[layer][prior], ph = (double)a.ph[layer][prior];
+            const double y0 = d[0], x0 = d[1], y1 = d[2], x1 = d[3];
+            const double gy0 = g[0], gx0 = g[1], gy1 = g[2], gx1 = g[3];
+            int ix, iy;
+            double px, qx, py, qy;
+            loc_centre(x0, x1, gx0, gx1, lw, ix, px, qx);
+            loc_centre(y0, y1, gy0, gy1, lh, iy, py, qy);
+            cell = iy * lw + ix;
+            if (px >= EPS && px <= 1.0 - EPS && qx >= EPS && qx <= 1.0 - EPS) {
+                r[0] = (float)(loc_logit(qx) - loc_logit(px));
+                flags |= 1;
+            }
+            if (py >= EPS && py <= 1.0 - EPS && qy >= EPS && qy <= 1.0 - EPS) {
+                r[1] = (float)(loc_logit(qy) - loc_logit(py));
+                flags |= 2;
+            }
+            const double dw = (x1 - x0) / pw, gw = (gx1 - gx0) / pw;
+            if (dw >= EPS && gw >= EPS) {
+                r[2] = (float)(log(gw) - log(dw));
+                flags |= 4;
+            }
+            const double dh = (y1 - y0) / ph, gh = (gy1 - gy0) / ph;
+            if (dh >= EPS && gh >= EPS) {
+                r[3] = (float)(log(gh) - log(dh));
+                flags |= 8;
+            }
+        }
+    }
+    int32_t* o = a.loc + (size_t)pos * LOC_WORDS;
+    o[0] = __float_as_int(r[0]); o[1] = __float_as_int(r[1]); o[2] = __float_as_int(r[2]); o[3] = __float_as_int(r[3]);
+    o[4] = flags; o[5] = cell;
+}
+
 }  // namespace byk
 
 // ---- C-ABI --------------------------------------------------------------------------------------------------------------
@@ -210,6 +306,8 @@ struct byolo_eval {
     int64_t capacity = 0;
     int32_t launches = 0;
     int64_t images = 0;
+    byolo_eval_loc_cfg loc;                                     // valid while d_loc is set (byolo_eval_set_loc)
+    int32_t* d_loc = nullptr;
     std::string err;
 };
 
@@ -287,6 +385,19 @@ extern "C" int32_t byolo_eval_add(byolo_eval_t* ev, const float* d_rows, int32_t
     for (int u = 0; u < BYOLO_EVAL_MAX_UNC; ++u) a.unc[u] = u < ev->cfg.n_unc ? ev->cfg.unc_cols[u] : 0;
     hipLaunchKernelGGL(byk::eval_match_kernel, dim3(B), dim3(64), 0, static_cast<hipStream_t>(stream), a);
     EVHIP(ev, hipGetLastError());
+    if (ev->d_loc) {                                            // the launch's records are final once the match kernel has ended
+        byk::LocArgs l;
+        l.rows = d_rows; l.gt_boxes = d_gt_boxes; l.table = ev->d_table; l.state = ev->d_state; l.loc = ev->d_loc; l.capacity = ev->capacity;
+        l.B = B; l.cap = cap; l.D = ev->cfg.row_len; l.gmax = gmax; l.rec_words = record_words(ev->cfg); l.parity = a.parity; l.img_base = a.img_base;
+        l.layer_col = ev->loc.layer_col; l.prior_col = ev->loc.prior_col; l.n_layers = ev->loc.n_layers;
+        for (int k = 0; k < byk::LOC_L; ++k) {
+            l.lh[k] = ev->loc.lh[k]; l.lw[k] = ev->loc.lw[k]; l.n_priors[k] = ev->loc.n_priors[k];
+            for (int q = 0; q < byk::LOC_P; ++q) { l.pw[k][q] = ev->loc.prior_w[k][q]; l.ph[k][q] = ev->loc.prior_h[k][q]; }
+        }
+        const int64_t threads = (int64_t)B * cap;               // <= 65535 * 4096
+        hipLaunchKernelGGL(byk::eval_loc_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), l);
+        EVHIP(ev, hipGetLastError());
+    }
     ev->launches += 1;
     ev->images += B;
     return BYOLO_OK;
@@ -323,6 +434,49 @@ extern "C" int32_t byolo_eval_records(byolo_eval_t* ev, int32_t* h_dst, int64_t 
     const size_t rw = (size_t)record_words(ev->cfg);
     hipStream_t s = static_cast<hipStream_t>(stream);
     EVHIP(ev, hipMemcpyAsync(h_dst, ev->d_table + (size_t)first * rw, sizeof(int32_t) * rw * (size_t)n_records, hipMemcpyDeviceToHost, s));
+    EVHIP(ev, hipStreamSynchronize(s));
+    return BYOLO_OK;
+}
+
+// ---- localisation residuals ------------------------------------------------------------------------------------------------
+extern "C" size_t byolo_eval_loc_bytes(int64_t capacity) {
+    return capacity < 1 || capacity > 0x7fffffffll ? 0 : sizeof(int32_t) * (size_t)byk::LOC_WORDS * (size_t)capacity;
+}
+
+extern "C" int32_t byolo_eval_set_loc(byolo_eval_t* ev, const byolo_eval_loc_cfg* cfg, void* d_loc_table) {
+    if (!ev) return efail(nullptr, BYOLO_ERR_ARG, "byolo_eval_set_loc: null handle");
+    if (ev->launches) return efail(ev, BYOLO_ERR_STATE, "byolo_eval_set_loc: records were added since the last byolo_eval_reset");
+    if (!d_loc_table) { ev->d_loc = nullptr; return BYOLO_OK; }
+    if (!cfg) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_set_loc: null cfg");
+    if (cfg->struct_bytes != (int32_t)sizeof(byolo_eval_loc_cfg))
+        return efail(ev, BYOLO_ERR_ARG, "byolo_eval_set_loc: struct_bytes %d, this library's byolo_eval_loc_cfg has %d", cfg->struct_bytes, (int)sizeof(byolo_eval_loc_cfg));
+    if (cfg->layer_col < 0 || cfg->layer_col >= ev->cfg.row_len) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_set_loc: layer_col %d outside the row", cfg->layer_col);
+    if (cfg->prior_col < 0 || cfg->prior_col >= ev->cfg.row_len) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_set_loc: prior_col %d outside the row", cfg->prior_col);
+    if (cfg->n_layers < 1 || cfg->n_layers > BYOLO_EVAL_LOC_MAX_LAYERS) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_set_loc: n_layers outside 1 .. %d", BYOLO_EVAL_LOC_MAX_LAYERS);
+    for (int l = 0; l < cfg->n_layers; ++l) {
+        if (cfg->n_priors[l] < 1 || cfg->n_priors[l] > BYOLO_EVAL_LOC_MAX_PRIORS)
+            return efail(ev, BYOLO_ERR_ARG, "byolo_eval_set_loc: n_priors of layer %d outside 1 .. %d", l, BYOLO_EVAL_LOC_MAX_PRIORS);
+        if (cfg->lh[l] < 1 || cfg->lw[l] < 1) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_set_loc: grid of layer %d below 1 x 1", l);
+        for (int p = 0; p < cfg->n_priors[l]; ++p) {
+            const float w = cfg->prior_w[l][p], h = cfg->prior_h[l][p];
+            if (!(w > 0.f && w <= 3.402823466e38f && h > 0.f && h <= 3.402823466e38f))
+                return efail(ev, BYOLO_ERR_ARG, "byolo_eval_set_loc: prior %d of layer %d is not finite and > 0", p, l);
+        }
+    }
+    if (reinterpret_cast<uintptr_t>(d_loc_table) & 3) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_set_loc: d_loc_table must be 4-byte aligned");
+    ev->loc = *cfg;
+    ev->d_loc = static_cast<int32_t*>(d_loc_table);
+    return BYOLO_OK;
+}
+
+extern "C" int32_t byolo_eval_loc_records(byolo_eval_t* ev, int32_t* h_dst, int64_t first, int64_t n_records, void* stream) {
+    if (!ev) return efail(nullptr, BYOLO_ERR_ARG, "byolo_eval_loc_records: null handle");
+    if (!ev->d_loc) return efail(ev, BYOLO_ERR_STATE, "byolo_eval_loc_records: no loc table is set (byolo_eval_set_loc)");
+    if (first < 0 || n_records < 0 || first + n_records > ev->capacity) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_loc_records: records outside the table");
+    if (n_records == 0) return BYOLO_OK;
+    if (!h_dst) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_loc_records: null argument");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    EVHIP(ev, hipMemcpyAsync(h_dst, ev->d_loc + (size_t)first * byk::LOC_WORDS, sizeof(int32_t) * byk::LOC_WORDS * (size_t)n_records, hipMemcpyDeviceToHost, s));
     EVHIP(ev, hipStreamSynchronize(s));
     return BYOLO_OK;
 }

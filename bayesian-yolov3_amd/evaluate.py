@@ -1,14 +1,16 @@
 """
 Evaluation script: scores a checkpoint of any of the three models on LABELLED TFRecord shards (the records
-create_tf_records_*.py writes for training) -- per class AP, log-average miss rate and score calibration, and what the
-uncertainty columns say about true and false positives.  The reference has no counterpart: its inference scripts write
-ECP-JSON for an external toolkit.
+create_tf_records_*.py writes for training) -- per class AP, log-average miss rate and score calibration, what the
+uncertainty columns say about true and false positives, and (aleatoric, bayesian) whether the predicted variances explain
+the localisation error of the true positives.  The reference has no counterpart: its inference scripts write ECP-JSON for an
+external toolkit.
 
     python evaluate.py --model standard|aleatoric|bayesian        (edit the config in `main()`)
 
 Same config keys as `inference_*.py` (`data.file_pattern` names the labelled shards; `crop: True` evaluates the centre crop of
 `crop_img_size`, the reference's ValDataset), plus the optional `iou_thresh` (0.5), `min_score` (0.0), `eval_capacity`
-(records the device table holds, default 2^20) and `eval_batches` (stop after that many batches).  `weights='synthetic'`,
+(records the device table holds, default 2^20), `eval_batches` (stop after that many batches) and `localisation` (None: on
+for the aleatoric and bayesian models; False: off).  `weights='synthetic'`,
 `seed` and `engine_options` as in the inference scripts.
 
 `Model.run` -> `Evaluator.add` per batch (byolo/evaluate.py: one matching kernel per batch on the forward's stream); batches
@@ -50,6 +52,7 @@ def check_config(config, model='bayesian'):
     cfg.setdefault('min_score', 0.0)
     cfg.setdefault('eval_capacity', 1 << 20)
     cfg.setdefault('eval_batches', None)
+    cfg.setdefault('localisation', None)
     cfg.setdefault('seed', 0)
     cfg.setdefault('cpu_thread_cnt', 1)
     cfg.setdefault('T', 1)
@@ -125,7 +128,7 @@ def evaluate(config, model='bayesian'):
     m, checkpoint = build_model(cfg)
     out_path = '{}_{}'.format(cfg['out_path'], _inf.step_of(checkpoint))
     os.makedirs(out_path)                                 # like the inference scripts: refuses to overwrite an existing run
-    ev = Evaluator(m, iou_thresh=cfg['iou_thresh'], min_score=cfg['min_score'], capacity=cfg['eval_capacity'])
+    ev = Evaluator(m, iou_thresh=cfg['iou_thresh'], min_score=cfg['min_score'], capacity=cfg['eval_capacity'], loc=cfg['localisation'])
     feed = dataset_utils._Feed(cfg, 'data', 'eval', device=m.engine.torch_device)
     try:
         t0 = time.time()
@@ -139,8 +142,13 @@ def evaluate(config, model='bayesian'):
     for c in metrics['classes']:
         logging.info(class_line(c))
     for name, u in metrics['uncertainty'].items():
-        logging.info('{:16s}: mean over TP {:.6g} ({} finite, {} not), over FP {:.6g} ({} finite, {} not)'.format(
-            name, u['tp']['mean'], u['tp']['finite'], u['tp']['nonfinite'], u['fp']['mean'], u['fp']['finite'], u['fp']['nonfinite']))
+        logging.info('{:16s}: mean over TP {:.6g} ({} finite, {} not), over FP {:.6g} ({} finite, {} not), AUROC FP over TP {:.4f}'.format(
+            name, u['tp']['mean'], u['tp']['finite'], u['tp']['nonfinite'], u['fp']['mean'], u['fp']['finite'], u['fp']['nonfinite'],
+            u['auroc_fp']))
+    if 'localisation' in metrics:
+        from byolo import eval_loc
+        for line in eval_loc.log_lines(metrics['localisation']):
+            logging.info(line)
     metrics.update(images=images, checkpoint=checkpoint, model=MODELS[cfg['model']], loop_seconds=loop_seconds,
                    steady_img_s=steady_rate(points),
                    config=json.loads(json.dumps(cfg, default=lambda x: str(x))))

@@ -198,7 +198,8 @@ class EvalHook:
     """config['eval_interval'] (absent: no hook, the run is what it was): every that many steps the trained heads are handed
     to an inference model (built once, at the evaluation size: the centre crop when config['crop'], else the full frame) and
     config['eval_batches'] (default 4) batches of the 'val' shards are scored through the feed's 'eval' split
-    (byolo/evaluate.py).  Logs '{step} eval  >>> class c: LAMR .., AP ..; ...'.  Reads the trainer, never writes it; the
+    (byolo/evaluate.py).  Logs '{step} eval  >>> class c: LAMR .., AP ..; ...' and, for the models whose rows carry
+    variances, '{step} evloc >>> ale x: rmse .., sigma_scale .., nll ..; ...'.  Reads the trainer, never writes it; the
     'eval' split draws no random number, so the training and validation streams are what they are without the hook."""
 
     def __init__(self, model_cls, config):
@@ -239,6 +240,11 @@ class EvalHook:
             ev.close()
         logging.info('{:5d} eval  >>> '.format(step) + '; '.join(
             'class {}: LAMR {:.4f}, AP {:.4f}'.format(c['class'], c['lamr'], c['ap']) for c in self.last['classes']))
+        loc = self.last.get('localisation')
+        if loc is not None:
+            logging.info('{:5d} evloc >>> '.format(step) + '; '.join(
+                '{} {}: n {}, rmse {:.4f}, sigma_scale {:.4f}, nll {:.4f}'.format(kind, c, s['n'], s['rmse'], s['sigma_scale'], s['nll'])
+                for kind in ('ale', 'epi', 'total') if kind in loc for c, s in loc[kind].items()))
         return self.last
 
     def close(self):

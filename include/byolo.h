@@ -615,6 +615,33 @@ BYOLO_API int32_t byolo_eval_add(byolo_eval_t* ev, const float* d_rows, int32_t 
 BYOLO_API int32_t byolo_eval_finish(byolo_eval_t* ev, byolo_eval_summary* out, int64_t* h_class_gt, int32_t n_classes, void* stream);
 BYOLO_API int32_t byolo_eval_records(byolo_eval_t* ev, int32_t* h_dst, int64_t first, int64_t n_records, void* stream);
 
+/* Localisation residuals (aleatoric and Bayesian rows; INTEGRATION.md "Evaluation" has the definitions).  With a loc table set,
+ * byolo_eval_add launches a second kernel right behind the matching on the same stream that writes, for every record of the
+ * batch and at the record's index, BYOLO_EVAL_LOC_WORDS 32-bit words:
+ *   0 .. 3  float residual r_x, r_y, r_w, r_h = t(matched ground-truth box) - t(detection): both boxes taken back to the raw
+ *           location values at the detection's own cell and prior (the row's layer_col / prior_col columns name them), in
+ *           float64, rounded once to float32
+ *   4       int32 flags: bits 0 - 3 the coordinate's residual is valid, bit 4 tp, bit 5 the row's ids are valid, bits 8 - 15
+ *           the layer, bits 16 - 23 the prior (both 0 with invalid ids)
+ *   5       int32 cell iy * lw + ix
+ * A record that is not a true positive, or whose ids are not finite, integral and inside this table, has residuals 0, valid
+ * bits 0 and cell 0.  lh / lw: the layer's grid; prior_w / prior_h: the priors as the decode uses them (normalised).
+ * d_loc_table holds byolo_eval_loc_bytes(capacity) bytes, caller-owned, 4-byte aligned; NULL switches the residuals off.
+ * byolo_eval_set_loc is refused with BYOLO_ERR_STATE between the first byolo_eval_add and the next byolo_eval_reset, and with
+ * BYOLO_ERR_ARG (message: the argument) otherwise.  The main records are the same bytes with and without it. */
+#define BYOLO_EVAL_LOC_WORDS 6
+#define BYOLO_EVAL_LOC_MAX_LAYERS 8
+#define BYOLO_EVAL_LOC_MAX_PRIORS 16
+typedef struct byolo_eval_loc_cfg {
+    int32_t struct_bytes;          /* sizeof(byolo_eval_loc_cfg) of the caller's header: a mismatch is BYOLO_ERR_ARG */
+    int32_t layer_col, prior_col, n_layers;
+    int32_t lh[BYOLO_EVAL_LOC_MAX_LAYERS], lw[BYOLO_EVAL_LOC_MAX_LAYERS], n_priors[BYOLO_EVAL_LOC_MAX_LAYERS];
+    float prior_w[BYOLO_EVAL_LOC_MAX_LAYERS][BYOLO_EVAL_LOC_MAX_PRIORS], prior_h[BYOLO_EVAL_LOC_MAX_LAYERS][BYOLO_EVAL_LOC_MAX_PRIORS];
+} byolo_eval_loc_cfg;
+BYOLO_API size_t byolo_eval_loc_bytes(int64_t capacity);
+BYOLO_API int32_t byolo_eval_set_loc(byolo_eval_t* ev, const byolo_eval_loc_cfg* cfg, void* d_loc_table);
+BYOLO_API int32_t byolo_eval_loc_records(byolo_eval_t* ev, int32_t* h_dst, int64_t first, int64_t n_records, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
