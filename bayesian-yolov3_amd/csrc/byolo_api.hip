@@ -1532,6 +1532,7 @@ static int32_t calibrate_bn_impl(byolo_t* h, const float* d_img, int32_t B, void
         else if (h->plan.feed[si] == 2) h->plan.off[s.out_tensor] = h->plan.off[s.addend_tensor];
     }
     HIPCHK(h, hipSetDevice(h->device));
+    h->last_ws = d_workspace;                                   // byolo_layer_output: what the calibration leaves is readable like a forward's
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     char* ws = reinterpret_cast<char*>(d_workspace);
     double* d_tmp = reinterpret_cast<double*>(ws + h->plan.stats_off);
@@ -1552,7 +1553,9 @@ static int32_t calibrate_bn_impl(byolo_t* h, const float* d_img, int32_t B, void
         fill_conv(h, s, d_img, ws, B, 1, p);
         if (!s.is_conv()) { int32_t rc = run_aux_step(h, s, p, st); if (rc) return rc; continue; }
         const int ctile = split ? conv_split_tile(s.tile, s.kx3 || s.p1) : s.tile;
-        if (l.op == OP_DETECTION) { if (split) p.flags |= EPI_F32OUT; HIPCHK(h, launch_conv_igemm(p, ctile, st)); continue; }
+        // (a head over input channels that are no multiple of 32 is a direct convolution like any other: the matrix-pipe launcher
+        //  divides by its 0 K-tiles)
+        if (l.op == OP_DETECTION) { if (split) p.flags |= EPI_F32OUT; HIPCHK(h, l.direct ? launch_conv_direct(p, st) : launch_conv_igemm(p, ctile, st)); continue; }
         // raw conv output (+ addend for STEP_MAIN), fp32; split precision: the accumulators, ACT_SCALE * 2^wshift * conv
         p.scale = h->d_ones; p.shift = h->d_zeros; p.flags = split ? (s.mode == STEP_PARTIAL ? EPI_RAW : EPI_F32OUT) : 0;
         if (split && l.direct) p.split &= 1;                               // direct launch: plain fp32 output here
@@ -1599,7 +1602,11 @@ extern "C" int32_t byolo_calibrate_bn(byolo_t* h, const float* d_img, int32_t B,
                                       void* stream) {
     return guarded(h, "byolo_calibrate_bn", [&] {
         const int32_t rc = calibrate_bn_impl(h, d_img, B, d_workspace, workspace_bytes, stream);
-        if (h) h->plan.B = -1;                                  // (the next call plans again: calibrate_bn_impl gives folded tensors memory)
+        if (h) {                                                // a doctored plan is dropped (calibrate_bn_impl gives folded tensors memory): the next
+            bool doctored = rc != BYOLO_OK;                     // call plans again; any other stays, and byolo_layer_output reads the (B, 1) run
+            for (char f : h->plan.feed) doctored = doctored || f != 0;
+            if (doctored) h->plan.B = -1;
+        }
         return rc;
     });
 }

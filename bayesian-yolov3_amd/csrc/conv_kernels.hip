@@ -369,33 +369,37 @@ hipError_t launch_split_to_f32(const float* src, float* dst, int64_t n, float mu
 // calibration helpers (byolo_calibrate_bn): per-channel batch statistics, device-side BN fold,
 // in-place BN + leaky [+ residual].  Not on the inference hot path.
 // ---------------------------------------------------------------------------------------------
+// Sums of (x - k) and (x - k)^2 with k = the channel's value in row 0 (the same for every block, so partial sums still add up):
+// x - k is exact in double, and E[(x-k)^2] - E[x-k]^2 does not cancel the way E[x^2] - E[x]^2 does for a channel whose mean is
+// large against its spread (mean 1000, variance 1e-6: the unshifted form in double is 1e-3 off, tests/test_calibrate_gpu.py).
 __global__ void channel_stats_partial(const float* x, int64_t M, int C, double* tmp /*[blocks][2][C]*/) {
     // block handles a strided set of rows; thread c-strided over channels
     for (int c = threadIdx.x; c < C; c += blockDim.x) {
+        const double k = x[c];
         double s = 0.0, q = 0.0;
         for (int64_t m = blockIdx.x; m < M; m += gridDim.x) {
-            const double v = x[m * C + c];
+            const double v = (double)x[m * C + c] - k;
             s += v; q += v * v;
         }
         tmp[((size_t)blockIdx.x * 2 + 0) * C + c] = s;
         tmp[((size_t)blockIdx.x * 2 + 1) * C + c] = q;
     }
 }
-__global__ void channel_stats_final(const double* tmp, int blocks, int64_t M, int C, float* mean, float* var) {
+__global__ void channel_stats_final(const float* x, const double* tmp, int blocks, int64_t M, int C, float* mean, float* var) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
     double s = 0.0, q = 0.0;
     for (int b = 0; b < blocks; ++b) { s += tmp[((size_t)b * 2) * C + c]; q += tmp[((size_t)b * 2 + 1) * C + c]; }
-    const double mu = s / (double)M;
-    double v = q / (double)M - mu * mu;
+    const double d = s / (double)M;                       // mean - k
+    double v = q / (double)M - d * d;
     if (v < 0) v = 0;
-    mean[c] = (float)mu; var[c] = (float)v;
+    mean[c] = (float)((double)x[c] + d); var[c] = (float)v;
 }
 static constexpr int STATS_BLOCKS = 1024;
 hipError_t launch_channel_stats(const float* x, int64_t M, int C, float* d_mean, float* d_var, double* d_tmp,
                                 hipStream_t st) {
     hipLaunchKernelGGL(channel_stats_partial, dim3(STATS_BLOCKS), dim3(256), 0, st, x, M, C, d_tmp);
-    hipLaunchKernelGGL(channel_stats_final, dim3((C + 255) / 256), dim3(256), 0, st, d_tmp, STATS_BLOCKS, M, C,
+    hipLaunchKernelGGL(channel_stats_final, dim3((C + 255) / 256), dim3(256), 0, st, x, d_tmp, STATS_BLOCKS, M, C,
                        d_mean, d_var);
     return hipGetLastError();
 }

@@ -392,7 +392,22 @@ BYOLO_API int32_t byolo_loss(byolo_t* h, int32_t kind, int32_t aleatoric_loss, i
 /* ---- synthetic-weight support: data-dependent BN initialisation (no reference counterpart;
  * replaces "train the network" for benchmarking with random-init weights): runs the graph on
  * d_img with dropout off, sets every BN's moving_mean/variance to the batch statistics of its conv
- * output layer by layer, re-folds.  Read the result back with byolo_get_param. */
+ * output layer by layer, re-folds.  Read the result back with byolo_get_param.
+ * The contract (tests/test_calibrate_gpu.py, against oracle/cpu_ref.forward(calibrate=True) in float64; measured distances in
+ * profiles/calibrate_parity.md):
+ *   - the statistics of a layer are those of its RAW convolution output (before dropout, BN and leaky-ReLU) over all B * h * w rows,
+ *     computed on the activations the layers in front produce with the statistics just set for them;
+ *   - the variance is the biased one (divided by the row count, like tf.nn.moments);
+ *   - dropout is off; a stacked graph runs at T = 1;
+ *   - sums are accumulated in double, around the channel's value in row 0, in a fixed order: a channel of mean 1000 and variance
+ *     1e-6 comes out to 1e-4 relative, one row gives variance exactly 0, and the result is deterministic (calibrating twice, or two
+ *     handles on the same frames, gives identical parameters);
+ *   - in every precision and plan the handle afterwards equals one finalized from byolo_get_param's values: a forward on either gives
+ *     the same bits; launch graphs captured before the call replay with the new statistics; with keep_all_outputs,
+ *     byolo_layer_output reads the (B, T = 1) run the calibration left in d_workspace.
+ * Frames that give fewer than about 9 rows at the coarsest grid (B * h * w at stride 32) produce near-zero variances: the folded
+ * 1 / sqrt(var + 1e-5) then amplifies rounding by up to 316 per layer and the weights are ill conditioned.  Statistics that are
+ * not finite are BYOLO_ERR_ARG. */
 BYOLO_API int32_t byolo_calibrate_bn(byolo_t* h, const float* d_img, int32_t B, void* d_workspace, size_t workspace_bytes,
                            void* stream);
 
