@@ -68,6 +68,16 @@ class EvalSummary(ctypes.Structure):
                [(n, ctypes.c_int64) for n in ("n_records", "n_seen", "n_images")]
 
 
+VOTE_NONE, VOTE_ALE, VOTE_EPI, VOTE_TOTAL = 0, 1, 2, 3            # BYOLO_VOTE_*
+
+
+class VoteCfg(ctypes.Structure):
+    """include/byolo.h byolo_vote_cfg (field for field; tests/test_box_vote_cpu.py compares the two)."""
+    _fields_ = [("struct_bytes", ctypes.c_int32), ("var", ctypes.c_int32)] + \
+               [(n, ctypes.c_float) for n in ("sigma_t", "iou_min", "min_score", "var_floor")] + \
+               [("ale_col", ctypes.c_int32), ("epi_col", ctypes.c_int32)]
+
+
 _i32, _i64, _f32 = ctypes.c_int32, ctypes.c_int64, ctypes.c_float
 _vp, _cp, _sz, _u64 = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint64
 _P = ctypes.POINTER
@@ -168,6 +178,10 @@ PROTOTYPES = {
     "byolo_eval_loc_bytes": (_sz, [_i64]),
     "byolo_eval_set_loc": (_i32, [_vp, _P(EvalLocCfg), _vp]),
     "byolo_eval_loc_records": (_i32, [_vp, _vp, _i64, _i64, _vp]),
+    "byolo_box_vote_workspace_bytes": (_sz, [_i32, _i64]),
+    "byolo_box_vote": (_i32, [_vp, _vp, _i32, _i64, _i32, _i32, _i32, _i32, _P(VoteCfg), _P(EvalLocCfg), _vp, _vp, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "byolo_set_box_vote": (_i32, [_vp, _P(VoteCfg)]),
+    "byolo_box_vote_counts": (_i32, [_vp, _vp, _i32, _i32, _vp]),
 }
 
 

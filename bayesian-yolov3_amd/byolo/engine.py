@@ -37,6 +37,7 @@ class Engine:
         self._graph = []                 # the builder calls in order: twin() replays them on a second handle
         self._twin = None
         self._trainers = weakref.WeakSet()       # byolo.train.HeadTrainer objects bound to this handle (closed before it)
+        self._box_vote = None            # the settings set_box_vote() switched variance voting on with (None: off)
 
     # ---- arithmetic of the convolution stack (include/byolo.h: BYOLO_PREC_*) ----------------------------
     @property
@@ -164,6 +165,8 @@ class Engine:
             getattr(t, name)(*args)
         t.set_plan_opts(**self.plan_opts())               # the same plan on both handles (per-handle since round 6)
         t.set_precision(precision)
+        if self._box_vote is not None:
+            t.set_box_vote(self._box_vote)
         t.set_params(self.get_params())
         t.finalize()
         return t
@@ -430,7 +433,84 @@ class Engine:
         res = dict(boxes=boxes, rows=rows, kept=kept, count=count)
         if want_nms and self.cfg.nms_mode == _lib.NMS_PER_CLASS:
             res["class_counts"] = self._class_counts(B, dev, stream)
+        if want_nms and self._box_vote is not None:       # 'rows' are the voted rows (byolo_set_box_vote)
+            vn = torch.empty((B, self.out_cap), dtype=torch.int32, device=dev)
+            check(self._h, lib.byolo_box_vote_counts(self._h, ctypes.c_void_p(vn.data_ptr()), B, self.out_cap, ctypes.c_void_p(stream)))
+            res["vote_n"] = vn
         return res
+
+    # ---- variance voting (include/byolo.h "variance voting") ---------------------------------
+    VOTE_KINDS = {"none": _lib.VOTE_NONE, "ale": _lib.VOTE_ALE, "epi": _lib.VOTE_EPI, "total": _lib.VOTE_TOTAL}
+
+    @classmethod
+    def _vote_cfg(cls, settings, ale_col, epi_col):
+        """byolo_vote_cfg of a settings dict (var, sigma_t, iou_min, min_score, var_floor).  var defaults to what the rows offer:
+        'total' for Bayesian rows, 'ale' for aleatoric rows, 'none' without variances.  sigma_t = 0.02 and var_floor = 1e-8 are
+        starting values, not tuned on any checkpoint."""
+        s = dict(settings)
+        var = s.pop("var", None)
+        if var is None:
+            var = "total" if epi_col >= 0 else ("ale" if ale_col >= 0 else "none")
+        if var not in cls.VOTE_KINDS:
+            raise ValueError("box_vote: var is one of %s, not %r" % (sorted(cls.VOTE_KINDS), var))
+        cfg = _lib.VoteCfg(struct_bytes=ctypes.sizeof(_lib.VoteCfg), var=cls.VOTE_KINDS[var], sigma_t=float(s.pop("sigma_t", 0.02)),
+                           iou_min=float(s.pop("iou_min", 0.0)), min_score=float(s.pop("min_score", 0.0)),
+                           var_floor=float(s.pop("var_floor", 1e-8)), ale_col=int(ale_col), epi_col=int(epi_col))
+        if s:
+            raise TypeError("box_vote: unknown settings %s" % sorted(s))
+        return cfg
+
+    def set_box_vote(self, settings=True):
+        """Variance voting inside forward(): True or a dict of settings switches it on -- 'rows' are then the voted rows and the
+        result has 'vote_n' [B, cap] --, False / None switches it off (the default; forward() is then what it was).  Call it once
+        the graph has its detection layers: the default of `var` follows their kind."""
+        if settings is None or settings is False:
+            check(self._h, lib.byolo_set_box_vote(self._h, None))
+            self._box_vote = None
+            return
+        settings = {} if settings is True else dict(settings)
+        kinds = [a[1] for n, a in self._graph if n == "add_detection"]
+        if not kinds:
+            raise ValueError("set_box_vote: add the detection layers first")
+        ale_col, epi_col = {_lib.DET_STANDARD: (-1, -1), _lib.DET_ALEATORIC: (4, -1), _lib.DET_EPISTEMIC: (8, 4)}[int(kinds[-1])]
+        cfg = self._vote_cfg(settings, ale_col, epi_col)
+        check(self._h, lib.byolo_set_box_vote(self._h, ctypes.byref(cfg)))
+        self._box_vote = settings
+
+    def box_vote(self, boxes, nms_result, obj_idx, cls_start_idx, nms_mode=None, geom=None, ale_col=None, epi_col=None,
+                 layer_col=None, prior_col=None, **settings):
+        """The voting stage by itself (byolo_box_vote) on pre-NMS rows `boxes` [B, N, D] and the result of sort_nms / forward
+        on them: returns {'rows': voted copy of nms_result['rows'], 'vote_n': [B, cap] int32}; nms_result is not touched.
+        geom: the detection layers (lib_yolo DetLayer objects or (lh, lw, priors) tuples, byolo.eval_loc.geometry), needed unless
+        var='none'.  The variance and id columns default to the decode's for a row of this length (aleatoric 14 + C: ale 4;
+        Bayesian 21 + C: epi 4, ale 8; ids in the last two columns)."""
+        torch = _torch()
+        from . import eval_loc
+        assert boxes.is_cuda and boxes.dtype == torch.float32 and boxes.is_contiguous() and boxes.dim() == 3
+        B, N, D = boxes.shape
+        rows_in, kept, count = nms_result["rows"], nms_result["kept"], nms_result["count"]
+        cap = int(rows_in.shape[1])
+        assert rows_in.is_contiguous() and kept.is_contiguous() and count.is_contiguous()
+        assert tuple(rows_in.shape) == (B, cap, D) and tuple(kept.shape) == (B, cap) and tuple(count.shape) == (B, 2)
+        nms_mode = self.cfg.nms_mode if nms_mode is None else nms_mode
+        C = self.cfg.cls_cnt
+        if ale_col is None and epi_col is None:
+            ale_col, epi_col = {14 + C: (4, -1), 21 + C: (8, 4)}.get(D, (-1, -1))
+        ale_col, epi_col = -1 if ale_col is None else ale_col, -1 if epi_col is None else epi_col
+        cfg = self._vote_cfg(settings, ale_col, epi_col)
+        loc = None
+        if geom is not None:
+            loc = eval_loc.loc_cfg(D - 2 if layer_col is None else layer_col, D - 1 if prior_col is None else prior_col, eval_loc.geometry(geom))
+        wsb = int(lib.byolo_box_vote_workspace_bytes(B, N))
+        ws = torch.empty(max(wsb, 8), dtype=torch.uint8, device=boxes.device)
+        rows = torch.empty_like(rows_in)
+        vote_n = torch.empty((B, cap), dtype=torch.int32, device=boxes.device)
+        stream = torch.cuda.current_stream(boxes.device).cuda_stream
+        p = lambda t: ctypes.c_void_p(t.data_ptr())
+        check(self._h, lib.byolo_box_vote(self._h, p(boxes), B, N, D, int(obj_idx), int(cls_start_idx), int(nms_mode), ctypes.byref(cfg),
+                                          ctypes.byref(loc) if loc is not None else None, p(rows_in), p(kept), p(count), cap, p(rows),
+                                          p(vote_n), p(ws), wsb, ctypes.c_void_p(stream)))
+        return dict(rows=rows, vote_n=vote_n)
 
     def layer_output(self, idx):
         """Copy of layer `idx`'s output after a forward (needs keep_all_outputs=True)."""

@@ -438,6 +438,9 @@ class InferenceLoop:
                 return None, flags
             rows = eng.finish_tshard(buf[:N * D].view(1, N, D), T)
             res = eng.sort_nms(rows, self.model.obj_idx, self.model.cls_start_idx)
+            vote = getattr(eng, '_box_vote', None)
+            if vote is not None:                           # engine_options['box_vote']: what byolo_forward does behind its own NMS
+                res.update(eng.box_vote(rows, res, self.model.obj_idx, self.model.cls_start_idx, geom=self.model.det_layers, **vote))
             if n_img % world != rank:
                 return False, flags
             n = int(res['count'][0, 0])

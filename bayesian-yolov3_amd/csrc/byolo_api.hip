@@ -153,6 +153,7 @@ extern "C" int32_t byolo_destroy(byolo_t* h) {
         if (h->ev_convs) (void)hipEventDestroy(h->ev_convs);
         if (h->d_status) (void)hipFree(h->d_status);
         if (h->pc_own) (void)hipFree(h->pc_own);
+        if (h->vn_own) (void)hipFree(h->vn_own);
         if (h->h_status) (void)hipHostFree(h->h_status);
         for (auto& ps : h->prof) {
             for (auto& e : ps.ev) if (e) (void)hipEventDestroy(e);
@@ -960,6 +961,13 @@ static int32_t forward_impl(byolo_t* h, const float* d_img, int32_t B, int32_t T
                 HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->pc_own), (size_t)B * cc * sizeof(int32_t)));
                 h->pc_own_cap = (size_t)B * cc;
             }
+            const bool voting = h->vote_on && d_rows;
+            if (voting && h->vn_own_cap < (size_t)B * out_cap) {
+                HIPCHK(h, hipSetDevice(h->device));
+                if (h->vn_own) { HIPCHK(h, hipDeviceSynchronize()); HIPCHK(h, hipFree(h->vn_own)); h->vn_own = nullptr; h->vn_own_cap = 0; }
+                HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->vn_own), (size_t)B * out_cap * sizeof(int32_t)));
+                h->vn_own_cap = (size_t)B * out_cap;
+            }
             int32_t rc = BYOLO_OK;
             for (int64_t lo = 0; lo < B && rc == BYOLO_OK; lo += cap) {
                 const int32_t n = (int32_t)std::min<int64_t>(cap, B - lo);
@@ -973,8 +981,14 @@ static int32_t forward_impl(byolo_t* h, const float* d_img, int32_t B, int32_t T
                                                         hipMemcpyDeviceToDevice, reinterpret_cast<hipStream_t>(stream));
                     if (e != hipSuccess) rc = fail(h, BYOLO_ERR_HIP, "byolo_forward: per-class counts of a piece: %s", hipGetErrorString(e));
                 }
+                if (rc == BYOLO_OK && voting) {
+                    const hipError_t e = hipMemcpyAsync(h->vn_own + (size_t)lo * out_cap, h->vn_ptr, (size_t)n * out_cap * sizeof(int32_t),
+                                                        hipMemcpyDeviceToDevice, reinterpret_cast<hipStream_t>(stream));
+                    if (e != hipSuccess) rc = fail(h, BYOLO_ERR_HIP, "byolo_forward: vote counts of a piece: %s", hipGetErrorString(e));
+                }
             }
             if (rc == BYOLO_OK && per_class) { h->pc_counts = h->pc_own; h->pc_B = B; }
+            if (rc == BYOLO_OK && voting) { h->vn_ptr = h->vn_own; h->vn_B = B; }
             h->first_image = first;
             return rc;
         }
@@ -1009,6 +1023,12 @@ static int32_t forward_piece(byolo_t* h, const float* d_img, int32_t B, int32_t 
         if (h->cls_start + h->cfg.cls_cnt > h->row_len) return fail(h, BYOLO_ERR_ARG, "byolo_forward: per-class NMS: class columns outside the row");
         h->pc_counts = nms_class_counts_ptr(static_cast<char*>(d_workspace) + h->plan.nms_off, B, h->n_boxes, h->cfg.cls_cnt);
         h->pc_B = B; h->pc_C = h->cfg.cls_cnt;
+    }
+    if (d_rows && h->vote_on) {                             // refused here as well: a variance kind the handle's rows do not have
+        VoteParams v;
+        rc = byolo_vote_from_handle(h, &v, "byolo_forward"); if (rc) return rc;
+        h->vn_ptr = reinterpret_cast<const int32_t*>(static_cast<char*>(d_workspace) + h->plan.vote_n_off);
+        h->vn_B = B; h->vn_cap = (int32_t)nms_out_cap(h);
     }
     // (see ev_convs)  Only where a forward fills the chip by itself: a small one -- 8 images at 416 x 416 are 0.5 TFLOP in launches of
     // a few dozen tiles -- gains from running beside the next (config 2: 2480 img/s one after the other, 3110 side by side).
@@ -1315,6 +1335,14 @@ static int32_t enqueue_forward(byolo_t* h, const FwdArgs& a, hipStream_t st, boo
         n.rows = d_rows; n.kept = d_kept; n.count = d_count; n.general_only = h->opts.nms_general != 0;
         if (h->cfg.nms_mode == BYOLO_NMS_TWO_CLASS && h->cfg.cls_cnt != 2) return fail(h, BYOLO_ERR_ARG, "byolo_forward: 2-class NMS needs cls_cnt == 2");
         HIPCHK(h, launch_sort_nms(n, st));
+        if (h->vote_on) {                                   // variance voting, in place on the kept rows (box_vote.hip)
+            VoteParams v;
+            rc = byolo_vote_from_handle(h, &v, "byolo_forward"); if (rc) return rc;
+            v.boxes = boxes; v.B = B; v.rows_in = d_rows; v.rows_out = d_rows; v.kept = d_kept; v.count = d_count; v.cap = (int)nms_out_cap(h);
+            v.vote_n = reinterpret_cast<int32_t*>(ws + h->plan.vote_n_off);
+            v.ws = ws + h->plan.vote_off; v.ws_bytes = box_vote_workspace_bytes(B, h->n_boxes);
+            HIPCHK(h, launch_box_vote(v, st));
+        }
     }
     if (h->profiling) { HIPCHK(h, hipEventRecord(h->wslot().ev[4], st)); h->wslot().ev_valid = true; }
     return BYOLO_OK;

@@ -120,6 +120,7 @@ struct Plan {
     int B = -1, T = -1;
     std::vector<int64_t> off;      // per layer tensor offset in bytes (-1: none)
     size_t arena = 0, boxes_off = 0, nms_off = 0, stats_off = 0, total = 0;
+    size_t vote_n_off = 0, vote_off = 0;   // box voting (byolo_set_box_vote): vote_n [B, cap] and the stage's workspace; no bytes while it is off
     size_t img_split_off = 0;      // split precision: the image as hi/lo pairs, for a matrix-pipe convolution that reads it (img_c % 32 == 0)
     size_t slab_off = 0, slab_bytes = 0, cnt_off = 0, cnt_bytes = 0;   // split-K slabs (shared by all steps), per-step ticket counters
     std::vector<ConvSplit> split;  // per step
@@ -215,6 +216,11 @@ struct byolo {
     // pc_own (a forward that ran in pieces)
     const int32_t* pc_counts = nullptr; int32_t pc_B = 0, pc_C = 0;
     int32_t* pc_own = nullptr; size_t pc_own_cap = 0;
+    // byolo_set_box_vote: byolo_forward votes in place behind the NMS (box_vote.hip).  vn_ptr: where the last such forward left
+    // vote_n [vn_B, vn_cap] -- inside that call's workspace, or in vn_own (a forward that ran in pieces)
+    bool vote_on = false; byolo_vote_cfg vote_cfg = {};
+    const int32_t* vn_ptr = nullptr; int32_t vn_B = 0, vn_cap = 0;
+    int32_t* vn_own = nullptr; size_t vn_own_cap = 0;
     int64_t first_image = 0;       // position of a call's first image in the logical batch (dropout stream)
     int stop_layer = -1;           // >= 0: enqueue_forward stops in front of the first step of this layer (byolo_run_backbone)
     int tshard_t0 = 0, tshard_T = 0;   // byolo_set_tshard: this call's T samples are samples t0 .. t0 + T - 1 of tshard_T per image (0 = off)
@@ -279,4 +285,7 @@ int32_t check_run(byolo_t* h, int32_t B, int32_t T, const char* what, bool need_
 // byolo_api.hip: the convolutions in front of byolo_mark_backbone_end as byolo_forward enqueues them (plan of (B, 1), no dropout,
 // no decode); the tensors the heads read stay live in d_workspace.  Split precision: waits for the stream and returns BYOLO_ERR_RANGE
 // (status cleared) if an activation left the range.  For the head trainer (train_heads.hip).
+// box_vote.hip: the VoteParams of byolo_forward's voting stage from the handle's rows and detection layers (pointers left null)
+int32_t byolo_vote_from_handle(byolo_t* h, VoteParams* p, const char* what);
+static inline int64_t nms_out_cap(const byolo_t* h) { return (int64_t)h->cfg.max_out * nms_classes(h->cfg.nms_mode, h->cfg.cls_cnt); }
 int32_t byolo_run_backbone(byolo_t* h, const float* d_img, int32_t B, void* d_workspace, size_t workspace_bytes, hipStream_t st);

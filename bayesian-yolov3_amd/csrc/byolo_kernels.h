@@ -285,6 +285,24 @@ struct NmsParams {
 const int32_t* nms_class_counts_ptr(void* ws, int B, int64_t N, int C);   // the kept-per-class counts [B, C] of a run with C classes, inside ws
 hipError_t launch_sort_nms(const NmsParams& p, hipStream_t st);
 
+// ---- variance voting behind the NMS (box_vote.hip; include/byolo.h "variance voting") ------------------------------------
+struct VoteGeom { int layer_col, prior_col, n_layers; int lh[8], lw[8], n_priors[8]; };      // byolo_eval_loc_cfg without the priors
+struct VoteParams {
+    const float* boxes;      // [B, N, D] the pre-NMS rows
+    int B; int64_t N; int D, obj_idx, cls_start;
+    int C;                   // classes as NmsParams::C
+    int var;                 // BYOLO_VOTE_*
+    float sigma_t, iou_min, min_score, var_floor;
+    int ale_col, epi_col;    // first of the four variance columns, -1 = none
+    VoteGeom geom;           // read unless var == BYOLO_VOTE_NONE
+    const float* rows_in; const int32_t* kept; const int32_t* count; int cap;      // the NMS result, cap rows per image
+    float* rows_out;         // [B, cap, D], may be rows_in
+    int32_t* vote_n;         // [B, cap]
+    void* ws; size_t ws_bytes;
+};
+size_t box_vote_workspace_bytes(int B, int64_t N);
+hipError_t launch_box_vote(const VoteParams& p, hipStream_t st);
+
 // ---- ground-truth encoding and training loss (train_kernels.hip) ------------------------
 struct EncodeGtParams {
     const float* boxes;      // [B, max_boxes, 4]  ymin, xmin, ymax, xmax (image fractions)

@@ -226,6 +226,11 @@ void make_plan(byolo_t* h, int B, int T, bool inject) {
     p.boxes_off = p.arena;
     size_t o = p.boxes_off + align_up((size_t)B * h->n_boxes * h->row_len * sizeof(float), 256);
     p.nms_off = o; o += align_up(nms_workspace_bytes_ex(B, h->n_boxes, h->cfg.nms_mode, h->cfg.cls_cnt), 256);
+    p.vote_n_off = p.vote_off = o;
+    if (h->vote_on) {
+        o += align_up((size_t)B * nms_out_cap(h) * sizeof(int32_t), 256);
+        p.vote_off = o; o += align_up(box_vote_workspace_bytes(B, h->n_boxes), 256);
+    }
     p.stats_off = o; o += align_up((size_t)1024 * 2 * h->maxC * sizeof(double) + 2 * h->maxC * sizeof(float), 256);
     p.img_split_off = o; if (h->img_split) o += align_up((size_t)B * h->cfg.img_h * h->cfg.img_w * h->cfg.img_c * sizeof(float), 256);
     // launch geometry per step: tile configuration and the split-K of the last partial round (shape-only)

@@ -1,8 +1,11 @@
-// nms_box.h -- the box and the IoU that the NMS (tail_kernels.hip) and the evaluation matcher (eval_kernels.hip) share.
+// nms_box.h -- the box and the IoU that the NMS (tail_kernels.hip), the evaluation matcher (eval_kernels.hip) and variance
+// voting (box_vote.hip) share, and the score key / class of a row that the NMS and the voting agree on.
 // IoU is evaluated operation-for-operation as TensorFlow's IOU() in float32 with single rounding (__f*_rn: no FMA
 // contraction), std::min/std::max NaN semantics.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <cfloat>
 
 namespace byk {
 
@@ -33,6 +36,36 @@ __device__ __forceinline__ bool iou_gt(const NBox& i, const NBox& j, float thr) 
 __device__ __forceinline__ float iou_value(const NBox& i, const NBox& j) {
     if (i.area <= 0.f || j.area <= 0.f) return 0.f;
     return iou_of(i, j);
+}
+
+// ---- score and class of a row, as the NMS pipeline (tail_kernels.hip pc_*) and the vote stage (box_vote.hip) decide them ----
+__device__ __forceinline__ unsigned int score_key(float f) {
+    // ascending key == descending score; NaN and scores <= -FLT_MAX are not candidates
+    // (TF: `score > std::numeric_limits<float>::lowest()`), they sort last.
+    if (!(f > -FLT_MAX)) return 0xFFFFFFFFu;
+    unsigned int u = __float_as_uint(f);
+    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return ~u;
+}
+
+static constexpr int PC_NONE = 255;                          // class byte of a row that belongs to no class
+
+// The class of one row from its C class scores `t` (global memory or LDS) and its score: class c iff cls[c] > cls[k] for every
+// k != c -- a maximum attained twice or any NaN leaves no such c; a score that is no NMS candidate leaves none either.
+// One class: every candidate is a member and `t` is not read (the rows of BYOLO_NMS_AGNOSTIC need not have class columns).
+__device__ __forceinline__ int classify_row(const float* t, int C, float score) {
+    if (score_key(score) == 0xFFFFFFFFu) return PC_NONE;
+    if (C == 1) return 0;
+    float best = t[0];
+    int arg = 0;
+    bool uniq = true, nan = best != best;
+    for (int c = 1; c < C; ++c) {
+        const float v = t[c];
+        nan |= v != v;
+        if (v > best) { best = v; arg = c; uniq = true; }
+        else if (v == best) uniq = false;
+    }
+    return (uniq && !nan) ? arg : PC_NONE;
 }
 
 }  // namespace byk

@@ -382,15 +382,7 @@ hipError_t launch_decode(int kind, const DecodeParams& p, hipStream_t st) {
 // file); what follows first are the device functions its kernels share.  A sort key is 64 bits, (score key, row index):
 // ascending keys == (score descending, index ascending), the order TensorFlow's kernel visits the boxes in.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned int score_key(float f) {
-    // ascending key == descending score; NaN and scores <= -FLT_MAX are not candidates
-    // (TF: `score > std::numeric_limits<float>::lowest()`), they sort last.
-    if (!(f > -FLT_MAX)) return 0xFFFFFFFFu;
-    unsigned int u = __float_as_uint(f);
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return ~u;
-}
-
+// (score_key: nms_box.h -- the vote stage of box_vote.hip decides "candidate" with the same function)
 __device__ __forceinline__ void ce(unsigned long long& a, unsigned long long& b, bool up) {
     if ((a > b) == up) { const unsigned long long t = a; a = b; b = t; }
 }
@@ -625,7 +617,6 @@ __device__ __forceinline__ void scan_prefix(int max_out, const unsigned long lon
 //   pc_finish     kept rows of class 0, 1, ... back to back, zero fill, counts
 // An empty class costs one workgroup that reads its length and returns, in every stage.
 // ------------------------------------------------------------------------------------------------
-static constexpr int PC_NONE = 255;                          // class byte of a row that belongs to no class
 static_assert(BYOLO_MAX_CLASSES < PC_NONE, "the class digit of the per-class NMS key is one byte");
 static constexpr int PC_ROWS = 128;                          // output rows per pc_finish workgroup
 static constexpr int PC_TILE = 64;                           // rows per pc_classify_tiled workgroup
@@ -669,24 +660,7 @@ const int32_t* nms_class_counts_ptr(void* ws, int B, int64_t N, int C) {
 }
 size_t nms_workspace_bytes(int B, int64_t N, int C) { return pc_ws_layout(B, N, C, nullptr, nullptr); }   // grows with C
 
-// The class of one row from its C class scores `t` (global memory or LDS) and its score: class c iff cls[c] > cls[k] for every
-// k != c -- a maximum attained twice or any NaN leaves no such c; a score that is no NMS candidate leaves none either.
-// One class: every candidate is a member and `t` is not read (the rows of BYOLO_NMS_AGNOSTIC need not have class columns).
-__device__ __forceinline__ int classify_row(const float* t, int C, float score) {
-    if (score_key(score) == 0xFFFFFFFFu) return PC_NONE;
-    if (C == 1) return 0;
-    float best = t[0];
-    int arg = 0;
-    bool uniq = true, nan = best != best;
-    for (int c = 1; c < C; ++c) {
-        const float v = t[c];
-        nan |= v != v;
-        if (v > best) { best = v; arg = c; uniq = true; }
-        else if (v == best) uniq = false;
-    }
-    return (uniq && !nan) ? arg : PC_NONE;
-}
-
+// (classify_row: nms_box.h, shared with box_vote.hip)
 // Few classes (C <= PC_DIRECT_C): one lane per row reads its class scores where they are.
 __global__ __launch_bounds__(256) void pc_classify_kernel(const float* boxes, int64_t N, int D, int obj_idx, int cls_start,
                                                           int C, unsigned char* cls_all, int* hist_all) {

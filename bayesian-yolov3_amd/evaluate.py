@@ -13,6 +13,12 @@ Same config keys as `inference_*.py` (`data.file_pattern` names the labelled sha
 for the aleatoric and bayesian models; False: off).  `weights='synthetic'`,
 `seed` and `engine_options` as in the inference scripts.
 
+`box_vote` (True or a dict of settings, as `engine_options['box_vote']`): the model refines its kept boxes by variance voting
+(INTEGRATION.md "Variance voting") and the voted rows are scored.  With `box_vote_compare: True` the model runs with voting OFF,
+`Engine.box_vote` produces the voted rows beside the NMS rows of every batch, two evaluators score both, and metrics.json carries
+the two result dicts under 'nms' and 'box_vote' -- read AP at `iou_thresh` 0.75; at 0.5 little should move.  On voted rows the
+localisation part counts centres that left their cell as `n_outside`.
+
 `Model.run` -> `Evaluator.add` per batch (byolo/evaluate.py: one matching kernel per batch on the forward's stream); batches
 run one after the other (`Model.run` re-runs a batch that leaves the split-f16 range in fp32 by itself).  One process, one
 GPU: multi-GPU evaluation is out of scope.  Writes `<out_path>_<step>/metrics.json`: the dict of `Evaluator.finish`, the
@@ -53,6 +59,14 @@ def check_config(config, model='bayesian'):
     cfg.setdefault('eval_capacity', 1 << 20)
     cfg.setdefault('eval_batches', None)
     cfg.setdefault('localisation', None)
+    cfg.setdefault('box_vote', None)
+    cfg.setdefault('box_vote_compare', False)
+    if cfg['box_vote'] is not None and cfg['box_vote'] is not True and cfg['box_vote'] is not False and not isinstance(cfg['box_vote'], dict):
+        raise ValueError('box_vote is True or a dict of settings')
+    if cfg['box_vote_compare'] and not cfg['box_vote']:
+        raise ValueError('box_vote_compare: True needs box_vote')
+    if cfg['box_vote'] and not cfg['box_vote_compare']:              # the model votes in place; the comparison votes beside the NMS rows
+        cfg['engine_options'] = dict(cfg.get('engine_options', {}), box_vote=cfg['box_vote'])
     cfg.setdefault('seed', 0)
     cfg.setdefault('cpu_thread_cnt', 1)
     cfg.setdefault('T', 1)
@@ -87,15 +101,20 @@ def build_model(cfg):
     return m, checkpoint
 
 
-def score(model, feed, evaluator, seed=0, max_batches=None, points=None):
+def score(model, feed, evaluator, seed=0, max_batches=None, points=None, vote=None, vote_evaluator=None):
     """Model.run -> Evaluator.add over the batches of `feed` (the 'eval' split of lib_yolo.dataset_utils._Feed); returns the
-    number of images.  points: a list that receives (time, images so far) after every batch."""
+    number of images.  points: a list that receives (time, images so far) after every batch.  vote (settings) and
+    vote_evaluator: every batch's NMS rows are also voted (Engine.box_vote) and the voted rows scored by vote_evaluator."""
     images = 0
     for step, b in enumerate(feed):
         if max_batches is not None and step >= max_batches:
             break
-        res = model.run(b['img'], seed=seed + step, want_boxes=False)
+        res = model.run(b['img'], seed=seed + step, want_boxes=vote_evaluator is not None)
         evaluator.add(res['rows'], res['count'][:, 0], b['boxes'], b['labels'], b['counts'])
+        if vote_evaluator is not None:
+            voted = res.get('engine', model.engine).box_vote(res['boxes'], res, model.obj_idx, model.cls_start_idx,
+                                                             geom=model.det_layers, **({} if vote is True else dict(vote)))
+            vote_evaluator.add(voted['rows'], res['count'][:, 0], b['boxes'], b['labels'], b['counts'])
         images += int(b['img'].shape[0])
         if points is not None:
             points.append((time.perf_counter(), images))
@@ -128,17 +147,26 @@ def evaluate(config, model='bayesian'):
     m, checkpoint = build_model(cfg)
     out_path = '{}_{}'.format(cfg['out_path'], _inf.step_of(checkpoint))
     os.makedirs(out_path)                                 # like the inference scripts: refuses to overwrite an existing run
-    ev = Evaluator(m, iou_thresh=cfg['iou_thresh'], min_score=cfg['min_score'], capacity=cfg['eval_capacity'], loc=cfg['localisation'])
+    new_ev = lambda: Evaluator(m, iou_thresh=cfg['iou_thresh'], min_score=cfg['min_score'], capacity=cfg['eval_capacity'], loc=cfg['localisation'])
+    ev = new_ev()
+    ev_vote = new_ev() if cfg['box_vote_compare'] else None
     feed = dataset_utils._Feed(cfg, 'data', 'eval', device=m.engine.torch_device)
     try:
         t0 = time.time()
         points = []
-        images = score(m, feed, ev, seed=int(cfg['seed']), max_batches=cfg['eval_batches'], points=points)
+        images = score(m, feed, ev, seed=int(cfg['seed']), max_batches=cfg['eval_batches'], points=points, vote=cfg['box_vote'],
+                       vote_evaluator=ev_vote)
         metrics = ev.finish()
+        voted_metrics = ev_vote.finish() if ev_vote is not None else None
         loop_seconds = time.time() - t0
     finally:
         feed.close()
         ev.close()
+        if ev_vote is not None:
+            ev_vote.close()
+    if voted_metrics is not None:
+        for c, v in zip(metrics['classes'], voted_metrics['classes']):
+            logging.info('class {:3d}: AP at IoU {:.2f}: NMS rows {:.4f}, voted rows {:.4f}'.format(c['class'], cfg['iou_thresh'], c['ap'], v['ap']))
     for c in metrics['classes']:
         logging.info(class_line(c))
     for name, u in metrics['uncertainty'].items():
@@ -152,6 +180,9 @@ def evaluate(config, model='bayesian'):
     metrics.update(images=images, checkpoint=checkpoint, model=MODELS[cfg['model']], loop_seconds=loop_seconds,
                    steady_img_s=steady_rate(points),
                    config=json.loads(json.dumps(cfg, default=lambda x: str(x))))
+    if voted_metrics is not None:                         # both result dicts side by side; the figures logged above are the NMS rows'
+        metrics = dict({k: v for k, v in metrics.items() if k not in voted_metrics}, nms={k: metrics[k] for k in voted_metrics},
+                       box_vote=voted_metrics)
     with open(os.path.join(out_path, 'metrics.json'), 'w') as f:
         json.dump(metrics, f, indent=1)
     elapsed = int(time.time() - start)

@@ -77,6 +77,8 @@ class ModelBuilder:
         self.__scope = []
         self.__used = {}
         opts = dict(engine_options or {})
+        # 'box_vote': True | {settings}: variance voting behind the NMS (Engine.set_box_vote), switched on once the detection layers exist
+        self.__box_vote = opts.pop('box_vote', None)
         self.engine = Engine(img_size=shape[1:], cls_cnt=cls_cnt, **opts)
         self.T = 1
 
@@ -105,6 +107,8 @@ class ModelBuilder:
 
     def get_model(self, obj_idx, cls_start_idx):
         assert obj_idx < cls_start_idx
+        if self.__box_vote:
+            self.engine.set_box_vote(self.__box_vote)
         return Model(self.__layers, self.__det_layers, self.__cls_cnt, obj_idx, cls_start_idx, builder=self)
 
     def __update_layers(self, index, name, kind):

@@ -657,6 +657,52 @@ BYOLO_API size_t byolo_eval_loc_bytes(int64_t capacity);
 BYOLO_API int32_t byolo_eval_set_loc(byolo_eval_t* ev, const byolo_eval_loc_cfg* cfg, void* d_loc_table);
 BYOLO_API int32_t byolo_eval_loc_records(byolo_eval_t* ev, int32_t* h_dst, int64_t first, int64_t n_records, void* stream);
 
+/* ---- variance voting (He et al., CVPR 2019; no counterpart in the reference; csrc/box_vote.hip; INTEGRATION.md "Variance voting"
+ * has the definition in full, tests/_box_vote_ref.py restates it) -------------------------------------------------------------
+ * After the NMS every kept row's box is replaced by the weighted mean of the pre-NMS boxes of its class that overlap it:
+ *   voters of kept row k   rows i of the same image and the same class as the NMS decided it (agnostic: every NMS candidate is
+ *                          class 0; otherwise the strict unique maximum of the class scores) with score >= min_score, the NMS's
+ *                          float32 IoU(k, i) > iou_min, four finite box values and -- unless var == BYOLO_VOTE_NONE -- layer / prior
+ *                          ids that are finite, integral and inside the geometry table, and variances that are finite and >= 0
+ *   weights                p = exp(-(1 - iou)^2 / sigma_t), g_c = p / max(var_c, var_floor) per coordinate c of (cx, cy, w, h);
+ *                          var_c = the row's variance of the raw location value, taken to box units at the row's own cell:
+ *                          var_cx = v_x (fx (1 - fx) / lw)^2 with fx the centre's position inside its cell, var_w = v_w w^2
+ *                          (BYOLO_VOTE_NONE: g_c = p); all float64 on the float32 inputs
+ *   result                 c' = sum g_c c / sum g_c; columns 0 - 3 of the row become (cy' - h'/2, cx' - w'/2, cy' + h'/2, cx' + w'/2),
+ *                          rounded once to float32; d_vote_n [B, cap] int32 receives the number of voters (0 in the padding)
+ * Every other column and the padding rows are copied unchanged; d_kept / d_count are only read.  A kept row that is not among
+ * its own voters keeps its bits and gets vote_n 0.  The sums are taken in a fixed order (fixed lane assignment, fixed reduction
+ * tree): the result is deterministic and does not depend on the image's position in the batch.
+ * sigma_t and var_floor have starting values (0.02, 1e-8) that nobody has tuned on a real checkpoint.
+ * ale_col / epi_col: first of the four columns (x, y, w, h) of the aleatoric / epistemic variances in a row, -1 = the rows have
+ * none (aleatoric rows: 4 / -1, Bayesian rows: 8 / 4); BYOLO_VOTE_TOTAL adds the two in float64.
+ * byolo_box_vote: the stand-alone stage behind byolo_sort_nms (also: behind byolo_finish_tshard + byolo_sort_nms) on the same
+ * d_boxes / nms_mode / obj_idx / cls_start_idx (BYOLO_NMS_PER_CLASS: the handle's cls_cnt).  geom: lh / lw / n_priors and the id
+ * columns of byolo_eval_loc_cfg (the priors themselves are not read); NULL with BYOLO_VOTE_NONE.  d_rows_out may alias d_rows_in.
+ * d_ws >= byolo_box_vote_workspace_bytes(B, N) (0 for B < 1 or N < 1), 8-byte aligned.  Refused with BYOLO_ERR_ARG before anything is
+ * launched, the argument named in byolo_last_error: a wrong struct_bytes, sigma_t <= 0, iou_min < 0, var_floor <= 0 (or any of
+ * them NaN), an unknown var, a var whose columns are -1, columns outside the row, a geometry table beyond its limits; a
+ * workspace that is too small is BYOLO_ERR_NOMEM.
+ * byolo_set_box_vote(h, cfg): byolo_forward votes in place on d_rows right behind the NMS (cfg NULL: off, the default; with it
+ * off every output is what it was without this entry point).  ale_col / epi_col of cfg are ignored: the handle knows its rows
+ * (standard rows take BYOLO_VOTE_NONE only, aleatoric rows not BYOLO_VOTE_EPI / _TOTAL), and the geometry is that of its detection
+ * layers.  The stage's workspace is part of byolo_workspace_bytes while voting is on.  byolo_box_vote_counts: vote_n [B, cap] of
+ * the handle's LAST byolo_forward with d_rows, copied to d_vote_n on `stream`; BYOLO_ERR_STATE without one. */
+enum { BYOLO_VOTE_NONE = 0, BYOLO_VOTE_ALE = 1, BYOLO_VOTE_EPI = 2, BYOLO_VOTE_TOTAL = 3 };
+typedef struct byolo_vote_cfg {
+    int32_t struct_bytes;          /* sizeof(byolo_vote_cfg) of the caller's header: a mismatch is BYOLO_ERR_ARG */
+    int32_t var;                   /* BYOLO_VOTE_* */
+    float sigma_t, iou_min, min_score, var_floor;
+    int32_t ale_col, epi_col;
+} byolo_vote_cfg;
+BYOLO_API size_t byolo_box_vote_workspace_bytes(int32_t B, int64_t N);
+BYOLO_API int32_t byolo_box_vote(byolo_t* h, const float* d_boxes, int32_t B, int64_t N, int32_t D, int32_t obj_idx,
+                                 int32_t cls_start_idx, int32_t nms_mode, const byolo_vote_cfg* cfg, const byolo_eval_loc_cfg* geom,
+                                 const float* d_rows_in, const int32_t* d_kept, const int32_t* d_count, int32_t cap,
+                                 float* d_rows_out, int32_t* d_vote_n, void* d_ws, size_t ws_bytes, void* stream);
+BYOLO_API int32_t byolo_set_box_vote(byolo_t* h, const byolo_vote_cfg* cfg);
+BYOLO_API int32_t byolo_box_vote_counts(byolo_t* h, int32_t* d_vote_n, int32_t B, int32_t cap, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
