@@ -62,6 +62,14 @@ class EvalLocCfg(ctypes.Structure):
                [(n, (ctypes.c_float * EVAL_LOC_MAX_PRIORS) * EVAL_LOC_MAX_LAYERS) for n in ("prior_w", "prior_h")]
 
 
+EVAL_LADDER_MAX = 16                                                     # BYOLO_EVAL_LADDER_MAX
+
+
+class EvalLadderCfg(ctypes.Structure):
+    """include/byolo.h byolo_eval_ladder_cfg (field for field; tests/test_eval_ladder_cpu.py compares the two)."""
+    _fields_ = [("struct_bytes", ctypes.c_int32), ("n_thr", ctypes.c_int32), ("thresholds", ctypes.c_float * EVAL_LADDER_MAX)]
+
+
 class EvalSummary(ctypes.Structure):
     """include/byolo.h byolo_eval_summary."""
     _fields_ = [(n, ctypes.c_int32) for n in ("struct_bytes", "overflow", "record_words", "reserved")] + \
@@ -178,6 +186,9 @@ PROTOTYPES = {
     "byolo_eval_loc_bytes": (_sz, [_i64]),
     "byolo_eval_set_loc": (_i32, [_vp, _P(EvalLocCfg), _vp]),
     "byolo_eval_loc_records": (_i32, [_vp, _vp, _i64, _i64, _vp]),
+    "byolo_eval_ladder_bytes": (_sz, [_i64, _i32]),
+    "byolo_eval_set_ladder": (_i32, [_vp, _P(EvalLadderCfg), _vp]),
+    "byolo_eval_ladder_records": (_i32, [_vp, _vp, _i64, _i64, _vp]),
     "byolo_box_vote_workspace_bytes": (_sz, [_i32, _i64]),
     "byolo_box_vote": (_i32, [_vp, _vp, _i32, _i64, _i32, _i32, _i32, _i32, _P(VoteCfg), _P(EvalLocCfg), _vp, _vp, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
     "byolo_set_box_vote": (_i32, [_vp, _P(VoteCfg)]),

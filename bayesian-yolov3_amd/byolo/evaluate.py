@@ -9,7 +9,11 @@ host, every sum taken in ascending order so that the figures are reproducible to
 
 With localisation on (the two uncertainty variants), `add` launches a second kernel behind the first that takes every true
 positive and its matched box back to the raw location values at the detection's cell and prior and records the residuals;
-`finish` then says whether the predicted variances explain them (byolo/eval_loc.py)."""
+`finish` then says whether the predicted variances explain them (byolo/eval_loc.py).
+
+With a ladder of IoU thresholds (`iou_thresholds`), `add` launches one more kernel that matches every image once per threshold
+-- the matching differs per threshold, so the ladder cannot be derived from the records of one -- and `finish` adds AP and LAMR
+per threshold and their mean (AP50, AP75, AP over 0.50 : 0.05 : 0.95) from ONE sorted table."""
 import ctypes
 
 import numpy as np
@@ -95,15 +99,57 @@ def calibration(score, tp):
     return {'count': count.tolist(), 'tp': n_tp.tolist(), 'score_sum': ssum.tolist(), 'ece': float(ece) if n else float('nan')}
 
 
+def ladder_thresholds(iou_thresholds):
+    """The float32 thresholds of a ladder: None (off), 'coco' (0.50 : 0.05 : 0.95) or a sequence of 1 .. 16 values in [0, 1],
+    each rounded once to float32.  Raises ValueError on anything else."""
+    if iou_thresholds is None:
+        return None
+    if isinstance(iou_thresholds, str):
+        if iou_thresholds != 'coco':
+            raise ValueError("iou_thresholds is None, 'coco' or a sequence of thresholds, not %r" % (iou_thresholds,))
+        return [np.float32(round(0.5 + 0.05 * k, 2)) for k in range(10)]
+    try:
+        thr = [np.float32(t) for t in iou_thresholds]
+    except (TypeError, ValueError):
+        raise ValueError("iou_thresholds is None, 'coco' or a sequence of thresholds, not %r" % (iou_thresholds,))
+    if not 1 <= len(thr) <= _lib.EVAL_LADDER_MAX:
+        raise ValueError('iou_thresholds holds %d thresholds, not 1 .. %d' % (len(thr), _lib.EVAL_LADDER_MAX))
+    for t in thr:
+        if not (t >= 0 and t <= 1):                                # NaN fails both
+            raise ValueError('iou_thresholds: %r is NaN or outside [0, 1]' % (float(t),))
+    return thr
+
+
+def ladder_metrics(thresholds, cum_tp, cum_fp, class_start, class_gt, n_images):
+    """The 'ladder' part of the result from the cumulative integers [K, n] of the sorted table: per class AP and LAMR at every
+    threshold (`ap_lamr`) and the float64 mean of the APs in ascending k (NaN without ground truth); the outer mean runs over
+    the classes with ground truth, in ascending class."""
+    K = len(thresholds)
+    classes = []
+    for c in range(len(class_gt)):
+        a, b = int(class_start[c]), int(class_start[c + 1])
+        n_gt = int(class_gt[c])
+        pairs = [ap_lamr(cum_tp[k, a:b], cum_fp[k, a:b], n_gt, n_images) for k in range(K)]
+        ap = [p[0] for p in pairs]
+        classes.append({'class': c, 'n_gt': n_gt, 'n_tp': [int(cum_tp[k, b - 1]) if b > a else 0 for k in range(K)], 'ap': ap,
+                        'lamr': [p[1] for p in pairs], 'ap_mean': float(_seq_sum(ap) / np.float64(K)) if n_gt > 0 else float('nan')})
+    with_gt = [c['ap_mean'] for c in classes if c['n_gt'] > 0]
+    return {'iou_thresholds': [float(t) for t in thresholds], 'classes': classes,
+            'ap_mean': float(_seq_sum(with_gt) / np.float64(len(with_gt))) if with_gt else float('nan')}
+
+
 class Evaluator:
     """Evaluator(model_or_layout): a lib_yolo Model, or a dict with row_len, obj_idx, cls_start_idx, cls_cnt and optionally
     unc_cols ({name: column}; default: the variant's table above).  capacity: records the device table holds (28 + 4 per
     uncertainty column bytes each); detections beyond it are dropped and `finish` raises ByoloError(ERR_NOMEM).
     loc: the localisation residuals (24 more bytes per record).  None: on for a Model of the two uncertainty variants, with the
     geometry of model.det_layers, and for a dict layout with a 'det_layers' entry ([(lh, lw, [(prior_h, prior_w), ...]), ...] or
-    DetLayer objects) whose rows carry the ids and variances; off otherwise.  True where it cannot be: ValueError."""
+    DetLayer objects) whose rows carry the ids and variances; off otherwise.  True where it cannot be: ValueError.
+    iou_thresholds: the ladder (`ladder_thresholds`: None, 'coco' or 1 .. 16 values); 4 * (1 + K) more bytes per record.  The
+    main table, the loc table and every other key of the result are the same with and without it."""
 
-    def __init__(self, model_or_layout, iou_thresh=0.5, min_score=0.0, capacity=1 << 20, device=None, table=None, loc=None, loc_table=None):
+    def __init__(self, model_or_layout, iou_thresh=0.5, min_score=0.0, capacity=1 << 20, device=None, table=None, loc=None, loc_table=None,
+                 iou_thresholds=None, ladder_table=None):
         import torch
         lay = model_or_layout
         if not isinstance(lay, dict):
@@ -138,6 +184,27 @@ class Evaluator:
         self.reset()
         self.loc_table = None
         self._setup_loc(lay, loc, loc_table)
+        self.iou_thresholds, self.ladder_table = ladder_thresholds(iou_thresholds), None
+        if self.iou_thresholds is not None:
+            self._setup_ladder(ladder_table)
+
+    def _setup_ladder(self, ladder_table):
+        import torch
+        K = len(self.iou_thresholds)
+        words = 1 + K
+        assert lib.byolo_eval_ladder_bytes(self.capacity, K) == 4 * words * self.capacity
+        # `ladder_table`: a caller's int32 tensor, as `table`
+        self.ladder_table = torch.empty((self.capacity, words), dtype=torch.int32, device=self.device) if ladder_table is None else ladder_table
+        assert self.ladder_table.is_cuda and self.ladder_table.dtype == torch.int32 and self.ladder_table.is_contiguous() and \
+            self.ladder_table.numel() >= self.capacity * words
+        self._check(self._set_ladder(self.iou_thresholds, self.ladder_table.data_ptr()))
+
+    def _set_ladder(self, thresholds, ptr, struct_bytes=None):
+        """byolo_eval_set_ladder; returns its code."""
+        cfg = _lib.EvalLadderCfg(struct_bytes=ctypes.sizeof(_lib.EvalLadderCfg) if struct_bytes is None else struct_bytes, n_thr=len(thresholds))
+        for k, t in enumerate(thresholds[:_lib.EVAL_LADDER_MAX]):
+            cfg.thresholds[k] = float(t)
+        return lib.byolo_eval_set_ladder(self._h, ctypes.byref(cfg), ctypes.c_void_p(ptr))
 
     def _setup_loc(self, lay, loc, loc_table):
         """Decides whether the residuals are recorded, and hands the geometry table and the loc table to the library."""
@@ -271,6 +338,15 @@ class Evaluator:
             fpv = unc32[:, u][fin[:, u] & ~is_tp[:, 0]].contiguous()
             two_u[u] = torch.searchsorted(tpv, fpv, right=False).sum() + torch.searchsorted(tpv, fpv, right=True).sum()
         loc_dev = self._loc_device(t, tf) if self.loc_table is not None else None
+        lad = None
+        if self.ladder_table is not None:                      # the same order serves every threshold
+            K = len(self.iou_thresholds)
+            lw = self.ladder_table.view(-1)[:n * (1 + K)].view(n, 1 + K)[:, 0][order]
+            ltp = ((lw[None, :] >> torch.arange(K, device=self.device, dtype=torch.int32)[:, None]) & 1).to(torch.int64)
+            lctp, lcfp = torch.cumsum(ltp, 1), torch.cumsum(1 - ltp, 1)
+            zk = torch.zeros((K, 1), dtype=torch.int64, device=self.device)
+            first = start[:-1][seg]
+            lad = torch.stack([lctp - torch.cat([zk, lctp], 1)[:, first], lcfp - torch.cat([zk, lcfp], 1)[:, first]])
         host = torch.cat([start.to(torch.float64), ustat.reshape(-1), usum.reshape(-1)]).cpu().numpy()      # the host wait
         two_u_h = two_u.cpu().numpy()
         ints = torch.stack([cum_tp, cum_fp]).cpu().numpy()
@@ -301,6 +377,10 @@ class Evaluator:
                'classes': classes, 'uncertainty': uncertainty}
         if loc_dev is not None:
             out['localisation'] = self._loc_host(loc_dev)
+        if lad is not None:
+            lad_h = lad.cpu().numpy()
+            self.sorted['ladder_cum_tp'], self.sorted['ladder_cum_fp'] = lad_h[0], lad_h[1]
+            out['ladder'] = ladder_metrics(self.iou_thresholds, lad_h[0], lad_h[1], start_h, [int(v) for v in class_gt], self.n_images)
         return out
 
     # ---- localisation: residuals against predicted variances ---------------------------------------------------------------
@@ -368,6 +448,20 @@ class Evaluator:
         out = np.zeros(n, dtype=eval_loc.LOC_DTYPE)
         if n:
             self._check(lib.byolo_eval_loc_records(self._h, out.ctypes.data_as(ctypes.c_void_p), 0, n, self._stream()))
+        return out
+
+    def ladder_records(self):
+        """The ladder table as an [n, 1 + K] int32 array, one row per record of `records()`: word 0 bit k = true positive at
+        iou_thresholds[k], word 1 + k the box matched there or -1."""
+        if self.ladder_table is None:
+            raise RuntimeError('no ladder of IoU thresholds is set for this evaluator')
+        summ = _lib.EvalSummary(struct_bytes=ctypes.sizeof(_lib.EvalSummary))
+        class_gt = (ctypes.c_int64 * self.cls_cnt)()
+        lib.byolo_eval_finish(self._h, ctypes.byref(summ), class_gt, self.cls_cnt, self._stream())
+        n = int(summ.n_records)
+        out = np.zeros((n, 1 + len(self.iou_thresholds)), dtype=np.int32)
+        if n:
+            self._check(lib.byolo_eval_ladder_records(self._h, out.ctypes.data_as(ctypes.c_void_p), 0, n, self._stream()))
         return out
 
     def records(self, sorted=False):

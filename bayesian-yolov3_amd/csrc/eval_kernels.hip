@@ -24,6 +24,14 @@
 // A true positive's box and its matched ground-truth box are taken back to the raw location values t_x, t_y, t_w, t_h at the
 // detection's own cell and prior (the row's layer_id / prior_id columns), in float64, one operation per line as
 // tests/_eval_loc_ref.py restates them; the residuals t(ground truth) - t(detection) go to a second table, six words per record.
+//
+// eval_ladder_kernel (byolo_eval_set_ladder): behind the match kernel on the same stream, one workgroup per image and one wave64
+// per threshold.  The matching depends on the threshold (a box a detection fails to claim stays open for a later one), so every
+// threshold gets the greedy pass of step 5 of its own, with its own matched set; the ground truth and the keys are staged and
+// sorted ONCE by all waves together, and the start of the image's records is recomputed exactly as the match kernel computed it
+// (the running offset this launch reads is the word the match kernel does not write).  The true-positive bits of a detection
+// meet in the upper half of its sorted key, which the passes no longer read; the records go to a third table, 1 + n_thr words
+// each, at the record's own index.  Neither the main table nor the device state is written.
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
@@ -205,6 +213,156 @@ __global__ __launch_bounds__(64) void eval_match_kernel(const EvalArgs a) {
     }
 }
 
+// ---- the ladder: the matching at several IoU thresholds ---------------------------------------------------------------------
+static constexpr int LAD_MAX = BYOLO_EVAL_LADDER_MAX;
+
+struct LadderArgs {
+    EvalArgs e;                                                  // table is not written, state is read only
+    int32_t* ladder;
+    int32_t n_thr;
+    float thr[LAD_MAX];
+};
+
+struct LadderLds {
+    EvalLds L;
+    float thr[LAD_MAX];
+    int part[LAD_MAX];                                           // per wave: survivors counted in the images before this one
+    int ns;
+};
+
+__global__ __launch_bounds__(64 * LAD_MAX) void eval_ladder_kernel(const LadderArgs la) {
+    __shared__ LadderLds S;
+    EvalLds& L = S.L;
+    const EvalArgs& a = la.e;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nthreads = 64 * la.n_thr;
+    const unsigned long long lt_mask = (1ull << lane) - 1ull;
+
+    // 1 -- ground truth (the counters are the match kernel's)
+    const int G = ev_clampi(a.gt_counts[b], 0, a.gmax);
+    for (int g = tid; g < G; g += nthreads) {
+        const float* q = a.gt_boxes + ((size_t)b * a.gmax + g) * 4;
+        const NBox o = make_box(q[0], q[1], q[2], q[3]);
+        int lab = a.gt_labels[(size_t)b * a.gmax + g];
+        if (lab < 0 || lab >= a.C) lab = -1;
+        L.y0[g] = o.y0; L.x0[g] = o.x0; L.y1[g] = o.y1; L.x1[g] = o.x1; L.ar[g] = o.area; L.label[g] = lab;
+    }
+    if (tid < la.n_thr) S.thr[tid] = la.thr[tid];
+    if (tid == 0) S.ns = 0;
+    __syncthreads();
+
+    // 2 -- keys of the surviving rows: the waves take turns at 64 rows; the keys are distinct, so their order before the sort
+    // does not matter
+    const int n = ev_clampi(a.count[(size_t)b * a.count_stride], 0, a.cap);
+    const float* rows = a.rows + (size_t)b * a.cap * a.D;
+    for (int i0 = wave << 6; i0 < n; i0 += nthreads) {
+        const int i = i0 + lane;
+        float s = 0.f; int c = 0;
+        const bool ok = i < n && ev_score(rows + (size_t)i * a.D, a, s, c);
+        const unsigned long long m = __ballot(ok);
+        int at = 0;
+        if (lane == 0 && m) at = atomicAdd(&S.ns, __popcll(m));  // LDS
+        at = __shfl(at, 0);
+        if (ok) {
+            if (s == 0.f) s = 0.f;                               // -0 orders as +0
+            unsigned int u = __float_as_uint(s);
+            u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+            L.key[at + __popcll(m & lt_mask)] = ((unsigned long long)(~u) << 32) | ((unsigned int)i << 8) | (unsigned int)c;
+        }
+    }
+
+    // 3 -- survivors of the images before this one, shared among the waves
+    int part = 0;
+    for (int pb = 0; pb < b; ++pb) {
+        const int pn = ev_clampi(a.count[(size_t)pb * a.count_stride], 0, a.cap);
+        const float* pr = a.rows + (size_t)pb * a.cap * a.D;
+        for (int i0 = wave << 6; i0 < pn; i0 += nthreads) {
+            const int i = i0 + lane;
+            float s; int c;
+            part += __popcll(__ballot(i < pn && ev_score(pr + (size_t)i * a.D, a, s, c)));
+        }
+    }
+    if (lane == 0) S.part[wave] = part;
+    __syncthreads();
+    const int ns = S.ns;
+    int before = 0;
+    for (int w = 0; w < la.n_thr; ++w) before += S.part[w];
+    const long long base = (long long)a.state[ST_TOTAL0 + a.parity] + before;
+
+    // 4 -- sort: descending score, then ascending row
+    int P2 = 64;
+    while (P2 < ns) P2 <<= 1;
+    for (int i = ns + tid; i < P2; i += nthreads) L.key[i] = ~0ull;
+    __syncthreads();
+    for (int k = 2; k <= P2; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = tid; t < P2 / 2; t += nthreads) {
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+                ev_ce(L.key[i], L.key[i + j], (i & k) == 0);
+            }
+            __syncthreads();
+        }
+    // the score half of a key has done its work: it collects the detection's true-positive bits
+    unsigned int* kw = reinterpret_cast<unsigned int*>(L.key);   // little endian: word 2 d is (row, class), word 2 d + 1 the score
+    for (int d = tid; d < ns; d += nthreads) kw[2 * d + 1] = 0u;
+    __syncthreads();
+
+    // 5 -- this wave's threshold: the pass of eval_match_kernel
+    const float thr = S.thr[wave];
+    const int rec_words = 1 + la.n_thr;
+    const int passes = (G + 63) >> 6;
+    unsigned int matched = 0;
+    for (int d0 = 0; d0 < ns; d0 += 64) {
+        const int d = d0 + lane;
+        const bool have = d < ns;
+        const unsigned int lo = have ? kw[2 * d] : 0u;
+        const int my_row = (int)(lo >> 8), my_cls = (int)(lo & 255u);
+        const float* r = rows + (size_t)my_row * a.D;
+        NBox me = make_box(0.f, 0.f, 0.f, 0.f);
+        if (have) me = make_box(r[0], r[1], r[2], r[3]);
+        int my_tp = 0, my_gt = -1;
+        const int nd = min(64, ns - d0);
+        for (int j = 0; j < nd; ++j) {
+            NBox o;
+            o.y0 = __shfl(me.y0, j); o.x0 = __shfl(me.x0, j); o.y1 = __shfl(me.y1, j); o.x1 = __shfl(me.x1, j);
+            o.area = __shfl(me.area, j);
+            const int oc = __shfl(my_cls, j);
+            float bi = -1.f;
+            int bg = 0x7fffffff;
+            for (int p = 0; p < passes; ++p) {
+                const int g = (p << 6) + lane;
+                if (g < G && L.label[g] == oc && !((matched >> p) & 1u)) {
+                    NBox q; q.y0 = L.y0[g]; q.x0 = L.x0[g]; q.y1 = L.y1[g]; q.x1 = L.x1[g]; q.area = L.ar[g];
+                    float v = iou_value(o, q);
+                    if (!(v >= 0.f)) v = 0.f;
+                    if (v > bi) { bi = v; bg = g; }
+                }
+            }
+#pragma unroll
+            for (int sft = 1; sft < 64; sft <<= 1) {
+                const float vi = __shfl_xor(bi, sft);
+                const int vg = __shfl_xor(bg, sft);
+                if (vi > bi || (vi == bi && vg < bg)) { bi = vi; bg = vg; }
+            }
+            const bool tp = bg != 0x7fffffff && bi >= thr;
+            if (tp && (bg & 63) == lane) matched |= 1u << (bg >> 6);
+            if (lane == j) { my_tp = tp ? 1 : 0; my_gt = tp ? bg : -1; }
+        }
+        const long long pos = base + d;
+        if (have) {
+            if (my_tp) atomicOr(&kw[2 * d + 1], 1u << wave);     // LDS
+            if (pos < a.capacity) la.ladder[(size_t)pos * rec_words + 1 + wave] = my_gt;
+        }
+    }
+    __syncthreads();
+
+    // 6 -- word 0: the bits of every threshold
+    for (int d = tid; d < ns; d += nthreads) {
+        const long long pos = base + d;
+        if (pos < a.capacity) la.ladder[(size_t)pos * rec_words] = (int32_t)kw[2 * d + 1];
+    }
+}
+
 // ---- localisation residuals --------------------------------------------------------------------------------------------------
 static constexpr int LOC_WORDS = BYOLO_EVAL_LOC_WORDS;
 static constexpr int LOC_L = BYOLO_EVAL_LOC_MAX_LAYERS, LOC_P = BYOLO_EVAL_LOC_MAX_PRIORS;
@@ -308,6 +466,8 @@ struct byolo_eval {
     int64_t images = 0;
     byolo_eval_loc_cfg loc;                                     // valid while d_loc is set (byolo_eval_set_loc)
     int32_t* d_loc = nullptr;
+    byolo_eval_ladder_cfg ladder;                               // valid while d_ladder is set (byolo_eval_set_ladder)
+    int32_t* d_ladder = nullptr;
     std::string err;
 };
 
@@ -398,6 +558,16 @@ extern "C" int32_t byolo_eval_add(byolo_eval_t* ev, const float* d_rows, int32_t
         hipLaunchKernelGGL(byk::eval_loc_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), l);
         EVHIP(ev, hipGetLastError());
     }
+    if (ev->d_ladder) {                                         // reads the offset word the match kernel leaves alone
+        byk::LadderArgs la;
+        la.e = a;
+        la.e.table = nullptr;
+        la.ladder = ev->d_ladder;
+        la.n_thr = ev->ladder.n_thr;
+        for (int k = 0; k < byk::LAD_MAX; ++k) la.thr[k] = k < la.n_thr ? ev->ladder.thresholds[k] : 0.f;
+        hipLaunchKernelGGL(byk::eval_ladder_kernel, dim3(B), dim3(64 * la.n_thr), 0, static_cast<hipStream_t>(stream), la);
+        EVHIP(ev, hipGetLastError());
+    }
     ev->launches += 1;
     ev->images += B;
     return BYOLO_OK;
@@ -477,6 +647,42 @@ extern "C" int32_t byolo_eval_loc_records(byolo_eval_t* ev, int32_t* h_dst, int6
     if (!h_dst) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_loc_records: null argument");
     hipStream_t s = static_cast<hipStream_t>(stream);
     EVHIP(ev, hipMemcpyAsync(h_dst, ev->d_loc + (size_t)first * byk::LOC_WORDS, sizeof(int32_t) * byk::LOC_WORDS * (size_t)n_records, hipMemcpyDeviceToHost, s));
+    EVHIP(ev, hipStreamSynchronize(s));
+    return BYOLO_OK;
+}
+
+// ---- the ladder --------------------------------------------------------------------------------------------------------------
+extern "C" size_t byolo_eval_ladder_bytes(int64_t capacity, int32_t n_thr) {
+    if (capacity < 1 || capacity > 0x7fffffffll || n_thr < 1 || n_thr > BYOLO_EVAL_LADDER_MAX) return 0;
+    return sizeof(int32_t) * (size_t)(1 + n_thr) * (size_t)capacity;
+}
+
+extern "C" int32_t byolo_eval_set_ladder(byolo_eval_t* ev, const byolo_eval_ladder_cfg* cfg, void* d_ladder_table) {
+    if (!ev) return efail(nullptr, BYOLO_ERR_ARG, "byolo_eval_set_ladder: null handle");
+    if (ev->launches) return efail(ev, BYOLO_ERR_STATE, "byolo_eval_set_ladder: records were added since the last byolo_eval_reset");
+    if (!d_ladder_table) { ev->d_ladder = nullptr; return BYOLO_OK; }
+    if (!cfg) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_set_ladder: null cfg");
+    if (cfg->struct_bytes != (int32_t)sizeof(byolo_eval_ladder_cfg))
+        return efail(ev, BYOLO_ERR_ARG, "byolo_eval_set_ladder: struct_bytes %d, this library's byolo_eval_ladder_cfg has %d", cfg->struct_bytes, (int)sizeof(byolo_eval_ladder_cfg));
+    if (cfg->n_thr < 1 || cfg->n_thr > BYOLO_EVAL_LADDER_MAX) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_set_ladder: n_thr outside 1 .. %d", BYOLO_EVAL_LADDER_MAX);
+    for (int k = 0; k < cfg->n_thr; ++k)
+        if (!(cfg->thresholds[k] >= 0.f && cfg->thresholds[k] <= 1.f))
+            return efail(ev, BYOLO_ERR_ARG, "byolo_eval_set_ladder: threshold %d is NaN or outside [0, 1]", k);
+    if (reinterpret_cast<uintptr_t>(d_ladder_table) & 3) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_set_ladder: d_ladder_table must be 4-byte aligned");
+    ev->ladder = *cfg;
+    ev->d_ladder = static_cast<int32_t*>(d_ladder_table);
+    return BYOLO_OK;
+}
+
+extern "C" int32_t byolo_eval_ladder_records(byolo_eval_t* ev, int32_t* h_dst, int64_t first, int64_t n_records, void* stream) {
+    if (!ev) return efail(nullptr, BYOLO_ERR_ARG, "byolo_eval_ladder_records: null handle");
+    if (!ev->d_ladder) return efail(ev, BYOLO_ERR_STATE, "byolo_eval_ladder_records: no ladder table is set (byolo_eval_set_ladder)");
+    if (first < 0 || n_records < 0 || first + n_records > ev->capacity) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_ladder_records: records outside the table");
+    if (n_records == 0) return BYOLO_OK;
+    if (!h_dst) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_ladder_records: null argument");
+    const size_t rw = (size_t)(1 + ev->ladder.n_thr);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    EVHIP(ev, hipMemcpyAsync(h_dst, ev->d_ladder + (size_t)first * rw, sizeof(int32_t) * rw * (size_t)n_records, hipMemcpyDeviceToHost, s));
     EVHIP(ev, hipStreamSynchronize(s));
     return BYOLO_OK;
 }

@@ -19,6 +19,16 @@ for the aleatoric and bayesian models; False: off).  `weights='synthetic'`,
 the two result dicts under 'nms' and 'box_vote' -- read AP at `iou_thresh` 0.75; at 0.5 little should move.  On voted rows the
 localisation part counts centres that left their cell as `n_outside`.
 
+`iou_thresholds` ('coco' = 0.50 : 0.05 : 0.95, or a list of 1 .. 16 thresholds; absent: off, metrics.json is what it was): every
+batch is also matched at each of these thresholds in the same pass (one more kernel per batch; the forward runs once), and the
+result gains 'ladder': AP and LAMR per class and threshold and their mean -- AP50, AP75 and the averaged AP of the detection
+benchmarks.  With `box_vote_compare` both evaluators carry the ladder and the two are logged side by side per threshold.
+
+`box_vote_sweep` (a list of at most 8 settings dicts; needs `box_vote_compare: True`): the model still runs ONCE per batch with
+voting off; every entry gets its own `Engine.box_vote` call on that batch's rows and its own evaluator, metrics.json gains
+'box_vote_sweep': [{'settings': ..., **result}, ...] and a table of mean AP per entry is logged -- the tool for choosing `sigma_t`
+and `var_floor`.
+
 `Model.run` -> `Evaluator.add` per batch (byolo/evaluate.py: one matching kernel per batch on the forward's stream); batches
 run one after the other (`Model.run` re-runs a batch that leaves the split-f16 range in fp32 by itself).  One process, one
 GPU: multi-GPU evaluation is out of scope.  Writes `<out_path>_<step>/metrics.json`: the dict of `Evaluator.finish`, the
@@ -33,6 +43,8 @@ import time
 import numpy as np
 
 MODELS = {'standard': 'yolov3', 'aleatoric': 'yolov3_aleatoric', 'bayesian': 'bayesian_yolov3_aleatoric'}
+VOTE_SETTINGS = ('var', 'sigma_t', 'iou_min', 'min_score', 'var_floor')      # byolo.engine.Engine.box_vote
+MAX_SWEEP = 8
 REQUIRED = ('full_img_size', 'cls_cnt', 'batch_size', 'crop', 'priors', 'implicit_background_class', 'data', 'out_path')
 
 
@@ -67,6 +79,26 @@ def check_config(config, model='bayesian'):
         raise ValueError('box_vote_compare: True needs box_vote')
     if cfg['box_vote'] and not cfg['box_vote_compare']:              # the model votes in place; the comparison votes beside the NMS rows
         cfg['engine_options'] = dict(cfg.get('engine_options', {}), box_vote=cfg['box_vote'])
+    from byolo.evaluate import ladder_thresholds
+    ladder_thresholds(cfg.get('iou_thresholds'))                     # ValueError on a bad ladder; both keys stay absent when absent
+    if cfg.get('box_vote_sweep') is not None:
+        sweep = cfg['box_vote_sweep']
+        if not cfg['box_vote_compare']:
+            raise ValueError('box_vote_sweep needs box_vote_compare: True')
+        if not isinstance(sweep, (list, tuple)) or not 1 <= len(sweep) <= MAX_SWEEP:
+            raise ValueError('box_vote_sweep is a list of 1 .. {} settings dicts'.format(MAX_SWEEP))
+        for k, entry in enumerate(sweep):
+            if not isinstance(entry, dict):
+                raise ValueError('box_vote_sweep[{}] is not a dict of settings'.format(k))
+            unknown = sorted(set(entry) - set(VOTE_SETTINGS))
+            if unknown:
+                raise ValueError('box_vote_sweep[{}]: unknown settings {}; known: {}'.format(k, unknown, list(VOTE_SETTINGS)))
+            for name, v in entry.items():
+                if name == 'var' and v is not None and not isinstance(v, str):
+                    raise ValueError('box_vote_sweep[{}]: var must be a string, not {!r}'.format(k, v))
+                if name != 'var' and (isinstance(v, bool) or not isinstance(v, (int, float)) or v != v):
+                    raise ValueError('box_vote_sweep[{}]: {} must be a number, not {!r}'.format(k, name, v))
+        cfg['box_vote_sweep'] = [dict(e) for e in sweep]
     cfg.setdefault('seed', 0)
     cfg.setdefault('cpu_thread_cnt', 1)
     cfg.setdefault('T', 1)
@@ -101,20 +133,21 @@ def build_model(cfg):
     return m, checkpoint
 
 
-def score(model, feed, evaluator, seed=0, max_batches=None, points=None, vote=None, vote_evaluator=None):
+def score(model, feed, evaluator, seed=0, max_batches=None, points=None, vote=None, vote_evaluator=None, sweep=()):
     """Model.run -> Evaluator.add over the batches of `feed` (the 'eval' split of lib_yolo.dataset_utils._Feed); returns the
     number of images.  points: a list that receives (time, images so far) after every batch.  vote (settings) and
-    vote_evaluator: every batch's NMS rows are also voted (Engine.box_vote) and the voted rows scored by vote_evaluator."""
+    vote_evaluator: every batch's NMS rows are also voted (Engine.box_vote) and the voted rows scored by vote_evaluator.
+    sweep: [(settings, evaluator)], each voted and scored the same way on the same rows of the one forward."""
     images = 0
     for step, b in enumerate(feed):
         if max_batches is not None and step >= max_batches:
             break
         res = model.run(b['img'], seed=seed + step, want_boxes=vote_evaluator is not None)
         evaluator.add(res['rows'], res['count'][:, 0], b['boxes'], b['labels'], b['counts'])
-        if vote_evaluator is not None:
+        for settings, vev in ([(vote, vote_evaluator)] if vote_evaluator is not None else []) + list(sweep):
             voted = res.get('engine', model.engine).box_vote(res['boxes'], res, model.obj_idx, model.cls_start_idx,
-                                                             geom=model.det_layers, **({} if vote is True else dict(vote)))
-            vote_evaluator.add(voted['rows'], res['count'][:, 0], b['boxes'], b['labels'], b['counts'])
+                                                             geom=model.det_layers, **({} if settings is True else dict(settings)))
+            vev.add(voted['rows'], res['count'][:, 0], b['boxes'], b['labels'], b['counts'])
         images += int(b['img'].shape[0])
         if points is not None:
             points.append((time.perf_counter(), images))
@@ -135,6 +168,44 @@ def class_line(c):
         c['class'], c['n_gt'], c['n_det'], c['n_tp'], c['ap'], c['lamr'], c['ece'])
 
 
+def _ap_at(lad_class, thresholds, t):
+    """The class's AP at threshold t of the ladder, or None when the ladder does not hold it."""
+    hits = [k for k, v in enumerate(thresholds) if np.float32(v) == np.float32(t)]
+    return lad_class['ap'][hits[0]] if hits else None
+
+
+def ladder_lines(lad, voted=None):
+    """Log lines of a 'ladder' result: per class AP50 / AP75 (where the ladder holds them) and the mean; with `voted` (the voted
+    rows' ladder) the two side by side per threshold."""
+    thr = lad['iou_thresholds']
+    lines = []
+    for c in lad['classes']:
+        named = ['AP{:02d} {:.4f}'.format(int(round(t * 100)), _ap_at(c, thr, t)) for t in (0.5, 0.75) if _ap_at(c, thr, t) is not None]
+        lines.append('class {:3d}: '.format(c['class']) + ', '.join(named + ['mean AP over {} thresholds {:.4f}'.format(len(thr), c['ap_mean'])]))
+    lines.append('mean AP over the classes with ground truth: {:.4f}'.format(lad['ap_mean']))
+    if voted is not None:
+        for c, v in zip(lad['classes'], voted['classes']):
+            for k, t in enumerate(thr):
+                lines.append('class {:3d}: AP at IoU {:.2f}: NMS rows {:.4f}, voted rows {:.4f}'.format(c['class'], t, c['ap'][k], v['ap'][k]))
+            lines.append('class {:3d}: mean AP: NMS rows {:.4f}, voted rows {:.4f}'.format(c['class'], c['ap_mean'], v['ap_mean']))
+        lines.append('mean AP: NMS rows {:.4f}, voted rows {:.4f}'.format(lad['ap_mean'], voted['ap_mean']))
+    return lines
+
+
+def sweep_lines(sweep, results, iou_thresh):
+    """The table of a vote sweep: per entry its settings and the mean AP (of the ladder when there is one, else AP at iou_thresh
+    averaged over the classes with ground truth)."""
+    lines = []
+    for k, (settings, r) in enumerate(zip(sweep, results)):
+        if 'ladder' in r:
+            what, ap = 'mean AP', r['ladder']['ap_mean']
+        else:
+            aps = [c['ap'] for c in r['classes'] if c['n_gt'] > 0]
+            what, ap = 'AP at IoU {:.2f}'.format(iou_thresh), float(np.cumsum(aps)[-1] / len(aps)) if aps else float('nan')
+        lines.append('box_vote_sweep[{}]: {} {:.4f}  {}'.format(k, what, ap, json.dumps(settings, sort_keys=True)))
+    return lines
+
+
 def evaluate(config, model='bayesian'):
     """Scores the checkpoint and writes <out_path>_<step>/metrics.json; returns its content."""
     from byolo import inference as _inf
@@ -147,23 +218,28 @@ def evaluate(config, model='bayesian'):
     m, checkpoint = build_model(cfg)
     out_path = '{}_{}'.format(cfg['out_path'], _inf.step_of(checkpoint))
     os.makedirs(out_path)                                 # like the inference scripts: refuses to overwrite an existing run
-    new_ev = lambda: Evaluator(m, iou_thresh=cfg['iou_thresh'], min_score=cfg['min_score'], capacity=cfg['eval_capacity'], loc=cfg['localisation'])
+    new_ev = lambda: Evaluator(m, iou_thresh=cfg['iou_thresh'], min_score=cfg['min_score'], capacity=cfg['eval_capacity'], loc=cfg['localisation'],
+                               iou_thresholds=cfg.get('iou_thresholds'))
     ev = new_ev()
     ev_vote = new_ev() if cfg['box_vote_compare'] else None
+    sweep = [(settings, new_ev()) for settings in (cfg.get('box_vote_sweep') or [])]
     feed = dataset_utils._Feed(cfg, 'data', 'eval', device=m.engine.torch_device)
     try:
         t0 = time.time()
         points = []
         images = score(m, feed, ev, seed=int(cfg['seed']), max_batches=cfg['eval_batches'], points=points, vote=cfg['box_vote'],
-                       vote_evaluator=ev_vote)
+                       vote_evaluator=ev_vote, sweep=sweep)
         metrics = ev.finish()
         voted_metrics = ev_vote.finish() if ev_vote is not None else None
+        sweep_metrics = [e.finish() for _, e in sweep]
         loop_seconds = time.time() - t0
     finally:
         feed.close()
         ev.close()
         if ev_vote is not None:
             ev_vote.close()
+        for _, e in sweep:
+            e.close()
     if voted_metrics is not None:
         for c, v in zip(metrics['classes'], voted_metrics['classes']):
             logging.info('class {:3d}: AP at IoU {:.2f}: NMS rows {:.4f}, voted rows {:.4f}'.format(c['class'], cfg['iou_thresh'], c['ap'], v['ap']))
@@ -173,6 +249,11 @@ def evaluate(config, model='bayesian'):
         logging.info('{:16s}: mean over TP {:.6g} ({} finite, {} not), over FP {:.6g} ({} finite, {} not), AUROC FP over TP {:.4f}'.format(
             name, u['tp']['mean'], u['tp']['finite'], u['tp']['nonfinite'], u['fp']['mean'], u['fp']['finite'], u['fp']['nonfinite'],
             u['auroc_fp']))
+    if 'ladder' in metrics:
+        for line in ladder_lines(metrics['ladder'], voted_metrics['ladder'] if voted_metrics is not None else None):
+            logging.info(line)
+    for line in sweep_lines(cfg.get('box_vote_sweep') or [], sweep_metrics, cfg['iou_thresh']):
+        logging.info(line)
     if 'localisation' in metrics:
         from byolo import eval_loc
         for line in eval_loc.log_lines(metrics['localisation']):
@@ -183,6 +264,8 @@ def evaluate(config, model='bayesian'):
     if voted_metrics is not None:                         # both result dicts side by side; the figures logged above are the NMS rows'
         metrics = dict({k: v for k, v in metrics.items() if k not in voted_metrics}, nms={k: metrics[k] for k in voted_metrics},
                        box_vote=voted_metrics)
+    if sweep:
+        metrics['box_vote_sweep'] = [dict(r, settings=settings) for (settings, _), r in zip(sweep, sweep_metrics)]
     with open(os.path.join(out_path, 'metrics.json'), 'w') as f:
         json.dump(metrics, f, indent=1)
     elapsed = int(time.time() - start)

@@ -199,7 +199,9 @@ class EvalHook:
     to an inference model (built once, at the evaluation size: the centre crop when config['crop'], else the full frame) and
     config['eval_batches'] (default 4) batches of the 'val' shards are scored through the feed's 'eval' split
     (byolo/evaluate.py).  Logs '{step} eval  >>> class c: LAMR .., AP ..; ...' and, for the models whose rows carry
-    variances, '{step} evloc >>> ale x: rmse .., sigma_scale .., nll ..; ...'.  Reads the trainer, never writes it; the
+    variances, '{step} evloc >>> ale x: rmse .., sigma_scale .., nll ..; ...'.  config['eval_iou_thresholds'] (absent: off;
+    'coco' or a list, as byolo.evaluate.Evaluator's iou_thresholds) adds '{step} evlad >>> class c: AP@0.50 .., ..., mean ..'.
+    Reads the trainer, never writes it; the
     'eval' split draws no random number, so the training and validation streams are what they are without the hook."""
 
     def __init__(self, model_cls, config):
@@ -226,7 +228,7 @@ class EvalHook:
         if self.model is None:
             self._build()
         trainer.apply_to(self.model)
-        ev = Evaluator(self.model, capacity=int(self.config.get('eval_capacity', 1 << 18)))
+        ev = Evaluator(self.model, capacity=int(self.config.get('eval_capacity', 1 << 18)), iou_thresholds=self.config.get('eval_iou_thresholds'))
         feed = dataset_utils._Feed(self.config, 'val', 'eval', device=self.model.engine.torch_device)
         try:
             for k, b in enumerate(feed):
@@ -245,6 +247,11 @@ class EvalHook:
             logging.info('{:5d} evloc >>> '.format(step) + '; '.join(
                 '{} {}: n {}, rmse {:.4f}, sigma_scale {:.4f}, nll {:.4f}'.format(kind, c, s['n'], s['rmse'], s['sigma_scale'], s['nll'])
                 for kind in ('ale', 'epi', 'total') if kind in loc for c, s in loc[kind].items()))
+        lad = self.last.get('ladder')
+        if lad is not None:
+            logging.info('{:5d} evlad >>> '.format(step) + '; '.join(
+                'class {}: '.format(c['class']) + ', '.join('AP@{:.2f} {:.4f}'.format(t, a) for t, a in zip(lad['iou_thresholds'], c['ap'])) +
+                ', mean {:.4f}'.format(c['ap_mean']) for c in lad['classes']) + '; mean AP {:.4f}'.format(lad['ap_mean']))
         return self.last
 
     def close(self):

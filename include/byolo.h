@@ -657,6 +657,30 @@ BYOLO_API size_t byolo_eval_loc_bytes(int64_t capacity);
 BYOLO_API int32_t byolo_eval_set_loc(byolo_eval_t* ev, const byolo_eval_loc_cfg* cfg, void* d_loc_table);
 BYOLO_API int32_t byolo_eval_loc_records(byolo_eval_t* ev, int32_t* h_dst, int64_t first, int64_t n_records, void* stream);
 
+/* The ladder: the matching at several IoU thresholds in one pass (AP50, AP75, AP averaged over 0.50 : 0.05 : 0.95;
+ * INTEGRATION.md "Evaluation").  The matching DIFFERS per threshold -- a box that a detection fails to claim stays open for a
+ * later one -- so the ladder is not derivable from the records of one threshold.  With a ladder table set, byolo_eval_add
+ * launches one more kernel behind the matching on the same stream (no host wait) that matches every image of the batch once per
+ * threshold, each threshold with its own matched set and otherwise by exactly the rule above (same survivors, same visiting
+ * order, same float32 IoU, `iou >= thresholds[k]` compared in float32), and writes, for every record of the batch and at the
+ * record's index, 1 + n_thr 32-bit words:
+ *   0       int32 bit k is set iff the detection is a true positive at thresholds[k]
+ *   1 + k   int32 the box it matched at thresholds[k], or -1
+ * Thresholds need not be sorted or distinct.  d_ladder_table holds byolo_eval_ladder_bytes(capacity, n_thr) bytes, caller-owned,
+ * 4-byte aligned; NULL switches the ladder off.  Nothing is written at or beyond `capacity` records.  byolo_eval_set_ladder is
+ * refused with BYOLO_ERR_STATE between the first byolo_eval_add and the next byolo_eval_reset, and with BYOLO_ERR_ARG for a wrong
+ * struct_bytes, n_thr outside 1 .. BYOLO_EVAL_LADDER_MAX, a threshold that is NaN or outside [0, 1] and a misaligned table.
+ * The main records, the device state, the loc table and -- with no ladder set -- the launches are the same with and without it. */
+#define BYOLO_EVAL_LADDER_MAX 16
+typedef struct byolo_eval_ladder_cfg {
+    int32_t struct_bytes;          /* sizeof(byolo_eval_ladder_cfg) of the caller's header: a mismatch is BYOLO_ERR_ARG */
+    int32_t n_thr;
+    float thresholds[BYOLO_EVAL_LADDER_MAX];
+} byolo_eval_ladder_cfg;
+BYOLO_API size_t byolo_eval_ladder_bytes(int64_t capacity, int32_t n_thr);
+BYOLO_API int32_t byolo_eval_set_ladder(byolo_eval_t* ev, const byolo_eval_ladder_cfg* cfg, void* d_ladder_table);
+BYOLO_API int32_t byolo_eval_ladder_records(byolo_eval_t* ev, int32_t* h_dst, int64_t first, int64_t n_records, void* stream);
+
 /* ---- variance voting (He et al., CVPR 2019; no counterpart in the reference; csrc/box_vote.hip; INTEGRATION.md "Variance voting"
  * has the definition in full, tests/_box_vote_ref.py restates it) -------------------------------------------------------------
  * After the NMS every kept row's box is replaced by the weighted mean of the pre-NMS boxes of its class that overlap it:
