@@ -168,10 +168,7 @@ class Evaluator:
         self.record_words = _lib.EVAL_RECORD_HEAD + len(self.unc_cols)
         self.dtype = record_dtype(len(self.unc_cols))
         self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
-        # `table`: a caller's int32 tensor to hold the records (tests put a guard region behind it)
-        self.table = torch.empty((self.capacity, self.record_words), dtype=torch.int32, device=self.device) if table is None else table
-        assert self.table.is_cuda and self.table.dtype == torch.int32 and self.table.is_contiguous() and \
-            self.table.numel() >= self.capacity * self.record_words
+        self.table = self._side_table(table, self.record_words)
         self._state = torch.zeros(lib.byolo_eval_state_bytes(self.cls_cnt) // 4, dtype=torch.int32, device=self.device)
         cfg = _lib.EvalCfg(struct_bytes=ctypes.sizeof(_lib.EvalCfg), row_len=self.row_len, obj_idx=self.obj_idx, cls_start_idx=self.cls_start_idx,
                            cls_cnt=self.cls_cnt, n_unc=len(self.unc_cols), iou_thresh=self.iou_thresh, min_score=self.min_score)
@@ -188,15 +185,17 @@ class Evaluator:
         if self.iou_thresholds is not None:
             self._setup_ladder(ladder_table)
 
-    def _setup_ladder(self, ladder_table):
+    def _side_table(self, given, words):
+        """A table of `words` int32 words per record: a new one, or the caller's tensor (tests put a guard region behind it)."""
         import torch
+        t = torch.empty((self.capacity, words), dtype=torch.int32, device=self.device) if given is None else given
+        assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= self.capacity * words
+        return t
+
+    def _setup_ladder(self, ladder_table):
         K = len(self.iou_thresholds)
-        words = 1 + K
-        assert lib.byolo_eval_ladder_bytes(self.capacity, K) == 4 * words * self.capacity
-        # `ladder_table`: a caller's int32 tensor, as `table`
-        self.ladder_table = torch.empty((self.capacity, words), dtype=torch.int32, device=self.device) if ladder_table is None else ladder_table
-        assert self.ladder_table.is_cuda and self.ladder_table.dtype == torch.int32 and self.ladder_table.is_contiguous() and \
-            self.ladder_table.numel() >= self.capacity * words
+        assert lib.byolo_eval_ladder_bytes(self.capacity, K) == 4 * (1 + K) * self.capacity
+        self.ladder_table = self._side_table(ladder_table, 1 + K)
         self._check(self._set_ladder(self.iou_thresholds, self.ladder_table.data_ptr()))
 
     def _set_ladder(self, thresholds, ptr, struct_bytes=None):
@@ -208,7 +207,6 @@ class Evaluator:
 
     def _setup_loc(self, lay, loc, loc_table):
         """Decides whether the residuals are recorded, and hands the geometry table and the loc table to the library."""
-        import torch
         ids = lay.get('id_cols')
         try:
             variant = variant_of(self.row_len, self.cls_cnt)
@@ -233,12 +231,8 @@ class Evaluator:
         if why is not None:
             raise ValueError('loc=True: ' + why)
         cfg = eval_loc.loc_cfg(ids[0], ids[1], eval_loc.geometry(lay['det_layers']))
-        words = _lib.EVAL_LOC_WORDS
-        assert lib.byolo_eval_loc_bytes(self.capacity) == 4 * words * self.capacity
-        # `loc_table`: a caller's int32 tensor, as `table`
-        self.loc_table = torch.empty((self.capacity, words), dtype=torch.int32, device=self.device) if loc_table is None else loc_table
-        assert self.loc_table.is_cuda and self.loc_table.dtype == torch.int32 and self.loc_table.is_contiguous() and \
-            self.loc_table.numel() >= self.capacity * words
+        assert lib.byolo_eval_loc_bytes(self.capacity) == 4 * _lib.EVAL_LOC_WORDS * self.capacity
+        self.loc_table = self._side_table(loc_table, _lib.EVAL_LOC_WORDS)
         self._check(lib.byolo_eval_set_loc(self._h, ctypes.byref(cfg), ctypes.c_void_p(self.loc_table.data_ptr())))
 
     def _check(self, rc, handle=True):
@@ -296,14 +290,25 @@ class Evaluator:
         self._check(lib.byolo_eval_add(self._h, p(rows), B, cap, p(count), int(count.stride(0)), p(gb), p(gl), p(gc), gmax, self._stream()))
         self.sorted = None
 
+    def _summary(self):
+        """byolo_eval_finish (waits for the stream): (its code, the summary, the eligible boxes per class)."""
+        summ = _lib.EvalSummary(struct_bytes=ctypes.sizeof(_lib.EvalSummary))
+        class_gt = (ctypes.c_int64 * self.cls_cnt)()
+        rc = lib.byolo_eval_finish(self._h, ctypes.byref(summ), class_gt, self.cls_cnt, self._stream())
+        return rc, summ, class_gt
+
+    def _fetch(self, fn, out, n):
+        """Fills `out` with the first n records of the table that `fn` copies; overflow: the tables are still valid."""
+        if n:
+            self._check(fn(self._h, out.ctypes.data_as(ctypes.c_void_p), 0, n, self._stream()))
+        return out
+
     # ---- the dataset-level reduction ------------------------------------------------------------------------------------
     def finish(self):
         """The metrics of everything added since reset() (waits for the stream).  Raises ByoloError(ERR_NOMEM) when detections
         were dropped for lack of capacity; `records()` then still returns the table's records."""
         import torch
-        summ = _lib.EvalSummary(struct_bytes=ctypes.sizeof(_lib.EvalSummary))
-        class_gt = (ctypes.c_int64 * self.cls_cnt)()
-        rc = lib.byolo_eval_finish(self._h, ctypes.byref(summ), class_gt, self.cls_cnt, self._stream())
+        rc, summ, class_gt = self._summary()
         self.n_records, self.n_images = int(summ.n_records), int(summ.n_images)
         self._check(rc)
         n, C = self.n_records, self.cls_cnt
@@ -441,28 +446,16 @@ class Evaluator:
         """The loc table as a numpy structured array (`eval_loc.LOC_DTYPE`), one entry per record of `records()`."""
         if self.loc_table is None:
             raise RuntimeError('localisation is off for this evaluator')
-        summ = _lib.EvalSummary(struct_bytes=ctypes.sizeof(_lib.EvalSummary))
-        class_gt = (ctypes.c_int64 * self.cls_cnt)()
-        lib.byolo_eval_finish(self._h, ctypes.byref(summ), class_gt, self.cls_cnt, self._stream())
-        n = int(summ.n_records)
-        out = np.zeros(n, dtype=eval_loc.LOC_DTYPE)
-        if n:
-            self._check(lib.byolo_eval_loc_records(self._h, out.ctypes.data_as(ctypes.c_void_p), 0, n, self._stream()))
-        return out
+        n = int(self._summary()[1].n_records)
+        return self._fetch(lib.byolo_eval_loc_records, np.zeros(n, dtype=eval_loc.LOC_DTYPE), n)
 
     def ladder_records(self):
         """The ladder table as an [n, 1 + K] int32 array, one row per record of `records()`: word 0 bit k = true positive at
         iou_thresholds[k], word 1 + k the box matched there or -1."""
         if self.ladder_table is None:
             raise RuntimeError('no ladder of IoU thresholds is set for this evaluator')
-        summ = _lib.EvalSummary(struct_bytes=ctypes.sizeof(_lib.EvalSummary))
-        class_gt = (ctypes.c_int64 * self.cls_cnt)()
-        lib.byolo_eval_finish(self._h, ctypes.byref(summ), class_gt, self.cls_cnt, self._stream())
-        n = int(summ.n_records)
-        out = np.zeros((n, 1 + len(self.iou_thresholds)), dtype=np.int32)
-        if n:
-            self._check(lib.byolo_eval_ladder_records(self._h, out.ctypes.data_as(ctypes.c_void_p), 0, n, self._stream()))
-        return out
+        n = int(self._summary()[1].n_records)
+        return self._fetch(lib.byolo_eval_ladder_records, np.zeros((n, 1 + len(self.iou_thresholds)), dtype=np.int32), n)
 
     def records(self, sorted=False):
         """The record table as a numpy structured array (`record_dtype`): in the order the kernel wrote it, or
@@ -472,18 +465,10 @@ class Evaluator:
             if self.sorted is None:
                 raise RuntimeError('records(sorted=True) needs finish() first')
             return self.sorted
-        summ = _lib.EvalSummary(struct_bytes=ctypes.sizeof(_lib.EvalSummary))
-        class_gt = (ctypes.c_int64 * self.cls_cnt)()
-        lib.byolo_eval_finish(self._h, ctypes.byref(summ), class_gt, self.cls_cnt, self._stream())   # overflow: the table is still valid
-        n = int(summ.n_records)
-        out = np.zeros(n, dtype=self.dtype)
-        if n:
-            self._check(lib.byolo_eval_records(self._h, out.ctypes.data_as(ctypes.c_void_p), 0, n, self._stream()))
-        return out
+        n = int(self._summary()[1].n_records)
+        return self._fetch(lib.byolo_eval_records, np.zeros(n, dtype=self.dtype), n)
 
     def class_gt(self):
         """Eligible ground-truth boxes per class and the image count so far (waits for the stream)."""
-        summ = _lib.EvalSummary(struct_bytes=ctypes.sizeof(_lib.EvalSummary))
-        class_gt = (ctypes.c_int64 * self.cls_cnt)()
-        lib.byolo_eval_finish(self._h, ctypes.byref(summ), class_gt, self.cls_cnt, self._stream())
+        _, summ, class_gt = self._summary()
         return [int(v) for v in class_gt], int(summ.n_images)

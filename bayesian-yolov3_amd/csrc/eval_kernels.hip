@@ -7,31 +7,38 @@
 // not-yet-matched ground-truth box OF ITS CLASS with the largest IoU (ties: lower box index); a true positive iff that IoU
 // >= iou_thresh, and only then is the box marked.  IoU is nms_box.h's: the float32 operations of the NMS, in the same order.
 //
-// eval_match_kernel: one wave64 per image.
-//   1  the image's ground truth -> LDS as NBox + label (label outside [0, C) = not eligible), class counters += eligible
-//   2  rows -> (score, row, class) keys of the surviving rows in LDS (ballot compaction); class = first index of the largest
-//      class score, score = obj * cls[class] (one float32 multiply), dropped when NaN or below min_score
+// The matching of one image is written once, as stages over the (tid, nthreads) of the image's workgroup:
+//   1  the image's ground truth -> LDS as NBox + label (label outside [0, C) = not eligible)
+//   2  rows -> (score, row, class) keys of the surviving rows in LDS: the waves take turns at 64 rows, an LDS counter hands each
+//      ballot its slots; class = first index of the largest class score, score = obj * cls[class] (one float32 multiply),
+//      dropped when NaN or below min_score.  The keys are distinct, so their order before the sort does not matter
 //   3  where the image's records start: the device's running offset + the survivors of the images before it in the batch,
-//      which every wave counts for itself (a few thousand rows; cheaper than a second launch or a wait between workgroups)
+//      which every workgroup counts for itself, each wave a share summed through LDS (a few thousand rows; cheaper than a
+//      second launch or a wait between workgroups)
 //   4  bitonic sort of the keys (LDS)
-//   5  64 detections per round, one per lane (box, class, uncertainty columns in registers); the round walks them in order:
-//      the detection is broadcast, every lane scores the ground-truth boxes lane, lane + 64, ... against it, a cross-lane
-//      arg-max picks the box; the matched set is one bit per pass in a per-lane word
-//   6  every lane writes its detection's record
+//   5  the greedy pass of ONE wave at one threshold: 64 detections per round, one per lane (box and class in registers); the
+//      round walks them in order: the detection is broadcast, every lane scores the ground-truth boxes lane, lane + 64, ...
+//      against it, a cross-lane arg-max picks the box; the matched set is one bit per pass in a per-lane word
+//   6  the writer, which is what the two kernels below differ in
 // Float arithmetic here is restated operation by operation (tests/_eval_ref.py): built with -ffp-contract=off.
+//
+// eval_match_kernel: one wave64 per image, the threshold is the evaluator's iou_thresh.  Stage 1 also adds the eligible boxes to
+// the class counters and the image to the image counter, the last image of the launch leaves the next launch's offset behind
+// stage 3, and every lane writes its detection's record with the uncertainty columns; a record beyond the capacity sets the
+// sticky overflow word instead.
+//
+// eval_ladder_kernel (byolo_eval_set_ladder): behind the match kernel on the same stream, one workgroup per image and one wave64
+// per threshold.  The matching depends on the threshold (a box a detection fails to claim stays open for a later one), so every
+// threshold gets the pass of stage 5 of its own, with its own matched set; stages 1 - 4 are run ONCE by all waves together, and
+// stage 3 arrives at the start the match kernel used (the running offset this launch reads is the word the match kernel does
+// not write).  The true-positive bits of a detection meet in the upper half of its sorted key, which the passes no longer read;
+// the records go to a third table, 1 + n_thr words each, at the record's own index.  Neither the main table nor the device
+// state is written.
 //
 // eval_loc_kernel (byolo_eval_set_loc): right behind the match kernel on the same stream, one thread per record of the launch.
 // A true positive's box and its matched ground-truth box are taken back to the raw location values t_x, t_y, t_w, t_h at the
 // detection's own cell and prior (the row's layer_id / prior_id columns), in float64, one operation per line as
 // tests/_eval_loc_ref.py restates them; the residuals t(ground truth) - t(detection) go to a second table, six words per record.
-//
-// eval_ladder_kernel (byolo_eval_set_ladder): behind the match kernel on the same stream, one workgroup per image and one wave64
-// per threshold.  The matching depends on the threshold (a box a detection fails to claim stays open for a later one), so every
-// threshold gets the greedy pass of step 5 of its own, with its own matched set; the ground truth and the keys are staged and
-// sorted ONCE by all waves together, and the start of the image's records is recomputed exactly as the match kernel computed it
-// (the running offset this launch reads is the word the match kernel does not write).  The true-positive bits of a detection
-// meet in the upper half of its sorted key, which the passes no longer read; the records go to a third table, 1 + n_thr words
-// each, at the record's own index.  Neither the main table nor the device state is written.
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
@@ -48,6 +55,7 @@ static constexpr int EV_MAX_DET = 4096;                      // rows per image (
 static constexpr int EV_MAX_GT = BYOLO_EVAL_MAX_GT;          // ground-truth boxes per image staged in LDS
 static constexpr int EV_HEAD = BYOLO_EVAL_RECORD_HEAD;       // record words before the uncertainty columns
 static constexpr int EV_MAX_UNC = BYOLO_EVAL_MAX_UNC;
+static constexpr int LAD_MAX = BYOLO_EVAL_LADDER_MAX;        // thresholds of a ladder = waves of its workgroup
 // device state (int32 words): the running record offset twice (a launch reads one and its last image writes the other: the
 // images of a launch run concurrently), the sticky overflow word, the image counter, then one counter per class
 enum { ST_TOTAL0 = 0, ST_TOTAL1 = 1, ST_OVERFLOW = 2, ST_IMAGES = 3, ST_CLASS0 = 8 };
@@ -65,6 +73,15 @@ struct EvalLds {
     unsigned long long key[EV_MAX_DET];
     float y0[EV_MAX_GT], x0[EV_MAX_GT], y1[EV_MAX_GT], x1[EV_MAX_GT], ar[EV_MAX_GT];
     int label[EV_MAX_GT];
+    int part[LAD_MAX];                                       // per wave: survivors counted in the images before this one
+    int ns;                                                  // the image's survivors so far: hands out the key slots
+};
+
+// what stages 1 - 4 leave for the pass and the writers, besides the LDS
+struct EvalImage {
+    const float* rows;
+    int G, ns;                                               // ground-truth boxes staged, keys sorted
+    long long base;                                          // index of the image's first record
 };
 
 // class (first index of the maximum, as np.argmax: a NaN class score wins and makes the score NaN) and score of a row;
@@ -89,81 +106,101 @@ __device__ __forceinline__ void ev_ce(unsigned long long& x, unsigned long long&
     if ((x > y) == up) { const unsigned long long t = x; x = y; y = t; }
 }
 
-__global__ __launch_bounds__(64) void eval_match_kernel(const EvalArgs a) {
-    __shared__ EvalLds L;
-    const int b = blockIdx.x, lane = threadIdx.x;
-    const unsigned long long lt_mask = (1ull << lane) - 1ull;
+// the halves of sorted key d (little endian): word 0 is (row << 8 | class), word 1 the score
+__device__ __forceinline__ unsigned int& ev_key_word(EvalLds& L, int d, int half) {
+    return reinterpret_cast<unsigned int*>(L.key)[2 * d + half];
+}
+
+// the survivors among the n rows at `rows`, 64 at a time and this wave's share of them: visit(i, ok, ballot, score, class)
+template <class Visit>
+__device__ __forceinline__ void ev_survivors(const float* rows, int n, const EvalArgs& a, int tid, int nthreads, Visit visit) {
+    for (int i0 = tid & ~63; i0 < n; i0 += nthreads) {
+        const int i = i0 + (tid & 63);
+        float s = 0.f; int c = 0;
+        const bool ok = i < n && ev_score(rows + (size_t)i * a.D, a, s, c);
+        visit(i, ok, __ballot(ok), s, c);
+    }
+}
+
+// stages 1 - 4 for image b.  MAIN: the instantiation that owns the device state's counters and the next launch's offset
+template <bool MAIN>
+__device__ __forceinline__ EvalImage ev_stage_and_sort(EvalLds& L, const EvalArgs& a, int b, int tid, int nthreads) {
+    const int lane = tid & 63, wave = tid >> 6;
+    EvalImage im;
 
     // 1 -- ground truth
-    const int G = ev_clampi(a.gt_counts[b], 0, a.gmax);
-    for (int g = lane; g < G; g += 64) {
+    im.G = ev_clampi(a.gt_counts[b], 0, a.gmax);
+    for (int g = tid; g < im.G; g += nthreads) {
         const float* q = a.gt_boxes + ((size_t)b * a.gmax + g) * 4;
         const NBox o = make_box(q[0], q[1], q[2], q[3]);
         int lab = a.gt_labels[(size_t)b * a.gmax + g];
         if (lab < 0 || lab >= a.C) lab = -1;
         L.y0[g] = o.y0; L.x0[g] = o.x0; L.y1[g] = o.y1; L.x1[g] = o.x1; L.ar[g] = o.area; L.label[g] = lab;
-        if (lab >= 0) atomicAdd(&a.state[ST_CLASS0 + lab], 1);
+        if (MAIN && lab >= 0) atomicAdd(&a.state[ST_CLASS0 + lab], 1);
     }
-    if (lane == 0) atomicAdd(&a.state[ST_IMAGES], 1);
+    if (MAIN && tid == 0) atomicAdd(&a.state[ST_IMAGES], 1);
+    if (tid == 0) L.ns = 0;
+    __syncthreads();
 
     // 2 -- keys of the surviving rows
     const int n = ev_clampi(a.count[(size_t)b * a.count_stride], 0, a.cap);
-    const float* rows = a.rows + (size_t)b * a.cap * a.D;
-    int ns = 0;
-    for (int i0 = 0; i0 < n; i0 += 64) {
-        const int i = i0 + lane;
-        float s = 0.f; int c = 0;
-        const bool ok = i < n && ev_score(rows + (size_t)i * a.D, a, s, c);
-        const unsigned long long m = __ballot(ok);
+    im.rows = a.rows + (size_t)b * a.cap * a.D;
+    ev_survivors(im.rows, n, a, tid, nthreads, [&](int i, bool ok, unsigned long long m, float s, int c) {
+        int at = 0;
+        if (lane == 0 && m) at = atomicAdd(&L.ns, __popcll(m));  // LDS
+        at = __shfl(at, 0);
         if (ok) {
             if (s == 0.f) s = 0.f;                           // -0 orders as +0
             unsigned int u = __float_as_uint(s);
             u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // ascending in u = ascending in s
-            L.key[ns + __popcll(m & lt_mask)] = ((unsigned long long)(~u) << 32) | ((unsigned int)i << 8) | (unsigned int)c;
+            L.key[at + __popcll(m & ((1ull << lane) - 1ull))] = ((unsigned long long)(~u) << 32) | ((unsigned int)i << 8) | (unsigned int)c;
         }
-        ns += __popcll(m);
-    }
+    });
 
     // 3 -- survivors of the images before this one
+    int part = 0;
+    for (int pb = 0; pb < b; ++pb)
+        ev_survivors(a.rows + (size_t)pb * a.cap * a.D, ev_clampi(a.count[(size_t)pb * a.count_stride], 0, a.cap), a, tid, nthreads,
+                     [&](int, bool, unsigned long long m, float, int) { part += __popcll(m); });
+    if (lane == 0) L.part[wave] = part;
+    __syncthreads();
+    im.ns = L.ns;
     int before = 0;
-    for (int pb = 0; pb < b; ++pb) {
-        const int pn = ev_clampi(a.count[(size_t)pb * a.count_stride], 0, a.cap);
-        const float* pr = a.rows + (size_t)pb * a.cap * a.D;
-        for (int i0 = 0; i0 < pn; i0 += 64) {
-            const int i = i0 + lane;
-            float s; int c;
-            before += __popcll(__ballot(i < pn && ev_score(pr + (size_t)i * a.D, a, s, c)));
-        }
-    }
-    const long long base = (long long)a.state[ST_TOTAL0 + a.parity] + before;
-    if (b == a.B - 1 && lane == 0) {
-        const long long t = base + ns;
+    for (int w = 0; w < (nthreads >> 6); ++w) before += L.part[w];
+    im.base = (long long)a.state[ST_TOTAL0 + a.parity] + before;
+    if (MAIN && b == a.B - 1 && tid == 0) {
+        const long long t = im.base + im.ns;
         a.state[ST_TOTAL0 + (a.parity ^ 1)] = t > 0x7fffffffll ? 0x7fffffff : (int)t;
     }
 
     // 4 -- sort: descending score, then ascending row
     int P2 = 64;
-    while (P2 < ns) P2 <<= 1;
-    for (int i = ns + lane; i < P2; i += 64) L.key[i] = ~0ull;
+    while (P2 < im.ns) P2 <<= 1;
+    for (int i = im.ns + tid; i < P2; i += nthreads) L.key[i] = ~0ull;
     __syncthreads();
     for (int k = 2; k <= P2; k <<= 1)
         for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = lane; t < P2 / 2; t += 64) {
+            for (int t = tid; t < P2 / 2; t += nthreads) {
                 const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
                 ev_ce(L.key[i], L.key[i + j], (i & k) == 0);
             }
             __syncthreads();
         }
+    return im;
+}
 
-    // 5, 6 -- match and write
+// 5 -- the pass of one wave at threshold thr; every detection's lane hands write(d, row, class, its row, tp, gt, best IoU)
+template <class Write>
+__device__ __forceinline__ void ev_greedy_pass(EvalLds& L, const EvalArgs& a, const EvalImage& im, float thr, int lane, Write write) {
+    const int G = im.G, ns = im.ns;
     const int passes = (G + 63) >> 6;                        // <= EV_MAX_GT / 64 = 16 bits of `matched`
     unsigned int matched = 0;                                // bit p: ground-truth box p * 64 + lane is taken
     for (int d0 = 0; d0 < ns; d0 += 64) {
         const int d = d0 + lane;
         const bool have = d < ns;
-        const unsigned int lo = have ? (unsigned int)L.key[d] : 0u;
+        const unsigned int lo = have ? ev_key_word(L, d, 0) : 0u;
         const int my_row = (int)(lo >> 8), my_cls = (int)(lo & 255u);
-        const float* r = rows + (size_t)my_row * a.D;
+        const float* r = im.rows + (size_t)my_row * a.D;
         NBox me = make_box(0.f, 0.f, 0.f, 0.f);
         if (have) me = make_box(r[0], r[1], r[2], r[3]);
         int my_tp = 0, my_gt = -1;
@@ -192,30 +229,36 @@ __global__ __launch_bounds__(64) void eval_match_kernel(const EvalArgs a) {
                 if (vi > bi || (vi == bi && vg < bg)) { bi = vi; bg = vg; }
             }
             const bool any = bg != 0x7fffffff;
-            const bool tp = any && bi >= a.iou_thresh;
+            const bool tp = any && bi >= thr;
             if (tp && (bg & 63) == lane) matched |= 1u << (bg >> 6);
             if (lane == j) { my_tp = tp ? 1 : 0; my_gt = tp ? bg : -1; my_iou = any ? bi : 0.f; }
         }
-        const long long pos = base + d;
-        if (have) {
-            if (pos < a.capacity) {
-                int32_t* w = a.table + (size_t)pos * (EV_HEAD + a.n_unc);
-                w[0] = a.img_base + b; w[1] = my_row; w[2] = my_cls;
-                w[3] = __float_as_int(__fmul_rn(r[a.obj_idx], r[a.cls_start + my_cls]));
-                w[4] = my_tp; w[5] = my_gt; w[6] = __float_as_int(my_iou);
-#pragma unroll
-                for (int u = 0; u < EV_MAX_UNC; ++u)
-                    if (u < a.n_unc) w[EV_HEAD + u] = __float_as_int(r[a.unc[u]]);
-            } else {
-                a.state[ST_OVERFLOW] = 1;                    // sticky: nothing clears it but byolo_eval_reset
-            }
-        }
+        if (have) write(d, my_row, my_cls, r, my_tp, my_gt, my_iou);
     }
 }
 
-// ---- the ladder: the matching at several IoU thresholds ---------------------------------------------------------------------
-static constexpr int LAD_MAX = BYOLO_EVAL_LADDER_MAX;
+__global__ __launch_bounds__(64) void eval_match_kernel(const EvalArgs a) {
+    __shared__ EvalLds L;
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const EvalImage im = ev_stage_and_sort<true>(L, a, b, lane, 64);
+    // 6 -- the record
+    ev_greedy_pass(L, a, im, a.iou_thresh, lane, [&](int d, int row, int cls, const float* r, int tp, int gt, float iou) {
+        const long long pos = im.base + d;
+        if (pos < a.capacity) {
+            int32_t* w = a.table + (size_t)pos * (EV_HEAD + a.n_unc);
+            w[0] = a.img_base + b; w[1] = row; w[2] = cls;
+            w[3] = __float_as_int(__fmul_rn(r[a.obj_idx], r[a.cls_start + cls]));
+            w[4] = tp; w[5] = gt; w[6] = __float_as_int(iou);
+#pragma unroll
+            for (int u = 0; u < EV_MAX_UNC; ++u)
+                if (u < a.n_unc) w[EV_HEAD + u] = __float_as_int(r[a.unc[u]]);
+        } else {
+            a.state[ST_OVERFLOW] = 1;                        // sticky: nothing clears it but byolo_eval_reset
+        }
+    });
+}
 
+// ---- the ladder: the matching at several IoU thresholds ---------------------------------------------------------------------
 struct LadderArgs {
     EvalArgs e;                                                  // table is not written, state is read only
     int32_t* ladder;
@@ -226,140 +269,32 @@ struct LadderArgs {
 struct LadderLds {
     EvalLds L;
     float thr[LAD_MAX];
-    int part[LAD_MAX];                                           // per wave: survivors counted in the images before this one
-    int ns;
 };
 
 __global__ __launch_bounds__(64 * LAD_MAX) void eval_ladder_kernel(const LadderArgs la) {
     __shared__ LadderLds S;
     EvalLds& L = S.L;
     const EvalArgs& a = la.e;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int nthreads = 64 * la.n_thr;
-    const unsigned long long lt_mask = (1ull << lane) - 1ull;
-
-    // 1 -- ground truth (the counters are the match kernel's)
-    const int G = ev_clampi(a.gt_counts[b], 0, a.gmax);
-    for (int g = tid; g < G; g += nthreads) {
-        const float* q = a.gt_boxes + ((size_t)b * a.gmax + g) * 4;
-        const NBox o = make_box(q[0], q[1], q[2], q[3]);
-        int lab = a.gt_labels[(size_t)b * a.gmax + g];
-        if (lab < 0 || lab >= a.C) lab = -1;
-        L.y0[g] = o.y0; L.x0[g] = o.x0; L.y1[g] = o.y1; L.x1[g] = o.x1; L.ar[g] = o.area; L.label[g] = lab;
-    }
     if (tid < la.n_thr) S.thr[tid] = la.thr[tid];
-    if (tid == 0) S.ns = 0;
-    __syncthreads();
-
-    // 2 -- keys of the surviving rows: the waves take turns at 64 rows; the keys are distinct, so their order before the sort
-    // does not matter
-    const int n = ev_clampi(a.count[(size_t)b * a.count_stride], 0, a.cap);
-    const float* rows = a.rows + (size_t)b * a.cap * a.D;
-    for (int i0 = wave << 6; i0 < n; i0 += nthreads) {
-        const int i = i0 + lane;
-        float s = 0.f; int c = 0;
-        const bool ok = i < n && ev_score(rows + (size_t)i * a.D, a, s, c);
-        const unsigned long long m = __ballot(ok);
-        int at = 0;
-        if (lane == 0 && m) at = atomicAdd(&S.ns, __popcll(m));  // LDS
-        at = __shfl(at, 0);
-        if (ok) {
-            if (s == 0.f) s = 0.f;                               // -0 orders as +0
-            unsigned int u = __float_as_uint(s);
-            u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-            L.key[at + __popcll(m & lt_mask)] = ((unsigned long long)(~u) << 32) | ((unsigned int)i << 8) | (unsigned int)c;
-        }
-    }
-
-    // 3 -- survivors of the images before this one, shared among the waves
-    int part = 0;
-    for (int pb = 0; pb < b; ++pb) {
-        const int pn = ev_clampi(a.count[(size_t)pb * a.count_stride], 0, a.cap);
-        const float* pr = a.rows + (size_t)pb * a.cap * a.D;
-        for (int i0 = wave << 6; i0 < pn; i0 += nthreads) {
-            const int i = i0 + lane;
-            float s; int c;
-            part += __popcll(__ballot(i < pn && ev_score(pr + (size_t)i * a.D, a, s, c)));
-        }
-    }
-    if (lane == 0) S.part[wave] = part;
-    __syncthreads();
-    const int ns = S.ns;
-    int before = 0;
-    for (int w = 0; w < la.n_thr; ++w) before += S.part[w];
-    const long long base = (long long)a.state[ST_TOTAL0 + a.parity] + before;
-
-    // 4 -- sort: descending score, then ascending row
-    int P2 = 64;
-    while (P2 < ns) P2 <<= 1;
-    for (int i = ns + tid; i < P2; i += nthreads) L.key[i] = ~0ull;
-    __syncthreads();
-    for (int k = 2; k <= P2; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < P2 / 2; t += nthreads) {
-                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-                ev_ce(L.key[i], L.key[i + j], (i & k) == 0);
-            }
-            __syncthreads();
-        }
+    const EvalImage im = ev_stage_and_sort<false>(L, a, blockIdx.x, tid, nthreads);
     // the score half of a key has done its work: it collects the detection's true-positive bits
-    unsigned int* kw = reinterpret_cast<unsigned int*>(L.key);   // little endian: word 2 d is (row, class), word 2 d + 1 the score
-    for (int d = tid; d < ns; d += nthreads) kw[2 * d + 1] = 0u;
+    for (int d = tid; d < im.ns; d += nthreads) ev_key_word(L, d, 1) = 0u;
     __syncthreads();
 
-    // 5 -- this wave's threshold: the pass of eval_match_kernel
-    const float thr = S.thr[wave];
+    // 6 -- this wave's threshold: its bit, and the box it matched
     const int rec_words = 1 + la.n_thr;
-    const int passes = (G + 63) >> 6;
-    unsigned int matched = 0;
-    for (int d0 = 0; d0 < ns; d0 += 64) {
-        const int d = d0 + lane;
-        const bool have = d < ns;
-        const unsigned int lo = have ? kw[2 * d] : 0u;
-        const int my_row = (int)(lo >> 8), my_cls = (int)(lo & 255u);
-        const float* r = rows + (size_t)my_row * a.D;
-        NBox me = make_box(0.f, 0.f, 0.f, 0.f);
-        if (have) me = make_box(r[0], r[1], r[2], r[3]);
-        int my_tp = 0, my_gt = -1;
-        const int nd = min(64, ns - d0);
-        for (int j = 0; j < nd; ++j) {
-            NBox o;
-            o.y0 = __shfl(me.y0, j); o.x0 = __shfl(me.x0, j); o.y1 = __shfl(me.y1, j); o.x1 = __shfl(me.x1, j);
-            o.area = __shfl(me.area, j);
-            const int oc = __shfl(my_cls, j);
-            float bi = -1.f;
-            int bg = 0x7fffffff;
-            for (int p = 0; p < passes; ++p) {
-                const int g = (p << 6) + lane;
-                if (g < G && L.label[g] == oc && !((matched >> p) & 1u)) {
-                    NBox q; q.y0 = L.y0[g]; q.x0 = L.x0[g]; q.y1 = L.y1[g]; q.x1 = L.x1[g]; q.area = L.ar[g];
-                    float v = iou_value(o, q);
-                    if (!(v >= 0.f)) v = 0.f;
-                    if (v > bi) { bi = v; bg = g; }
-                }
-            }
-#pragma unroll
-            for (int sft = 1; sft < 64; sft <<= 1) {
-                const float vi = __shfl_xor(bi, sft);
-                const int vg = __shfl_xor(bg, sft);
-                if (vi > bi || (vi == bi && vg < bg)) { bi = vi; bg = vg; }
-            }
-            const bool tp = bg != 0x7fffffff && bi >= thr;
-            if (tp && (bg & 63) == lane) matched |= 1u << (bg >> 6);
-            if (lane == j) { my_tp = tp ? 1 : 0; my_gt = tp ? bg : -1; }
-        }
-        const long long pos = base + d;
-        if (have) {
-            if (my_tp) atomicOr(&kw[2 * d + 1], 1u << wave);     // LDS
-            if (pos < a.capacity) la.ladder[(size_t)pos * rec_words + 1 + wave] = my_gt;
-        }
-    }
+    ev_greedy_pass(L, a, im, S.thr[wave], lane, [&](int d, int, int, const float*, int tp, int gt, float) {
+        const long long pos = im.base + d;
+        if (tp) atomicOr(&ev_key_word(L, d, 1), 1u << wave);     // LDS
+        if (pos < a.capacity) la.ladder[(size_t)pos * rec_words + 1 + wave] = gt;
+    });
     __syncthreads();
-
-    // 6 -- word 0: the bits of every threshold
-    for (int d = tid; d < ns; d += nthreads) {
-        const long long pos = base + d;
-        if (pos < a.capacity) la.ladder[(size_t)pos * rec_words] = (int32_t)kw[2 * d + 1];
+    // word 0: the bits of every threshold
+    for (int d = tid; d < im.ns; d += nthreads) {
+        const long long pos = im.base + d;
+        if (pos < a.capacity) la.ladder[(size_t)pos * rec_words] = (int32_t)ev_key_word(L, d, 1);
     }
 }
 
@@ -596,15 +531,38 @@ extern "C" int32_t byolo_eval_finish(byolo_eval_t* ev, byolo_eval_summary* out, 
     return BYOLO_OK;
 }
 
+// byolo_eval_records / _loc_records / _ladder_records (fn): n_records records of `words` words from `first` of d_table on
+static int32_t fetch_records(byolo_eval_t* ev, const char* fn, const int32_t* d_table, size_t words, int64_t first, int64_t n_records,
+                             int32_t* h_dst, void* stream) {
+    if (first < 0 || n_records < 0 || first + n_records > ev->capacity) return efail(ev, BYOLO_ERR_ARG, "%s: records outside the table", fn);
+    if (n_records == 0) return BYOLO_OK;
+    if (!h_dst) return efail(ev, BYOLO_ERR_ARG, "%s: null argument", fn);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    EVHIP(ev, hipMemcpyAsync(h_dst, d_table + (size_t)first * words, sizeof(int32_t) * words * (size_t)n_records, hipMemcpyDeviceToHost, s));
+    EVHIP(ev, hipStreamSynchronize(s));
+    return BYOLO_OK;
+}
+
 extern "C" int32_t byolo_eval_records(byolo_eval_t* ev, int32_t* h_dst, int64_t first, int64_t n_records, void* stream) {
     if (!ev) return efail(nullptr, BYOLO_ERR_ARG, "byolo_eval_records: null handle");
-    if (first < 0 || n_records < 0 || first + n_records > ev->capacity) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_records: records outside the table");
-    if (n_records == 0) return BYOLO_OK;
-    if (!h_dst) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_records: null argument");
-    const size_t rw = (size_t)record_words(ev->cfg);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    EVHIP(ev, hipMemcpyAsync(h_dst, ev->d_table + (size_t)first * rw, sizeof(int32_t) * rw * (size_t)n_records, hipMemcpyDeviceToHost, s));
-    EVHIP(ev, hipStreamSynchronize(s));
+    return fetch_records(ev, "byolo_eval_records", ev->d_table, (size_t)record_words(ev->cfg), first, n_records, h_dst, stream);
+}
+
+// byolo_eval_set_loc / _set_ladder (fn): everything around the checks of the cfg's own fields (`fields`: BYOLO_OK, or it has
+// failed).  A NULL table switches the side table off
+template <class Cfg, class Fields>
+static int32_t set_side_table(byolo_eval_t* ev, const char* fn, const Cfg* cfg, const char* cfg_name, void* d_table, const char* table_name,
+                              Cfg byolo_eval::*keep, int32_t* byolo_eval::*slot, Fields fields) {
+    if (!ev) return efail(nullptr, BYOLO_ERR_ARG, "%s: null handle", fn);
+    if (ev->launches) return efail(ev, BYOLO_ERR_STATE, "%s: records were added since the last byolo_eval_reset", fn);
+    if (!d_table) { ev->*slot = nullptr; return BYOLO_OK; }
+    if (!cfg) return efail(ev, BYOLO_ERR_ARG, "%s: null cfg", fn);
+    if (cfg->struct_bytes != (int32_t)sizeof(Cfg))
+        return efail(ev, BYOLO_ERR_ARG, "%s: struct_bytes %d, this library's %s has %d", fn, cfg->struct_bytes, cfg_name, (int)sizeof(Cfg));
+    if (const int32_t rc = fields()) return rc;
+    if (reinterpret_cast<uintptr_t>(d_table) & 3) return efail(ev, BYOLO_ERR_ARG, "%s: %s must be 4-byte aligned", fn, table_name);
+    ev->*keep = *cfg;
+    ev->*slot = static_cast<int32_t*>(d_table);
     return BYOLO_OK;
 }
 
@@ -614,41 +572,28 @@ extern "C" size_t byolo_eval_loc_bytes(int64_t capacity) {
 }
 
 extern "C" int32_t byolo_eval_set_loc(byolo_eval_t* ev, const byolo_eval_loc_cfg* cfg, void* d_loc_table) {
-    if (!ev) return efail(nullptr, BYOLO_ERR_ARG, "byolo_eval_set_loc: null handle");
-    if (ev->launches) return efail(ev, BYOLO_ERR_STATE, "byolo_eval_set_loc: records were added since the last byolo_eval_reset");
-    if (!d_loc_table) { ev->d_loc = nullptr; return BYOLO_OK; }
-    if (!cfg) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_set_loc: null cfg");
-    if (cfg->struct_bytes != (int32_t)sizeof(byolo_eval_loc_cfg))
-        return efail(ev, BYOLO_ERR_ARG, "byolo_eval_set_loc: struct_bytes %d, this library's byolo_eval_loc_cfg has %d", cfg->struct_bytes, (int)sizeof(byolo_eval_loc_cfg));
-    if (cfg->layer_col < 0 || cfg->layer_col >= ev->cfg.row_len) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_set_loc: layer_col %d outside the row", cfg->layer_col);
-    if (cfg->prior_col < 0 || cfg->prior_col >= ev->cfg.row_len) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_set_loc: prior_col %d outside the row", cfg->prior_col);
-    if (cfg->n_layers < 1 || cfg->n_layers > BYOLO_EVAL_LOC_MAX_LAYERS) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_set_loc: n_layers outside 1 .. %d", BYOLO_EVAL_LOC_MAX_LAYERS);
-    for (int l = 0; l < cfg->n_layers; ++l) {
-        if (cfg->n_priors[l] < 1 || cfg->n_priors[l] > BYOLO_EVAL_LOC_MAX_PRIORS)
-            return efail(ev, BYOLO_ERR_ARG, "byolo_eval_set_loc: n_priors of layer %d outside 1 .. %d", l, BYOLO_EVAL_LOC_MAX_PRIORS);
-        if (cfg->lh[l] < 1 || cfg->lw[l] < 1) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_set_loc: grid of layer %d below 1 x 1", l);
-        for (int p = 0; p < cfg->n_priors[l]; ++p) {
-            const float w = cfg->prior_w[l][p], h = cfg->prior_h[l][p];
-            if (!(w > 0.f && w <= 3.402823466e38f && h > 0.f && h <= 3.402823466e38f))
-                return efail(ev, BYOLO_ERR_ARG, "byolo_eval_set_loc: prior %d of layer %d is not finite and > 0", p, l);
+    return set_side_table(ev, "byolo_eval_set_loc", cfg, "byolo_eval_loc_cfg", d_loc_table, "d_loc_table", &byolo_eval::loc, &byolo_eval::d_loc, [&]() -> int32_t {
+        if (cfg->layer_col < 0 || cfg->layer_col >= ev->cfg.row_len) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_set_loc: layer_col %d outside the row", cfg->layer_col);
+        if (cfg->prior_col < 0 || cfg->prior_col >= ev->cfg.row_len) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_set_loc: prior_col %d outside the row", cfg->prior_col);
+        if (cfg->n_layers < 1 || cfg->n_layers > BYOLO_EVAL_LOC_MAX_LAYERS) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_set_loc: n_layers outside 1 .. %d", BYOLO_EVAL_LOC_MAX_LAYERS);
+        for (int l = 0; l < cfg->n_layers; ++l) {
+            if (cfg->n_priors[l] < 1 || cfg->n_priors[l] > BYOLO_EVAL_LOC_MAX_PRIORS)
+                return efail(ev, BYOLO_ERR_ARG, "byolo_eval_set_loc: n_priors of layer %d outside 1 .. %d", l, BYOLO_EVAL_LOC_MAX_PRIORS);
+            if (cfg->lh[l] < 1 || cfg->lw[l] < 1) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_set_loc: grid of layer %d below 1 x 1", l);
+            for (int p = 0; p < cfg->n_priors[l]; ++p) {
+                const float w = cfg->prior_w[l][p], h = cfg->prior_h[l][p];
+                if (!(w > 0.f && w <= 3.402823466e38f && h > 0.f && h <= 3.402823466e38f))
+                    return efail(ev, BYOLO_ERR_ARG, "byolo_eval_set_loc: prior %d of layer %d is not finite and > 0", p, l);
+            }
         }
-    }
-    if (reinterpret_cast<uintptr_t>(d_loc_table) & 3) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_set_loc: d_loc_table must be 4-byte aligned");
-    ev->loc = *cfg;
-    ev->d_loc = static_cast<int32_t*>(d_loc_table);
-    return BYOLO_OK;
+        return BYOLO_OK;
+    });
 }
 
 extern "C" int32_t byolo_eval_loc_records(byolo_eval_t* ev, int32_t* h_dst, int64_t first, int64_t n_records, void* stream) {
     if (!ev) return efail(nullptr, BYOLO_ERR_ARG, "byolo_eval_loc_records: null handle");
     if (!ev->d_loc) return efail(ev, BYOLO_ERR_STATE, "byolo_eval_loc_records: no loc table is set (byolo_eval_set_loc)");
-    if (first < 0 || n_records < 0 || first + n_records > ev->capacity) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_loc_records: records outside the table");
-    if (n_records == 0) return BYOLO_OK;
-    if (!h_dst) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_loc_records: null argument");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    EVHIP(ev, hipMemcpyAsync(h_dst, ev->d_loc + (size_t)first * byk::LOC_WORDS, sizeof(int32_t) * byk::LOC_WORDS * (size_t)n_records, hipMemcpyDeviceToHost, s));
-    EVHIP(ev, hipStreamSynchronize(s));
-    return BYOLO_OK;
+    return fetch_records(ev, "byolo_eval_loc_records", ev->d_loc, byk::LOC_WORDS, first, n_records, h_dst, stream);
 }
 
 // ---- the ladder --------------------------------------------------------------------------------------------------------------
@@ -658,31 +603,17 @@ extern "C" size_t byolo_eval_ladder_bytes(int64_t capacity, int32_t n_thr) {
 }
 
 extern "C" int32_t byolo_eval_set_ladder(byolo_eval_t* ev, const byolo_eval_ladder_cfg* cfg, void* d_ladder_table) {
-    if (!ev) return efail(nullptr, BYOLO_ERR_ARG, "byolo_eval_set_ladder: null handle");
-    if (ev->launches) return efail(ev, BYOLO_ERR_STATE, "byolo_eval_set_ladder: records were added since the last byolo_eval_reset");
-    if (!d_ladder_table) { ev->d_ladder = nullptr; return BYOLO_OK; }
-    if (!cfg) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_set_ladder: null cfg");
-    if (cfg->struct_bytes != (int32_t)sizeof(byolo_eval_ladder_cfg))
-        return efail(ev, BYOLO_ERR_ARG, "byolo_eval_set_ladder: struct_bytes %d, this library's byolo_eval_ladder_cfg has %d", cfg->struct_bytes, (int)sizeof(byolo_eval_ladder_cfg));
-    if (cfg->n_thr < 1 || cfg->n_thr > BYOLO_EVAL_LADDER_MAX) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_set_ladder: n_thr outside 1 .. %d", BYOLO_EVAL_LADDER_MAX);
-    for (int k = 0; k < cfg->n_thr; ++k)
-        if (!(cfg->thresholds[k] >= 0.f && cfg->thresholds[k] <= 1.f))
-            return efail(ev, BYOLO_ERR_ARG, "byolo_eval_set_ladder: threshold %d is NaN or outside [0, 1]", k);
-    if (reinterpret_cast<uintptr_t>(d_ladder_table) & 3) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_set_ladder: d_ladder_table must be 4-byte aligned");
-    ev->ladder = *cfg;
-    ev->d_ladder = static_cast<int32_t*>(d_ladder_table);
-    return BYOLO_OK;
+    return set_side_table(ev, "byolo_eval_set_ladder", cfg, "byolo_eval_ladder_cfg", d_ladder_table, "d_ladder_table", &byolo_eval::ladder, &byolo_eval::d_ladder, [&]() -> int32_t {
+        if (cfg->n_thr < 1 || cfg->n_thr > BYOLO_EVAL_LADDER_MAX) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_set_ladder: n_thr outside 1 .. %d", BYOLO_EVAL_LADDER_MAX);
+        for (int k = 0; k < cfg->n_thr; ++k)
+            if (!(cfg->thresholds[k] >= 0.f && cfg->thresholds[k] <= 1.f))
+                return efail(ev, BYOLO_ERR_ARG, "byolo_eval_set_ladder: threshold %d is NaN or outside [0, 1]", k);
+        return BYOLO_OK;
+    });
 }
 
 extern "C" int32_t byolo_eval_ladder_records(byolo_eval_t* ev, int32_t* h_dst, int64_t first, int64_t n_records, void* stream) {
     if (!ev) return efail(nullptr, BYOLO_ERR_ARG, "byolo_eval_ladder_records: null handle");
     if (!ev->d_ladder) return efail(ev, BYOLO_ERR_STATE, "byolo_eval_ladder_records: no ladder table is set (byolo_eval_set_ladder)");
-    if (first < 0 || n_records < 0 || first + n_records > ev->capacity) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_ladder_records: records outside the table");
-    if (n_records == 0) return BYOLO_OK;
-    if (!h_dst) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_ladder_records: null argument");
-    const size_t rw = (size_t)(1 + ev->ladder.n_thr);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    EVHIP(ev, hipMemcpyAsync(h_dst, ev->d_ladder + (size_t)first * rw, sizeof(int32_t) * rw * (size_t)n_records, hipMemcpyDeviceToHost, s));
-    EVHIP(ev, hipStreamSynchronize(s));
-    return BYOLO_OK;
+    return fetch_records(ev, "byolo_eval_ladder_records", ev->d_ladder, (size_t)(1 + ev->ladder.n_thr), first, n_records, h_dst, stream);
 }

@@ -62,27 +62,41 @@ def test_seeded_cases_match_the_restatement_at_every_threshold(group):
 # ---- the sizes at which the kernel changes its path ---------------------------------------------------------------------------
 COUNTS = [0, 1, 63, 64, 65, 127, 128, 129, 255, 256, 257, 300]
 GTS = [1, 65, 130, 65, 0, 130, 1, 65, 130, 0, 65, 130]
+# images whose keys sort at 4096, 2048 and 4096: with 16 waves the compare-exchange loop and the key compaction take a second trip
+LARGE_COUNTS = [2049, 1025, 2100]
+LARGE_GTS = [130, 65, 1]
 BOUNDARY_LADDERS = {1: [f32(0.75)], 3: [f32(0.5), f32(0.75), f32(0.9)],
                     16: [f32(t) for t in (0.5, 0.9, 0.75, 0.6) * 4]}      # 16 waves; four reference runs serve them all
 _BOUNDARY = {}
 
 
-def _boundary_case():
-    if not _BOUNDARY:
-        rows, count, gb, gl, gc = er.make_case(4242, len(COUNTS), 2, 'yolov3', GTS, cap=300, full=True)
-        assert list(count) == [300] * len(COUNTS)
-        _BOUNDARY['batches'] = [(rows, np.array(COUNTS, np.int32), gb, gl, gc)]
-    return _BOUNDARY['batches']
+def _boundary_case(key='boundary'):
+    """(batches, capacity) of the one batch `key` names: every image filled to the cap, then counted down to its size."""
+    if key not in _BOUNDARY:
+        seed, counts, gts, capacity = {'boundary': (4242, COUNTS, GTS, 2048), 'large': (777, LARGE_COUNTS, LARGE_GTS, 8192)}[key]
+        rows, count, gb, gl, gc = er.make_case(seed, len(counts), 2, 'yolov3', gts, cap=max(counts), full=True)
+        assert list(count) == [max(counts)] * len(counts)
+        _BOUNDARY[key] = [(rows, np.array(counts, np.int32), gb, gl, gc)], capacity
+    return _BOUNDARY[key]
 
 
-@pytest.mark.parametrize("n_thr", [1, 3, 16])
-def test_sort_and_pass_boundaries(n_thr):
+def _check_whole_main_table(ev, batches, layout, key):
+    """Every field of every main record, and the counters, at the evaluator's own threshold."""
+    exp, n_gt, n_img = lr.table_at(batches, layout, 2, f32(ev.iou_thresh), key=key)
+    table = ev.records()
+    assert table.dtype == exp.dtype and len(table) == len(exp)
+    for f in ('img', 'row', 'cls', 'score', 'tp', 'gt', 'iou'):
+        assert table[f].tobytes() == exp[f].tobytes(), (key, f, np.flatnonzero(table[f].view(np.int32) != exp[f].view(np.int32))[:5])
+    assert ev.class_gt() == (n_gt, n_img)
+
+
+def _check_boundaries(key, counts, n_thr):
     from byolo.evaluate import Evaluator
-    batches, layout, thr = _boundary_case(), er.layout('yolov3', 2), BOUNDARY_LADDERS[n_thr]
-    runs = [lr.table_at(batches, layout, 2, t, key='boundary') for t in thr]
+    (batches, capacity), layout, thr = _boundary_case(key), er.layout('yolov3', 2), BOUNDARY_LADDERS[n_thr]
+    runs = [lr.table_at(batches, layout, 2, t, key=key) for t in thr]
     tables, n_gt, n_img = [r[0] for r in runs], runs[0][1], runs[0][2]
-    assert len(tables[0]) == sum(COUNTS) and len({int(t['tp'].sum()) for t in tables}) == min(n_thr, 4)
-    ev = Evaluator(_layout(layout, 2), capacity=2048, iou_thresholds=thr)
+    assert len(tables[0]) == sum(counts) and len({int(t['tp'].sum()) for t in tables}) == min(n_thr, 4)
+    ev = Evaluator(_layout(layout, 2), capacity=capacity, iou_thresholds=thr)
     _add(ev, batches[0], strided=False)
     got = ev.finish()
     words = ev.ladder_records()
@@ -93,6 +107,29 @@ def test_sort_and_pass_boundaries(n_thr):
     assert np.array_equal(s['ladder_cum_tp'], cum_tp) and np.array_equal(s['ladder_cum_fp'], cum_fp)
     assert lr.same_ladder(got['ladder'], exp)
     _check_against_main_table(ev, got, words, thr)
+    _check_whole_main_table(ev, batches, layout, key)
+    ev.close()
+
+
+@pytest.mark.parametrize("n_thr", [1, 3, 16])
+def test_sort_and_pass_boundaries(n_thr):
+    _check_boundaries('boundary', COUNTS, n_thr)
+
+
+@pytest.mark.parametrize("n_thr", [1, 3, 16])
+def test_sort_and_pass_boundaries_large_images(n_thr):
+    _check_boundaries('large', LARGE_COUNTS, n_thr)
+
+
+@pytest.mark.parametrize("key", ['boundary', 'large'])
+def test_main_table_at_the_boundaries_without_a_ladder(key):
+    """The one-wave kernel alone at the same sizes."""
+    from byolo.evaluate import Evaluator
+    (batches, capacity), layout = _boundary_case(key), er.layout('yolov3', 2)
+    ev = Evaluator(_layout(layout, 2), capacity=capacity)
+    _add(ev, batches[0], strided=False)
+    assert ev.ladder_table is None and ev.finish()['n_detections'] == sum(batches[0][1])
+    _check_whole_main_table(ev, batches, layout, key)
     ev.close()
 
 
