@@ -30,40 +30,7 @@ from conftest import REPO
 
 sys.path.insert(0, os.path.join(REPO, "bayesian-yolov3_amd"))
 
-ACT_SCALE = 4.0
-
-
-def _split(a, scale):
-    import torch
-    a = a * scale
-    hi = a.half().float()
-    lo = (a - hi).half().float()
-    return hi / scale, lo / scale
-
-
-def _wino_split_conv(x, w):
-    """One 3x3 / stride-1 convolution as Winograd F(2x2,3x3) in split-f16 arithmetic, as a fused device kernel would run it:
-    V = B^T d B in fp32 from the decoded hi + lo input, stored as hi/lo pairs (scale 1: |V| <= 4 |d|, the same fp16 range as the
-    activations' 4 * value); U = G g G^T in double, rounded once, one power-of-two scale per output channel, hi/lo pairs; the 16
-    transform-domain products x_hi u_hi + x_hi u_lo + x_lo u_hi accumulated in fp32 over the input channels; Y = A^T M A in fp32."""
-    import torch
-    import torch.nn.functional as F
-    S, H, W, C = x.shape
-    N = w.shape[3]
-    th, tw = (H + 1) // 2, (W + 1) // 2
-    xp = F.pad(x.permute(0, 3, 1, 2), (1, 1 + 2 * tw - W, 1, 1 + 2 * th - H))
-    p = xp.unfold(2, 4, 2).unfold(3, 4, 2)                                   # [S, C, th, tw, 4, 4]
-    Bt = torch.tensor([[1, 0, -1, 0], [0, 1, 1, 0], [0, -1, 1, 0], [0, 1, 0, -1]], dtype=torch.float32)
-    G = torch.tensor([[1, 0, 0], [.5, .5, .5], [.5, -.5, .5], [0, 0, 1]], dtype=torch.float64)
-    At = torch.tensor([[1, 1, 1, 0], [0, 1, -1, -1]], dtype=torch.float32)
-    V = torch.einsum("ij,sctujk,lk->sctuil", Bt, p, Bt)                      # fp32 adds of exactly representable inputs
-    U = torch.einsum("ij,jkcn,lk->ilcn", G, w.double(), G).float()           # [4, 4, C, N]
-    ws = torch.exp2(13 - torch.floor(torch.log2(U.abs().amax(dim=(0, 1, 2)).clamp(min=1e-30))))
-    Vh, Vl = _split(V, 1.0)
-    Uh, Ul = _split(U, ws)
-    M = (torch.einsum("sctuil,ilcn->sntuil", Vh, Uh) + (torch.einsum("sctuil,ilcn->sntuil", Vh, Ul) + torch.einsum("sctuil,ilcn->sntuil", Vl, Uh)))
-    Y = torch.einsum("ai,sntuil,bl->sntaub", At, M, At)                      # [S, N, th, 2, tw, 2]
-    return Y.reshape(S, N, 2 * th, 2 * tw)[:, :, :H, :W].permute(0, 2, 3, 1).contiguous()
+from _layer_ref import ACT_SCALE, _split, _split_conv, _wino_split_conv      # noqa: E402  (one definition, shared with the per-layer tests)
 
 
 def _wino1d_split_conv(x, w):
@@ -121,11 +88,7 @@ def _run(H, W, T, wino=False):
             return _wino_split_conv(x, w)                              # ... beside what the product's plan already transforms in 2-D
         if wino is True and w.shape[0] == 3 and stride == 1 and x.shape[3] >= 64:
             return _wino_split_conv(x, w)
-        # one power of two per output channel (byolo_finalize): the channel's largest |w'| in [2^13, 2^14)
-        ws = torch.exp2(13 - torch.floor(torch.log2(w.abs().amax(dim=(0, 1, 2)).clamp(min=1e-30))))
-        xh, xl = _split(x, ACT_SCALE)
-        wh, wl = _split(w, ws)
-        return orig_conv(xh, wh, stride) + (orig_conv(xh, wl, stride) + orig_conv(xl, wh, stride))
+        return _split_conv(x, w, stride, conv=orig_conv)                 # one power of two per output channel, three products
 
     def leaky(x):
         y = orig_leaky(x)
