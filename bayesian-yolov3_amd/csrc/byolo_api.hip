@@ -576,6 +576,15 @@ static uint64_t sample_base(const byolo_t* h, int T, bool stacked) {
     return (uint64_t)h->first_image * (uint64_t)T;
 }
 
+// The raw epilogue: the accumulators as they are (STEP_PARTIAL, the launch in front of a feed == 1 reader, the Winograd-domain GEMMs,
+// calibration)
+static EpiArgs raw_epi(const byolo_t* h, int layer) {
+    EpiArgs e; memset(&e, 0, sizeof e);
+    e.scale = h->d_ones; e.shift = h->d_zeros; e.flags = EPI_RAW;
+    e.status = h->precision == 1 ? h->d_status : nullptr; e.layer_idx = layer;
+    return e;
+}
+
 static void fill_conv(const byolo_t* h, const Step& st, const float* d_img, char* ws, int B, int T, ConvParams& p) {
     const Layer& l = h->layers[st.layer];
     memset(&p, 0, sizeof p);
@@ -606,8 +615,7 @@ static void fill_conv(const byolo_t* h, const Step& st, const float* d_img, char
     p.N = layer_pitch(l); p.Npad = st.Npad; p.ldc = layer_pitch(l);      // (a detection head: padded to a multiple of 4, <= Npad)
     p.cin_tiles = (st.c_hi - st.c_lo) / 32; p.KT = l.ksize * l.ksize * p.cin_tiles;
     p.wpk = dptr(h, st.w_off);
-    if (st.mode == STEP_PARTIAL) { p.scale = h->d_ones; p.shift = h->d_zeros; }      // raw accumulators
-    else { p.scale = dptr(h, l.scale_off); p.shift = dptr(h, l.shift_off); }
+    p.epi = raw_epi(h, st.layer);                                 // (the layer's own epilogue: prep, calibrate_bn_impl)
     p.dst = h->plan.off[st.out_tensor] >= 0 ? reinterpret_cast<float*>(ws + h->plan.off[st.out_tensor]) : nullptr;      // (none: a STEP_REP folded into its reader stores into Step::raw_tensor instead, Plan::feed)
     // buffer-descriptor extents (check_run bounds every tensor by CONV_MAX_SRC_BYTES) and the launch-constant divisors
     p.src0_bytes = (uint32_t)((uint64_t)nsrc[0] * Hs[0] * Wsz[0] * Cs[0] * 4);
@@ -625,13 +633,11 @@ static void fill_conv(const byolo_t* h, const Step& st, const float* d_img, char
         p.addend_T = l.stacked ? T : 1;
     } else { p.addend = nullptr; p.addend_T = 1; }
     p.d_addT = make_fastdiv((uint32_t)p.addend_T);
-    p.status = h->precision == 1 ? h->d_status : nullptr; p.layer_idx = st.layer;
     p.no_plain = h->opts.plain_epilogue == 0;
 }
 
 // STEP_FINISH: mode 0 the raw sum (calibration), 1 / 2 the layer's epilogue with fp32 / hi-lo output
-static void fill_finish(const byolo_t* h, const Step& st, char* ws, int B, int T, int mode, bool drop, const byolo_drop_keys& keys,
-                        const uint32_t* mask_bits, bool inject, FinishParams& f) {
+static void fill_finish(const byolo_t* h, const Step& st, char* ws, int B, int T, int mode, FinishParams& f) {
     const Layer& l = h->layers[st.layer];
     memset(&f, 0, sizeof f);
     f.low = reinterpret_cast<const float*>(ws + h->plan.off[st.low_tensor]);
@@ -639,17 +645,7 @@ static void fill_finish(const byolo_t* h, const Step& st, char* ws, int B, int T
     f.dst = h->plan.off[st.out_tensor] >= 0 ? reinterpret_cast<float*>(ws + h->plan.off[st.out_tensor]) : nullptr;      // (none: the plan folded this step into its reader, Plan::feed)
     f.T = l.stacked ? T : 1; f.S = B * f.T; f.H = l.H; f.W = l.W; f.N = l.filters;
     f.mode = mode;
-    if (mode == 0) { f.scale = h->d_ones; f.shift = h->d_zeros; }
-    else {
-        f.flags = EPI_LEAKY;
-        f.scale = dptr(h, l.scale_off); f.shift = dptr(h, l.shift_off);
-        if (drop) {
-            f.flags |= EPI_DROPOUT; f.k0 = keys.k0; f.k1 = keys.k1; f.thr = keys.thr; f.mask_bits = mask_bits;
-            f.idx_base = inject ? 0 : sample_base(h, f.T, l.stacked) * (uint64_t)l.H * l.W * l.filters;
-            f.scale = dptr(h, l.scalek_off);
-        }
-    }
-    f.status = h->precision == 1 ? h->d_status : nullptr; f.layer_idx = st.layer;
+    f.epi = raw_epi(h, st.layer); f.epi.flags = 0;               // mode 0 as it is; modes 1 / 2: the caller writes the layer's (finish_params)
     f.d_hw = make_fastdiv((uint32_t)(l.H * l.W / 4)); f.d_w = make_fastdiv((uint32_t)(l.W / 2));      // of the source's grid
     f.d_n4 = make_fastdiv((uint32_t)(l.filters / 4)); f.d_T = make_fastdiv((uint32_t)f.T);
 }
@@ -658,7 +654,7 @@ static void fill_finish(const byolo_t* h, const Step& st, char* ws, int B, int T
 static int32_t run_aux_step(byolo_t* h, const Step& s, const ConvParams& p, hipStream_t st) {
     const Layer& l = h->layers[s.layer];
     if (s.mode == STEP_GATHER) { HIPCHK(h, launch_view_gather(p, st)); }
-    else { HIPCHK(h, launch_tensor_add(p.src0, p.src1, p.dst, (int64_t)p.M * l.C, h->precision == 1, st, p.status, s.layer)); }
+    else { HIPCHK(h, launch_tensor_add(p.src0, p.src1, p.dst, (int64_t)p.M * l.C, h->precision == 1, st, p.epi.status, s.layer)); }
     return BYOLO_OK;
 }
 
@@ -696,11 +692,10 @@ static int32_t run_winograd(byolo_t* h, const Step& s, const Layer& l, const Con
         const int ns = std::min(wp.chunk, S - s0);
         WinoParams w; memset(&w, 0, sizeof w);
         w.x = c.src0; w.v = V; w.m = Mb; w.y = c.dst;
-        w.residual = (c.flags & EPI_RESIDUAL) ? c.residual : nullptr;
-        w.scale = c.scale; w.shift = c.shift;
+        w.residual = (c.epi.flags & EPI_RESIDUAL) ? c.residual : nullptr;
+        w.epi = c.epi;
         w.H = l.H; w.W = l.W; w.C = c.C0; w.N = c.N; w.th = wp.th; w.tw = wp.tw;
         w.s0 = s0; w.P = ns * tt; w.P_pad = (int)align_up((size_t)w.P, 128);
-        w.flags = c.flags; w.k0 = c.k0; w.k1 = c.k1; w.thr = c.thr; w.idx_base = c.idx_base;
         w.d_tt = make_fastdiv((uint32_t)tt); w.d_tw = make_fastdiv((uint32_t)wp.tw);
         w.d_c4 = make_fastdiv((uint32_t)(c.C0 / 4)); w.d_n4 = make_fastdiv((uint32_t)(c.N / 4));
         // variants of the profile entries: -2 input transform, BN of the GEMM tile, -3 output transform; the GEMM
@@ -713,13 +708,12 @@ static int32_t run_winograd(byolo_t* h, const Step& s, const Layer& l, const Con
             WinoFusedParams f; memset(&f, 0, sizeof f);
             f.v = V; f.v_bytes = (uint32_t)((uint64_t)rows * c.C0 * 4);
             f.w = dptr(h, s.wino_off); f.wstride = (uint32_t)((size_t)(c.C0 / 32) * c.N * 32 * 4); f.w_bytes = 16u * f.wstride;
-            f.y = c.dst; f.residual = (c.flags & EPI_RESIDUAL) ? c.residual : nullptr; f.scale = c.scale; f.shift = c.shift;
+            f.y = c.dst; f.residual = w.residual; f.epi = c.epi;
             f.C = c.C0; f.N = c.N; f.KT = c.C0 / 32; f.n_tiles = c.N / 64;
             f.H = l.H; f.W = l.W; f.th = wp.th; f.tw = wp.tw; f.s0 = s0; f.P = w.P;
             const int RT = w.P_pad / 128;
             f.slots = 512 / f.n_tiles; f.q = RT / f.slots; f.rem = RT % f.slots;
             f.xi_stride = (uint32_t)((uint64_t)w.P_pad * c.C0 * 4);
-            f.flags = c.flags; f.k0 = c.k0; f.k1 = c.k1; f.thr = c.thr; f.idx_base = c.idx_base;
             f.d_ntiles = make_fastdiv((uint32_t)f.n_tiles); f.d_tt = w.d_tt; f.d_tw = w.d_tw;
             if (prof && (rc = mark_launch(h, s.layer, 130, rows, c.N, c.C0, algo_flops * ns / S, st))) return rc;
             HIPCHK(h, launch_wino_fused(f, st));
@@ -734,7 +728,7 @@ static int32_t run_winograd(byolo_t* h, const Step& s, const Layer& l, const Con
             const int R = 16 * q.RT;
             q.slots = 512 / q.n_tiles; q.q = R / q.slots; q.rem = R % q.slots;
             q.d_ntiles = make_fastdiv((uint32_t)q.n_tiles); q.d_RT = make_fastdiv((uint32_t)q.RT);
-            q.epi = 0; q.M = rows; q.Npad = c.N; q.ldc = c.N;
+            q.kind = 0; q.epi = raw_epi(h, s.layer); q.M = rows; q.Npad = c.N; q.ldc = c.N;
             if (prof && (rc = mark_launch(h, s.layer, 129, rows, c.N, c.C0, algo_flops * ns / S, st))) return rc;
             HIPCHK(h, launch_gemm_stream(q, st));
             if (prof && (rc = mark_launch(h, s.layer, -3, w.P, c.N, 0, 0.0, st))) return rc;
@@ -751,7 +745,7 @@ static int32_t run_winograd(byolo_t* h, const Step& s, const Layer& l, const Con
         g.wino_rows = (uint32_t)w.P_pad; g.d_wino = make_fastdiv((uint32_t)w.P_pad);
         g.wino_wstride = (uint32_t)((size_t)g.cin_tiles * c.Npad * 32 * 4);
         g.w_bytes = 16u * g.wino_wstride;
-        g.scale = h->d_ones; g.shift = h->d_zeros; g.flags = EPI_RAW; g.rep = 1; g.addend_T = 1;
+        g.epi = raw_epi(h, s.layer); g.rep = 1; g.addend_T = 1;
         g.dst = Mb;
         g.d_hw = make_fastdiv((uint32_t)rows); g.d_wout = make_fastdiv((uint32_t)rows);
         g.d_sdiv0 = g.d_sdiv1 = g.d_addT = make_fastdiv(1u);
@@ -772,14 +766,14 @@ static int32_t run_winograd(byolo_t* h, const Step& s, const Layer& l, const Con
 // One 3x3 / stride-1 convolution as Winograd F(2x2,3x3) in split-f16 arithmetic (wino_split.hip): per chunk of samples the input
 // transform and ONE launch of GEMM + output transform + epilogue.  `c` = the ConvParams of the direct launch.
 // Profile variants: -4 the transform, 140 the fused launch (carries the direct-convolution FLOPs of its samples).
-// `feed`: null, or a WinoParams holding the feed / src_ fields of the element-wise step the transform evaluates itself (Plan::feed).
+// `feed`: null, or a WinoParams holding the feed / src fields of the element-wise step the transform evaluates itself (Plan::feed).
 static int32_t run_wino_split(byolo_t* h, const Step& s, const Layer& l, const ConvParams& c, const WinoPlan& wp, double algo_flops,
                               char* ws, hipStream_t st, const WinoParams* feed = nullptr) {
     const bool prof = h->profiling >= 2;
     int32_t rc;
     const int S = c.M / (l.H * l.W), tt = wp.th * wp.tw;
     float* V = reinterpret_cast<float*>(ws + h->plan.wino_off);
-    const bool drop = c.flags & EPI_DROPOUT;
+    const bool drop = c.epi.flags & EPI_DROPOUT;
     for (int s0 = 0; s0 < S; s0 += wp.chunk) {
         const int ns = std::min(wp.chunk, S - s0);
         WinoParams w; memset(&w, 0, sizeof w);
@@ -796,7 +790,8 @@ static int32_t run_wino_split(byolo_t* h, const Step& s, const Layer& l, const C
         const uint64_t rows = (uint64_t)16 * w.P_pad;
         f.v = V; f.v_bytes = (uint32_t)(rows * c.C0 * 4); f.xi_stride = (uint32_t)((uint64_t)w.P_pad * c.C0 * 4);
         f.w = dptr(h, s.wino_off); f.w_bytes = (uint32_t)((size_t)16 * c.C0 * c.N * 4);
-        f.y = c.dst; f.residual = (c.flags & EPI_RESIDUAL) ? c.residual : nullptr; f.scale = dptr(h, drop ? l.wscalek_off : l.wscale_off); f.shift = c.shift;
+        f.y = c.dst; f.residual = (c.epi.flags & EPI_RESIDUAL) ? c.residual : nullptr;
+        f.epi = c.epi; f.epi.scale = dptr(h, drop ? l.wscalek_off : l.wscale_off);
         f.C = c.C0; f.N = c.N; f.KT = c.C0 / 32; f.n_tiles = c.N / wp.bn; f.bn = wp.bn;
         f.H = l.H; f.W = l.W; f.th = wp.th; f.tw = wp.tw; f.s0 = s0; f.P = w.P; f.P_pad = w.P_pad;
         f.bm = wp.bm; f.units = (w.P_pad / wp.bm) * f.n_tiles;
@@ -804,8 +799,6 @@ static int32_t run_wino_split(byolo_t* h, const Step& s, const Layer& l, const C
         const int chunk_idx = s0 / wp.chunk;
         f.persist = (h->opts.wino_split_persist == 2 && c.counters && chunk_idx < CNT_PER_STEP / 8) ? 2 : (h->opts.wino_split_persist ? 1 : 0);
         f.claims = c.counters ? c.counters + 8 * chunk_idx : nullptr;
-        f.flags = c.flags; f.k0 = c.k0; f.k1 = c.k1; f.thr = c.thr; f.idx_base = c.idx_base; f.mask_bits = c.mask_bits;
-        f.status = c.status; f.layer_idx = c.layer_idx;
         f.d_ntiles = make_fastdiv((uint32_t)f.n_tiles); f.d_tt = w.d_tt; f.d_tw = w.d_tw;
         if (prof && (rc = mark_launch(h, s.layer, 140, (int64_t)rows, c.N, c.C0, algo_flops * ns / S, st, 1, wp.bn))) return rc;   // (split_tiles of a Winograd entry: its channels per workgroup)
         HIPCHK(h, launch_wino_split(f, st));
@@ -1137,12 +1130,36 @@ static int32_t finish_forward(byolo_t* h, hipStream_t st, void* stream) {
     return BYOLO_OK;
 }
 
+// The epilogue of layer `layer` (a convolution or a detection head) in call `a`: flags, scale array, and with the masks on this
+// call's dropout keys, injected bits and element base -- for the layer's own launch and for every launch that evaluates it instead
+static int32_t layer_epi(byolo_t* h, int layer, const FwdArgs& a, EpiArgs& e) {
+    const Layer& l = h->layers[layer];
+    const bool inject = a.d_mask_bits != nullptr && a.dropout_on;
+    e = raw_epi(h, layer);
+    e.flags = l.op == OP_CONV ? EPI_LEAKY : 0;
+    e.scale = dptr(h, l.scale_off); e.shift = dptr(h, l.shift_off);
+    if (l.op != OP_CONV || l.drop_ordinal < 0 || !a.dropout_on) return BYOLO_OK;
+    const byolo_drop_keys k = byolo_layer_keys(a.seed, (uint32_t)l.drop_ordinal, (double)h->cfg.drop_prob);
+    e.flags |= EPI_DROPOUT; e.k0 = k.k0; e.k1 = k.k1; e.thr = k.thr;
+    if (inject) {                                                // this layer's first word; bit i = element i of this call's tensor
+        int64_t n_el = 0;
+        const int64_t off = mask_layout(h, a.B, a.T, l.drop_ordinal, &n_el);
+        if ((l.filters & 3) && !l.direct) return fail(h, BYOLO_ERR_ARG, "byolo_forward: injected masks need cout %% 4 == 0 on a matrix-pipe dropout layer; '%s' has %d", l.scope.c_str(), l.filters);
+        if (n_el >= ((int64_t)1 << 32)) return fail(h, BYOLO_ERR_ARG, "byolo_forward: injected masks index a dropout tensor with 32 bits; layer '%s' has %lld elements", l.scope.c_str(), (long long)n_el);
+        e.mask_bits = a.d_mask_bits + off / 32;
+    }
+    // element index of this call's first output element in the logical batch's [S,h,w,c] tensor (the counter hash);
+    // injected bits are indexed inside THIS call's tensor, whatever byolo_set_first_image says
+    e.idx_base = inject ? 0 : sample_base(h, l.stacked ? a.T : 1, l.stacked) * (uint64_t)l.H * l.W * l.filters;
+    e.scale = dptr(h, l.scalek_off);                             // scale / (1 - p)
+    return BYOLO_OK;
+}
+
 // Everything one forward puts on the stream, in order: the split-K tickets' clear, the image's hi/lo copy, the convolution stack,
 // decode, sort + NMS.  `capturing`: the stream is in capture mode (forward_graph) -- no event is recorded or waited for in here.
 static int32_t enqueue_forward(byolo_t* h, const FwdArgs& a, hipStream_t st, bool capturing, bool wait_convs, bool heads_only) {
-    const float* d_img = a.d_img; const int32_t B = a.B, T = a.T; const uint64_t seed = a.seed; const int32_t dropout_on = a.dropout_on;
-    const uint32_t* d_mask_bits = a.d_mask_bits; float* d_boxes = a.d_boxes; float* d_rows = a.d_rows; int32_t* d_kept = a.d_kept; int32_t* d_count = a.d_count;
-    const bool inject = d_mask_bits != nullptr && dropout_on;
+    const float* d_img = a.d_img; const int32_t B = a.B, T = a.T;
+    float* d_boxes = a.d_boxes; float* d_rows = a.d_rows; int32_t* d_kept = a.d_kept; int32_t* d_count = a.d_count;
     int32_t rc;
     char* ws = reinterpret_cast<char*>(a.d_workspace);
     if (h->profiling) {
@@ -1168,33 +1185,15 @@ static int32_t enqueue_forward(byolo_t* h, const FwdArgs& a, hipStream_t st, boo
     auto prep = [&](size_t si, ConvParams& p, int& tile, double& algo) -> int32_t {
         const Step& s = h->steps[si];
         const Layer& l = h->layers[s.layer];
-        fill_conv(h, s, d_img, ws, B, T, p);
-        if (l.op == OP_CONV && s.mode != STEP_PARTIAL) {
-            p.flags = EPI_LEAKY;
-            if (l.drop_ordinal >= 0 && dropout_on) {
-                const byolo_drop_keys k = byolo_layer_keys(seed, (uint32_t)l.drop_ordinal, (double)h->cfg.drop_prob);
-                p.flags |= EPI_DROPOUT; p.k0 = k.k0; p.k1 = k.k1; p.thr = k.thr;
-                if (inject) {                                // this layer's first word; bit i = element i of this call's tensor
-                    int64_t n_el = 0;
-                    const int64_t off = mask_layout(h, B, T, l.drop_ordinal, &n_el);
-                    if ((l.filters & 3) && !l.direct) return fail(h, BYOLO_ERR_ARG, "byolo_forward: injected masks need cout %% 4 == 0 on a matrix-pipe dropout layer; '%s' has %d", l.scope.c_str(), l.filters);
-                    if (n_el >= ((int64_t)1 << 32)) return fail(h, BYOLO_ERR_ARG, "byolo_forward: injected masks index a dropout tensor with 32 bits; layer '%s' has %lld elements", l.scope.c_str(), (long long)n_el);
-                    p.mask_bits = d_mask_bits + off / 32;
-                }
-                // element index of this call's first output element in the logical batch's [S,h,w,c] tensor (the counter hash);
-                // injected bits are indexed inside THIS call's tensor, whatever byolo_set_first_image says
-                p.idx_base = inject ? 0 : sample_base(h, l.stacked ? T : 1, l.stacked) * (uint64_t)l.H * l.W * l.filters;
-                p.scale = dptr(h, l.scalek_off);             // scale / (1 - p)
-            }
-            if (l.fused_residual >= 0) {
-                p.flags |= EPI_RESIDUAL;
+        fill_conv(h, s, d_img, ws, B, T, p);                    // (STEP_PARTIAL keeps its raw epilogue: partial sums for the STEP_MAIN launch)
+        if (s.mode != STEP_PARTIAL) {
+            int32_t rc = layer_epi(h, s.layer, a, p.epi); if (rc) return rc;
+            if (l.op == OP_CONV && l.fused_residual >= 0) {
+                p.epi.flags |= EPI_RESIDUAL;
                 p.residual = reinterpret_cast<const float*>(ws + h->plan.off[h->layers[l.fused_residual].ref[0]]);
             }
         }
-        if (s.mode == STEP_PARTIAL) p.flags = EPI_RAW;          // raw partial sums for the STEP_MAIN launch
-        if (h->precision == 1) {
-            if (l.op == OP_DETECTION) p.flags |= EPI_F32OUT;    // the decode kernels read plain fp32
-        }
+        if (h->precision == 1 && l.op == OP_DETECTION) p.epi.flags |= EPI_F32OUT;      // the decode kernels read plain fp32
         // tile configuration and split-K of the last partial round: decided per (B, T) in make_plan
         tile = h->plan.tile[si];
         const ConvSplit& sp = h->plan.split[si];
@@ -1211,23 +1210,10 @@ static int32_t enqueue_forward(byolo_t* h, const FwdArgs& a, hipStream_t st, boo
     };
     // a STEP_FINISH step's parameters: what its launch takes, or -- folded into its reader -- what that reader's input transform takes
     auto finish_params = [&](const Step& s, FinishParams& f) -> int32_t {
-        const Layer& l = h->layers[s.layer];
-        byolo_drop_keys keys{0, 0, 0};
-        const bool drop = l.drop_ordinal >= 0 && dropout_on;
-        const uint32_t* bits = nullptr;
-        if (drop) {
-            keys = byolo_layer_keys(seed, (uint32_t)l.drop_ordinal, (double)h->cfg.drop_prob);
-            if (inject) {
-                int64_t n_el = 0;
-                const int64_t off = mask_layout(h, B, T, l.drop_ordinal, &n_el);
-                if (n_el >= ((int64_t)1 << 32)) return fail(h, BYOLO_ERR_ARG, "byolo_forward: injected masks index a dropout tensor with 32 bits; layer '%s' has %lld elements", l.scope.c_str(), (long long)n_el);
-                bits = d_mask_bits + off / 32;
-            }
-        }
-        fill_finish(h, s, ws, B, T, h->precision == 1 ? 2 : 1, drop, keys, bits, inject, f);
-        return BYOLO_OK;
+        fill_finish(h, s, ws, B, T, h->precision == 1 ? 2 : 1, f);
+        return layer_epi(h, s.layer, a, f.epi);
     };
-    // the src_ fields of a convolution whose input transform evaluates the step in front of it (Plan::feed_src)
+    // the feed / src fields of a convolution whose input transform evaluates the step in front of it (Plan::feed_src)
     auto feed_params = [&](size_t pi, WinoParams& w) -> int32_t {
         const Step& ps = h->steps[pi];
         memset(&w, 0, sizeof w);
@@ -1235,15 +1221,11 @@ static int32_t enqueue_forward(byolo_t* h, const FwdArgs& a, hipStream_t st, boo
         if (w.feed == 1) {                                      // the replayed epilogue of the per-image convolution, as its own launch would run it
             ConvParams c; int tile = 0; double algo = 0.0;
             int32_t rc = prep(pi, c, tile, algo); if (rc) return rc;
-            w.src_low = reinterpret_cast<const float*>(ws + h->plan.off[ps.raw_tensor]); w.src_T = T;
-            w.src_scale = c.scale; w.src_shift = c.shift; w.src_flags = c.flags; w.src_k0 = c.k0; w.src_k1 = c.k1; w.src_thr = c.thr;
-            w.src_idx_base = c.idx_base; w.src_mask_bits = c.mask_bits; w.src_status = c.status; w.src_layer_idx = c.layer_idx;
+            w.src_low = reinterpret_cast<const float*>(ws + h->plan.off[ps.raw_tensor]); w.src_T = T; w.src = c.epi;
         } else {
             FinishParams f;
             int32_t rc = finish_params(ps, f); if (rc) return rc;
-            w.src_low = f.low; w.src_part = f.part; w.src_T = f.T;
-            w.src_scale = f.scale; w.src_shift = f.shift; w.src_flags = f.flags; w.src_k0 = f.k0; w.src_k1 = f.k1; w.src_thr = f.thr;
-            w.src_idx_base = f.idx_base; w.src_mask_bits = f.mask_bits; w.src_status = f.status; w.src_layer_idx = f.layer_idx;
+            w.src_low = f.low; w.src_part = f.part; w.src_T = f.T; w.src = f.epi;
         }
         return BYOLO_OK;
     };
@@ -1268,7 +1250,7 @@ static int32_t enqueue_forward(byolo_t* h, const FwdArgs& a, hipStream_t st, boo
         int tile = 0; double algo = 0.0;
         rc = prep(si, p, tile, algo); if (rc) return rc;
         if (h->plan.feed[si] == 1) {                            // the T replays run inside the reader's input transform: raw accumulators, once per image
-            p.flags = EPI_RAW; p.rep = 1; p.scale = h->d_ones; p.shift = h->d_zeros; p.mask_bits = nullptr;
+            p.epi = raw_epi(h, s.layer); p.rep = 1;
             p.dst = reinterpret_cast<float*>(ws + h->plan.off[s.raw_tensor]);
         }
         const ConvSplit& sp = h->plan.split[si];
@@ -1276,9 +1258,8 @@ static int32_t enqueue_forward(byolo_t* h, const FwdArgs& a, hipStream_t st, boo
             // back-to-back: the next step (the 1x1 convolution / detection head that alone reads this output) inside this launch
             ConvParams f; int ftile = 0; double falgo = 0.0;
             rc = prep(si + 1, f, ftile, falgo); if (rc) return rc;
-            p.f_wpk = f.wpk; p.f_w_bytes = f.w_bytes; p.f_scale = f.scale; p.f_shift = f.shift; p.f_dst = f.dst;
-            p.f_N = f.N; p.f_Npad = f.Npad; p.f_ldc = f.ldc; p.f_flags = f.flags; p.f_layer_idx = f.layer_idx;
-            p.f_k0 = f.k0; p.f_k1 = f.k1; p.f_thr = f.thr; p.f_idx_base = f.idx_base; p.f_mask_bits = f.mask_bits;
+            p.f_wpk = f.wpk; p.f_w_bytes = f.w_bytes; p.f_epi = f.epi; p.f_dst = f.dst;
+            p.f_N = f.N; p.f_Npad = f.Npad; p.f_ldc = f.ldc;
             if (per_step) { rc = mark_launch(h, s.layer, 4256, p.M, l.filters, (int64_t)l.ksize * l.ksize * (s.c_hi - s.c_lo), algo + falgo, st, 1, 0); if (rc) return rc; }
             HIPCHK(h, launch_conv_igemm(p, tile, st));
             ++si;                                               // the follower is done
@@ -1302,9 +1283,8 @@ static int32_t enqueue_forward(byolo_t* h, const FwdArgs& a, hipStream_t st, boo
             q.RT = R + 1;                                       // one weight matrix for all rows
             q.slots = 512 / q.n_tiles; q.q = R / q.slots; q.rem = R % q.slots;
             q.d_ntiles = make_fastdiv((uint32_t)q.n_tiles); q.d_RT = make_fastdiv((uint32_t)q.RT);
-            q.epi = l.op == OP_DETECTION ? 2 : 1; q.M = p.M; q.Npad = p.Npad; q.ldc = p.ldc;
-            q.scale = p.scale; q.shift = p.shift; q.addend = p.addend; q.hw = l.H * l.W;
-            q.flags = p.flags; q.k0 = p.k0; q.k1 = p.k1; q.thr = p.thr; q.idx_base = p.idx_base;
+            q.kind = l.op == OP_DETECTION ? 2 : 1; q.M = p.M; q.Npad = p.Npad; q.ldc = p.ldc;
+            q.epi = p.epi; q.addend = p.addend; q.hw = l.H * l.W;
             q.d_hw = p.d_hw; q.d_addT = p.d_addT;
             if (per_step) { rc = mark_launch(h, s.layer, bn == 64 ? 132 : 131, p.M, l.filters, p.C0, algo, st); if (rc) return rc; }
             HIPCHK(h, launch_gemm_stream(q, st));
@@ -1567,6 +1547,7 @@ static int32_t calibrate_bn_impl(byolo_t* h, const float* d_img, int32_t B, void
     float* d_mean = reinterpret_cast<float*>(ws + h->plan.stats_off + (size_t)1024 * 2 * h->maxC * sizeof(double));
     float* d_var = d_mean + h->maxC;
     std::vector<float> sc, sf;
+    const FwdArgs cal{d_img, B, 1, 0, 0, nullptr, d_workspace, nullptr, nullptr, nullptr, nullptr};      // a call without dropout
     if (h->precision == 1 && h->img_split)
         HIPCHK(h, launch_f32_to_split(d_img, reinterpret_cast<float*>(ws + h->plan.img_split_off), (int64_t)B * h->cfg.img_h * h->cfg.img_w * h->cfg.img_c, ACT_SCALE, st));
     for (const Step& s : h->steps) {
@@ -1574,7 +1555,7 @@ static int32_t calibrate_bn_impl(byolo_t* h, const float* d_img, int32_t B, void
         const bool split = h->precision == 1;
         ConvParams p;
         if (s.mode == STEP_FINISH) {                                       // the raw sum of the two halves, then the statistics below
-            FinishParams f; fill_finish(h, s, ws, B, 1, 0, false, byolo_drop_keys{0, 0, 0}, nullptr, false, f);
+            FinishParams f; fill_finish(h, s, ws, B, 1, 0, f);
             HIPCHK(h, launch_finish_upsampled(f, st));
             p.dst = f.dst; p.M = f.S * f.H * f.W;
         } else {
@@ -1583,9 +1564,9 @@ static int32_t calibrate_bn_impl(byolo_t* h, const float* d_img, int32_t B, void
         const int ctile = split ? conv_split_tile(s.tile, s.kx3 || s.p1) : s.tile;
         // (a head over input channels that are no multiple of 32 is a direct convolution like any other: the matrix-pipe launcher
         //  divides by its 0 K-tiles)
-        if (l.op == OP_DETECTION) { if (split) p.flags |= EPI_F32OUT; HIPCHK(h, l.direct ? launch_conv_direct(p, st) : launch_conv_igemm(p, ctile, st)); continue; }
+        if (l.op == OP_DETECTION) { rc = layer_epi(h, s.layer, cal, p.epi); if (rc) return rc; if (split) p.epi.flags |= EPI_F32OUT; HIPCHK(h, l.direct ? launch_conv_direct(p, st) : launch_conv_igemm(p, ctile, st)); continue; }
         // raw conv output (+ addend for STEP_MAIN), fp32; split precision: the accumulators, ACT_SCALE * 2^wshift * conv
-        p.scale = h->d_ones; p.shift = h->d_zeros; p.flags = split ? (s.mode == STEP_PARTIAL ? EPI_RAW : EPI_F32OUT) : 0;
+        p.epi.flags = split ? (s.mode == STEP_PARTIAL ? EPI_RAW : EPI_F32OUT) : 0;
         if (split && l.direct) p.split &= 1;                               // direct launch: plain fp32 output here
         HIPCHK(h, l.direct ? launch_conv_direct(p, st) : launch_conv_igemm(p, ctile, st));
         if (s.mode == STEP_PARTIAL) continue;                              // half of a split conv: statistics at STEP_MAIN / STEP_FINISH

@@ -23,6 +23,25 @@ inline hipError_t set_dynamic_lds_once(const void* fn, size_t bytes, std::atomic
 
 enum : int { EPI_LEAKY = 1, EPI_DROPOUT = 2, EPI_RESIDUAL = 4, EPI_RAW = 8 /* store the accumulators as they are */,
               EPI_F32OUT = 16 /* split-f16 launch: plain fp32 output (detection heads) */ };
+// What every kernel that finishes a convolution takes from the host besides its operands: the ONE description of an epilogue
+// (byolo_api.hip layer_epi / raw_epi write it; every parameter struct below embeds it whole).  A kernel without an injection
+// path -- the fp32 128-wide igemm tile, gemm_stream, wino_fused, the winograd output transform -- never sees mask_bits != nullptr:
+// the planner does not plan it for an injecting call (byolo_plan.hip make_plan: `inject` turns the fp32 128 x 128 tile into 128 x 64,
+// opts.winograd and opts.stream1x1 off, and fuses no back-to-back pair, whose follower has no such path either).
+struct EpiArgs {
+    const float* scale; const float* shift;   // per output channel
+    // injected dropout masks (byolo_forward's d_mask_bits; lib_yolo/layers.py:521-524 with the caller's own Bernoulli draw):
+    // bit i decides element i of THIS CALL's dropout input [S,h,w,cout] (1 = keep; < 2^32 elements, idx_base = 0);
+    // null = the counter hash
+    const uint32_t* mask_bits;
+    // numeric status of the handle (byolo_status): status[0] |= 1 when a split-f16 output leaves the fp16 range,
+    // status[1] = min(status[1], layer_idx) -- the first layer it happened in; null = not tracked
+    unsigned* status;
+    uint64_t idx_base;                // dropout element index of dst[0] (sub-batch / shard of a logical batch)
+    uint32_t k0, k1, thr;             // dropout keys (byolo_rng.h)
+    int flags;                        // EPI_*
+    int layer_idx;
+};
 
 // n / d for n < 2^31 as (umulhi(n, mul) + n) >> shr: the kernels divide by launch constants only
 // (h*w, w, T, #column tiles), and a 32-bit integer division costs ~30 vector-ALU instructions that
@@ -53,7 +72,7 @@ struct ConvParams {
     uint32_t src0_bytes, src1_bytes;  // extent of each source (buffer descriptor range)
     const float* wpk;                 // packed weights [K/32][Npad][32]   (direct kernel: HWIO as is)
     uint32_t w_bytes;
-    const float* scale; const float* shift;   // per output channel
+    EpiArgs epi;
     const float* residual;            // [M][ldc] or null
     const float* addend;             // [B*hw][N] raw partial sums joined before scale (T-invariant half), or null
     int addend_T;                     // samples per image of THIS launch's rows (1 if rows are images)
@@ -67,20 +86,10 @@ struct ConvParams {
     int ksize, stride, pad;
     int M, N, Npad, ldc;
     int KT, cin_tiles;                // K/32, (C0+C1)/32
-    int flags;                        // EPI_*
     int split;                        // matrix-pipe launch: 1 = split-f16 sources / weights / residual / output (mfma_pipe.h), 0 = fp32;
                                       // direct launch: bit 0 = sources and residual are hi/lo tensors, bit 1 = the output is
     int kx3;                          // split launch: 1 = 3x3 / stride 1 on shared-tap stages (conv_tile_kx3): weights packed in (ky, chunk, kx) order, KT counts
                                       // stages; 2 = 1x1 / stride 1 over one plain source on the uniform loop (conv_tile_p1)
-    uint32_t k0, k1, thr;             // dropout keys (byolo_rng.h)
-    uint64_t idx_base;                // dropout element index of dst[0] (sub-batch / shard of a logical batch)
-    // injected dropout masks (byolo_forward's d_mask_bits; lib_yolo/layers.py:521-524 with the caller's own Bernoulli draw):
-    // bit i decides element i of THIS CALL's dropout input [S,h,w,cout] (1 = keep; < 2^32 elements, idx_base = 0);
-    // null = the counter hash
-    const uint32_t* mask_bits;
-    // numeric status of the handle (byolo_status): status[0] |= 1 when a split-f16 output leaves the fp16 range,
-    // status[1] = min(status[1], layer) -- the first layer it happened in; null = not tracked
-    unsigned* status; int layer_idx;
     // set by launch_conv_igemm: a split-f16 launch whose epilogue is the plain case -- no addend, residual, T-replay, raw / fp32 output
     // or injected masks, cout % 32 == 0, 16-byte rows -- and may run the straight-line epilogue (conv_igemm.hip finish_plain)
     int plain;
@@ -108,11 +117,9 @@ struct ConvParams {
     // writes its hi/lo rows into LDS instead of memory, a second MFMA pass multiplies them with the follower's weights, the
     // follower's epilogue stores.  f_wpk == null: no follower.  The f_ fields are the follower's ConvParams fields of the same name.
     const float* f_wpk; uint32_t f_w_bytes;
-    const float* f_scale; const float* f_shift;
+    EpiArgs f_epi;
     float* f_dst;
-    int f_N, f_Npad, f_ldc, f_flags, f_layer_idx;
-    uint32_t f_k0, f_k1, f_thr; uint64_t f_idx_base;
-    const uint32_t* f_mask_bits;
+    int f_N, f_Npad, f_ldc;
 };
 
 // Winograd F(2x2, 3x3) transforms around the GEMM (winograd.hip)
@@ -120,23 +127,20 @@ struct WinoParams {
     const float* x; float* v;         // input [S,H,W,C];  V [16][P_pad][C] (this chunk)
     const float* m; float* y;         // M [16][P_pad][N] (this chunk);  output [S,H,W,N]
     const float* residual;            // [S,H,W,N] or null
-    const float* scale; const float* shift;
+    EpiArgs epi;                      // of the output transform
     int H, W, C, N, th, tw;           // th, tw = ceil(H/2), ceil(W/2) output tiles per image
     int s0;                           // first sample of the chunk
     int P, P_pad;                     // tiles of the chunk (samples * th * tw), rounded up to 128
-    int flags; uint32_t k0, k1, thr; uint64_t idx_base;
     FastDiv d_tt, d_tw, d_c4, d_n4;   // th*tw, tw, C/4, N/4
     float vmul;                       // split precision (wino_split.hip): V = vmul * (B^T d B) of the stored hi + lo values
     // split precision, wino_split.hip: the input transform evaluates the element-wise pass in front of the convolution itself (feed != 0;
-    // byolo_plan.hip Plan::feed) -- x is not read; the value at (sample s, y, x) is that pass's epilogue, with ITS scale / shift /
-    // dropout keys / element index / status words, passed through the hi/lo encoding in registers:
+    // byolo_plan.hip Plan::feed) -- x is not read; the value at (sample s, y, x) is that pass's epilogue (`src`: ITS scale / shift /
+    // dropout keys / element index / status words), passed through the hi/lo encoding in registers:
     //   1  the T-fold replay of a per-image convolution: src_low = its raw accumulators [images, H, W, C], sample s reads image s / src_T
     //   2  the finish of a 1x1 convolution over an upsampled source (FinishParams): src_low [S, H/2, W/2, C] + src_part [S / src_T, H, W, C] (or null)
     int feed, src_T;
     const float* src_low; const float* src_part;
-    const float* src_scale; const float* src_shift;
-    int src_flags; uint32_t src_k0, src_k1, src_thr; uint64_t src_idx_base; const uint32_t* src_mask_bits;
-    unsigned* src_status; int src_layer_idx;
+    EpiArgs src;
 };
 // Winograd F(2x2,3x3) in split-f16 arithmetic (wino_split.hip): V [16][P_pad x C, K-tile major inside a plane: v_index()] as hi/lo groups -> output [S,H,W,N] as hi/lo
 // groups, GEMM + output transform + epilogue in one launch of P_pad / 128 * N / 128 workgroups
@@ -146,7 +150,7 @@ struct WinoSplitParams {
     const float* w; uint32_t w_bytes;     // U: 16 * C / 32 K-tiles in (point, chunk) order, split-f16 fragment order (mfma_pipe.h)
     float* y;                             // output [S,H,W,N], hi/lo groups
     const float* residual;                // [S,H,W,N] hi/lo groups, added after the activation (layers.py:505-507), or null; not together with dropout
-    const float* scale; const float* shift;
+    EpiArgs epi;
     int C, N, KT, n_tiles;                // KT = C / 32 (a multiple of 4), n_tiles = N / bn
     int H, W, th, tw, s0, P, P_pad;       // as WinoParams
     int bm, bn;                           // output tiles / channels per workgroup: 64 (P_pad is a multiple of it), 128 | 256
@@ -154,16 +158,14 @@ struct WinoSplitParams {
                                           // 2 they claim the next unit of their XCD from `claims` (8 words, zero before the launch)
     unsigned* claims;
     int units;                            // P_pad / bm * n_tiles units of (64 output tiles, bn channels)
-    int flags; uint32_t k0, k1, thr; uint64_t idx_base; const uint32_t* mask_bits;
-    unsigned* status; int layer_idx;
     FastDiv d_ntiles, d_tt, d_tw;
 };
 bool wino_split_ok(int C, int N);
 hipError_t launch_wino_split_input(const WinoParams& p, hipStream_t st);
 hipError_t launch_wino_split(const WinoSplitParams& p, hipStream_t st);
-// Row-streaming persistent GEMM (gemm_stream.hip): the Winograd-domain GEMM (epi 0: 16 row blocks of RT row tiles, one
-// weight matrix each, raw accumulators out), a 1x1 / stride-1 convolution with its fused epilogue (epi 1), or a
-// detection head (epi 2: + bias, any cout)
+// Row-streaming persistent GEMM (gemm_stream.hip): the Winograd-domain GEMM (kind 0: 16 row blocks of RT row tiles, one
+// weight matrix each, raw accumulators out), a 1x1 / stride-1 convolution with its fused epilogue (kind 1), or a
+// detection head (kind 2: + bias, any cout)
 struct GemmStreamParams {
     const float* a; uint32_t a_bytes;     // A: [rows][C] (rows beyond a_bytes read 0)
     const float* w; uint32_t w_bytes;     // weight matrices, each packed [C/32][Npad][32], wstride bytes apart
@@ -173,10 +175,9 @@ struct GemmStreamParams {
     int slots, q, rem;                    // 512 / n_tiles row ranges of q (+1 for the first rem) row tiles
     uint32_t wstride;
     FastDiv d_ntiles, d_RT;
-    int epi, M, Npad, ldc;                // epilogue kind; valid rows (epi != 0); weight rows per K-tile; dst row stride
-    const float* scale; const float* shift;
-    const float* addend; int hw;          // epi 1: raw partial sums [images*hw][N] joined before scale, or null; h*w
-    int flags; uint32_t k0, k1, thr; uint64_t idx_base;      // EPI_LEAKY / EPI_DROPOUT; dropout keys (byolo_rng.h)
+    int kind, M, Npad, ldc;               // epilogue kind; valid rows (kind != 0); weight rows per K-tile; dst row stride
+    EpiArgs epi;                          // kind 1: EPI_LEAKY / EPI_DROPOUT; kind 2: shift only
+    const float* addend; int hw;          // kind 1: raw partial sums [images*hw][N] joined before scale, or null; h*w
     FastDiv d_hw, d_addT;                 // hw, samples per image of the rows (addend)
 };
 int conv1x1_stream_tile(int M, int C, int N, bool force = false);    // tile width (128 | 64) if a 1x1 convolution of M rows fits the streaming launch, else 0
@@ -185,12 +186,11 @@ struct WinoFusedParams {
     const float* v; uint32_t v_bytes;     // V: [16][P_pad][C]
     const float* w; uint32_t w_bytes;     // 16 matrices, each packed [C/32][N][32]
     float* y; const float* residual;      // output / residual [S,H,W,N]
-    const float* scale; const float* shift;
+    EpiArgs epi;
     int C, N, KT, n_tiles;                // KT = C / 32 (even), n_tiles = N / 64
     int H, W, th, tw, s0, P;              // as WinoParams
     int slots, q, rem;                    // 512 / n_tiles ranges of q (+1 for the first rem) row tiles (128 output tiles each)
     uint32_t xi_stride, wstride;          // bytes between consecutive transform points in V / in the weights
-    int flags; uint32_t k0, k1, thr; uint64_t idx_base;
     FastDiv d_ntiles, d_tt, d_tw;
 };
 bool wino_fused_ok(int C, int N);
@@ -228,9 +228,7 @@ hipError_t launch_conv_direct(const ConvParams& p, hipStream_t st);   // small-c
 struct FinishParams {
     const float* low; const float* part; float* dst;
     int S, H, W, N, T;
-    const float* scale; const float* shift;
-    int flags; uint32_t k0, k1, thr; uint64_t idx_base; const uint32_t* mask_bits;
-    unsigned* status; int layer_idx;
+    EpiArgs epi;
     int mode;                         // 0 the raw fp32 sum (BN calibration), 1 epilogue with fp32 output (fp32 mode), 2 epilogue with hi/lo output
     FastDiv d_hw, d_w, d_n4, d_T;     // (H / 2) * (W / 2), W / 2, N / 4, T
 };

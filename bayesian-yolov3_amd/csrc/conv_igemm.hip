@@ -76,7 +76,7 @@ template <int BM, int BN, int WM, int WN, bool SPLIT>
 __device__ __forceinline__ void finish_tile(const ConvParams& p, float* smem, f32x16 (&acc)[BM / WM / 32][BN / WN / 32],
                                             const uint32_t tile_m, const uint32_t tile_n, const TileShare sh) {
     constexpr int NT = 64 * WM * WN, TM = BM / WM / 32, TN = BN / WN / 32;
-    // injected dropout masks (ConvParams::mask_bits): every build but the fp32 128 x 128 tile, which sits at exactly 256
+    // injected dropout masks (EpiArgs::mask_bits): every build but the fp32 128 x 128 tile, which sits at exactly 256
     // registers and would spill -- byolo_plan.hip plans the 64-wide tile for such a call in the fp32 mode
     constexpr bool INJECT = SPLIT || BN < 128;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -147,9 +147,9 @@ __device__ __forceinline__ void finish_tile(const ConvParams& p, float* smem, f3
     // every lane owns, per 32x32 tile, ONE pixel and 4 groups of 4 CONSECUTIVE channels: NHWC stores
     // (and residual loads) are 16-byte vectors.  The row part of every address (dst, residual, addend,
     // dropout element index) is derived once per row; the (j, g) channel-group part is an immediate.
-    const bool do_leaky = p.flags & EPI_LEAKY, do_drop = p.flags & EPI_DROPOUT, do_res = p.flags & EPI_RESIDUAL;
+    const bool do_leaky = p.epi.flags & EPI_LEAKY, do_drop = p.epi.flags & EPI_DROPOUT, do_res = p.epi.flags & EPI_RESIDUAL;
     const float slope = do_leaky ? 0.1f : 1.f;
-    const bool split_out = !(p.flags & EPI_F32OUT);            // SPLIT: encode the output (everything but a detection head)
+    const bool split_out = !(p.epi.flags & EPI_F32OUT);            // SPLIT: encode the output (everything but a detection head)
     // T-invariant de-duplication (lowering in byolo_api.hip):
     //   rep > 1     the conv ran once per IMAGE (its input does not depend on the MC sample); only the
     //               dropout mask differs between the T samples, so the epilogue is replayed T times and
@@ -159,7 +159,7 @@ __device__ __forceinline__ void finish_tile(const ConvParams& p, float* smem, f3
     const int rep = p.rep;
     const int nb = (int)(tile_n * BN) + wn * TN * 32 + 4 * lh;       // first channel of this lane's (j=0, g=0) group
     // EPI_RAW (the Winograd-domain GEMM): the accumulators are the result; nothing but the 16-byte stores
-    if ((p.flags & EPI_RAW) && ((p.N | p.ldc) & 3) == 0) {
+    if ((p.epi.flags & EPI_RAW) && ((p.N | p.ldc) & 3) == 0) {
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
             const uint32_t m = tile_m * BM + wm * TM * 32 + i * 32 + li;
@@ -204,12 +204,12 @@ __device__ __forceinline__ void finish_tile(const ConvParams& p, float* smem, f3
                 const uint32_t mo = rep > 1 ? (row_img[i] * rep + t) * hw + row_pix[i] : row_m[i];
                 dst_row[i] = p.dst + (size_t)mo * p.ldc + nb;
                 res_row[i] = do_res ? p.residual + (size_t)mo * p.ldc + nb : nullptr;
-                idx_row[i] = p.idx_base + (uint64_t)mo * (uint64_t)p.N + (uint64_t)nb;
+                idx_row[i] = p.epi.idx_base + (uint64_t)mo * (uint64_t)p.N + (uint64_t)nb;
             }
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
                 if (row_m[i] >= (uint32_t)p.M) continue;
-                const epi::DropRow drow(idx_row[i], p.k1);        // VEC: pair index / high-half key word, once per row
+                const epi::DropRow drow(idx_row[i], p.epi.k1);        // VEC: pair index / high-half key word, once per row
                 // VEC: the row's addend (joins before scale) or residual (joins after the activation) values are
                 // fetched up front, all TN*4 groups in flight at once -- a load + wait per group serialises the
                 // epilogue on memory latency (the staging / fragment registers of the K loop are dead here)
@@ -232,8 +232,8 @@ __device__ __forceinline__ void finish_tile(const ConvParams& p, float* smem, f3
                         const int n0 = nb + dn;                               // 4 channels n0 .. n0+3
                         if (n0 >= p.N) continue;
                         // arrays are padded to Npad; with the masks on, scale already holds 1 / (1 - p) (host)
-                        const f32x4 sc4 = *reinterpret_cast<const f32x4*>(p.scale + n0);
-                        const f32x4 sf4 = *reinterpret_cast<const f32x4*>(p.shift + n0);
+                        const f32x4 sc4 = *reinterpret_cast<const f32x4*>(p.epi.scale + n0);
+                        const f32x4 sf4 = *reinterpret_cast<const f32x4*>(p.epi.shift + n0);
                         f32x4 a4;
 #pragma unroll
                         for (int q = 0; q < 4; ++q) a4[q] = acc[i][j][4 * g + q];
@@ -249,17 +249,17 @@ __device__ __forceinline__ void finish_tile(const ConvParams& p, float* smem, f3
                         bool keep[4] = {true, true, true, true};
                         if (do_drop) {
                             if constexpr (VEC) {
-                                if (INJECT && p.mask_bits) {                            // injected masks: bit i of the layer = element i of this call's tensor
+                                if (INJECT && p.epi.mask_bits) {                            // injected masks: bit i of the layer = element i of this call's tensor
                                     // (idx_base is 0 on such a call, the tensor has < 2^32 elements, cout % 4 == 0: byolo_forward checks;
                                     //  element index % 4 == 0: the group's bits sit in one word)
                                     const uint32_t el = drow.el_lo() + (uint32_t)dn;
-                                    const uint32_t w = p.mask_bits[el >> 5] >> (el & 31u);
+                                    const uint32_t w = p.epi.mask_bits[el >> 5] >> (el & 31u);
 #pragma unroll
                                     for (int q = 0; q < 4; ++q) keep[q] = (w >> q) & 1u;
-                                } else epi::keep4(drow, dn, p.k0, p.thr, keep);
+                                } else epi::keep4(drow, dn, p.epi.k0, p.epi.thr, keep);
                             } else {
 #pragma unroll
-                                for (int q = 0; q < 4; ++q) keep[q] = byolo_keep(idx0 + q, p.k0, p.k1, p.thr);
+                                for (int q = 0; q < 4; ++q) keep[q] = byolo_keep(idx0 + q, p.epi.k0, p.epi.k1, p.epi.thr);
                             }
                         }
                         f32x4 v = epi::bn_act4(a4, sc4, sf4, keep, slope);    // slope = 0.1 (leaky) or 1 (linear)
@@ -289,9 +289,9 @@ __device__ __forceinline__ void finish_tile(const ConvParams& p, float* smem, f3
     // float32 tensor (lib_yolo/layers.py:550-574) holds a number.  The lane's largest stored magnitude costs one v_max3 per two
     // values; a hit raises the handle's sticky status word, which byolo_forward / byolo_status turn into BYOLO_ERR_RANGE.
     if constexpr (SPLIT) {
-        if (split_out && p.status && vmax >= 65520.f) {
-            atomicOr(p.status, 1u);
-            atomicMin(p.status + 1, (unsigned)p.layer_idx);
+        if (split_out && p.epi.status && vmax >= 65520.f) {
+            atomicOr(p.epi.status, 1u);
+            atomicMin(p.epi.status + 1, (unsigned)p.epi.layer_idx);
         }
     }
 }
@@ -312,7 +312,7 @@ __device__ __forceinline__ void finish_plain(const ConvParams& p, f32x16 (&acc)[
     constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int wm = wave / WN, wn = wave % WN, li = lane & 31, lh = lane >> 5;
-    const float slope = (p.flags & EPI_LEAKY) ? 0.1f : 1.f;
+    const float slope = (p.epi.flags & EPI_LEAKY) ? 0.1f : 1.f;
     const int nb = (int)(tile_n * BN) + wn * TN * 32 + 4 * lh;
     float vmax = 0.f;
     if constexpr ((ABL & 64) != 0) {              // timing ablation: no epilogue arithmetic, one 16-byte store per accumulator block
@@ -339,8 +339,8 @@ __device__ __forceinline__ void finish_plain(const ConvParams& p, f32x16 (&acc)[
         f32x4 sc4[4], sf4[4];
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            sc4[g] = *reinterpret_cast<const f32x4*>(p.scale + nb + j * 32 + 8 * g);
-            sf4[g] = *reinterpret_cast<const f32x4*>(p.shift + nb + j * 32 + 8 * g);
+            sc4[g] = *reinterpret_cast<const f32x4*>(p.epi.scale + nb + j * 32 + 8 * g);
+            sf4[g] = *reinterpret_cast<const f32x4*>(p.epi.shift + nb + j * 32 + 8 * g);
         }
         f32x4 res[RES ? TM : 1][4];
         if constexpr (RES) {
@@ -354,8 +354,8 @@ __device__ __forceinline__ void finish_plain(const ConvParams& p, f32x16 (&acc)[
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
             if (row_m[i] >= (uint32_t)p.M) continue;
-            const uint64_t idx_row = p.idx_base + (uint64_t)row_m[i] * (uint64_t)p.N + (uint64_t)nb;
-            const epi::DropRow drow(idx_row, p.k1);
+            const uint64_t idx_row = p.epi.idx_base + (uint64_t)row_m[i] * (uint64_t)p.N + (uint64_t)nb;
+            const epi::DropRow drow(idx_row, p.epi.k1);
             float* d = p.dst + (size_t)row_m[i] * p.ldc + nb;
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
@@ -364,7 +364,7 @@ __device__ __forceinline__ void finish_plain(const ConvParams& p, f32x16 (&acc)[
 #pragma unroll
                 for (int q = 0; q < 4; ++q) a4[q] = acc[i][j][4 * g + q];
                 bool keep[4] = {true, true, true, true};
-                if constexpr (DROP) epi::keep4(drow, dn, p.k0, p.thr, keep);
+                if constexpr (DROP) epi::keep4(drow, dn, p.epi.k0, p.epi.thr, keep);
                 f32x4 v = epi::bn_act4_pk(a4, sc4[g], sf4[g], keep, slope);
                 if constexpr (RES) v += epi::split_decode4(res[i][g]);
                 vmax = epi::absmax4(vmax, v);
@@ -372,7 +372,7 @@ __device__ __forceinline__ void finish_plain(const ConvParams& p, f32x16 (&acc)[
             }
         }
     }
-    if (p.status && vmax >= 65520.f) { atomicOr(p.status, 1u); atomicMin(p.status + 1, (unsigned)p.layer_idx); }
+    if (p.epi.status && vmax >= 65520.f) { atomicOr(p.epi.status, 1u); atomicMin(p.epi.status + 1, (unsigned)p.epi.layer_idx); }
 }
 // the end of a tile of a split-f16 launch: the straight-line epilogue where the launch and the tile allow it
 // (WITH_RES = false: a kernel that never sees a residual -- the 8-wave tile of the head layers -- does not carry that instantiation,
@@ -380,11 +380,11 @@ __device__ __forceinline__ void finish_plain(const ConvParams& p, f32x16 (&acc)[
 template <int BM, int BN, int WM, int WN, bool WITH_RES = true>
 __device__ __forceinline__ void finish_split(const ConvParams& p, float* smem, f32x16 (&acc)[BM / WM / 32][BN / WN / 32],
                                              const uint32_t tile_m, const uint32_t tile_n, const TileShare sh) {
-    if (p.plain && sh.counter < 0 && (WITH_RES || !(p.flags & EPI_RESIDUAL))) {
+    if (p.plain && sh.counter < 0 && (WITH_RES || !(p.epi.flags & EPI_RESIDUAL))) {
         if constexpr (WITH_RES) {
-            if (p.flags & EPI_RESIDUAL) { finish_plain<BM, BN, WM, WN, false, true>(p, acc, tile_m, tile_n); return; }      // (never with dropout: conv_epilogue_is_plain)
+            if (p.epi.flags & EPI_RESIDUAL) { finish_plain<BM, BN, WM, WN, false, true>(p, acc, tile_m, tile_n); return; }      // (never with dropout: conv_epilogue_is_plain)
         }
-        if (p.flags & EPI_DROPOUT) finish_plain<BM, BN, WM, WN, true>(p, acc, tile_m, tile_n);
+        if (p.epi.flags & EPI_DROPOUT) finish_plain<BM, BN, WM, WN, true>(p, acc, tile_m, tile_n);
         else finish_plain<BM, BN, WM, WN, false>(p, acc, tile_m, tile_n);
     } else finish_tile<BM, BN, WM, WN, true>(p, smem, acc, tile_m, tile_n, sh);
 }
@@ -632,20 +632,20 @@ __device__ __forceinline__ void fused_tail(const ConvParams& p, float* smem, f32
     //  leaky(shift) -- their operand rows were zeros -- which the follower multiplies and never stores)
     auto to_lds = [&](auto drop_tag) {
         constexpr bool DROP = decltype(drop_tag)::value;
-        const float slope = (p.flags & EPI_LEAKY) ? 0.1f : 1.f;
+        const float slope = (p.epi.flags & EPI_LEAKY) ? 0.1f : 1.f;
         const int nb = wave * 32 + 4 * lh;                    // first channel of the lane's group g = 0
         float vmax = 0.f;
         f32x4 sc4[4], sf4[4];
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            sc4[g] = *reinterpret_cast<const f32x4*>(p.scale + nb + 8 * g);
-            sf4[g] = *reinterpret_cast<const f32x4*>(p.shift + nb + 8 * g);
+            sc4[g] = *reinterpret_cast<const f32x4*>(p.epi.scale + nb + 8 * g);
+            sf4[g] = *reinterpret_cast<const f32x4*>(p.epi.shift + nb + 8 * g);
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const uint32_t rr = (uint32_t)(i * 32 + li), m = tile_m * BM + rr;
-            const uint64_t idx_row = p.idx_base + (uint64_t)m * (uint64_t)p.N + (uint64_t)nb;
-            const epi::DropRow drow(idx_row, p.k1);
+            const uint64_t idx_row = p.epi.idx_base + (uint64_t)m * (uint64_t)p.N + (uint64_t)nb;
+            const epi::DropRow drow(idx_row, p.epi.k1);
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int dn = 8 * g;
@@ -653,7 +653,7 @@ __device__ __forceinline__ void fused_tail(const ConvParams& p, float* smem, f32
 #pragma unroll
                 for (int q = 0; q < 4; ++q) a4[q] = acc[i][0][4 * g + q];
                 bool keep[4] = {true, true, true, true};
-                if constexpr (DROP) epi::keep4(drow, dn, p.k0, p.thr, keep);     // (injected masks: the planner does not fuse such a call)
+                if constexpr (DROP) epi::keep4(drow, dn, p.epi.k0, p.epi.thr, keep);     // (injected masks: the planner does not fuse such a call)
                 const f32x4 v = epi::bn_act4_pk(a4, sc4[g], sf4[g], keep, slope);
                 vmax = epi::absmax4(vmax, v);
                 const f32x4 e = epi::split_encode4(v);
@@ -664,9 +664,9 @@ __device__ __forceinline__ void fused_tail(const ConvParams& p, float* smem, f32
                 *reinterpret_cast<f32x2*>(at + 64) = f32x2{e[2], e[3]};
             }
         }
-        if (p.status && vmax >= 65520.f) { atomicOr(p.status, 1u); atomicMin(p.status + 1, (unsigned)p.layer_idx); }
+        if (p.epi.status && vmax >= 65520.f) { atomicOr(p.epi.status, 1u); atomicMin(p.epi.status + 1, (unsigned)p.epi.layer_idx); }
     };
-    if (p.flags & EPI_DROPOUT) to_lds(std::true_type{}); else to_lds(std::false_type{});
+    if (p.epi.flags & EPI_DROPOUT) to_lds(std::true_type{}); else to_lds(std::false_type{});
     __syncthreads();
     // ---- the follower's GEMM: [128 x 256] x [256 x N2] ---------------------------------------------------------------------
     const BT2 bt(smem, tid);
@@ -704,38 +704,38 @@ __device__ __forceinline__ void fused_tail(const ConvParams& p, float* smem, f32
     // sample per row -- the planner fuses nothing else); dropout and the output encoding decided once per tile ------------------------
     auto follower = [&](auto drop_tag, auto split_tag) {
         constexpr bool DROP = decltype(drop_tag)::value, SPLIT_OUT = decltype(split_tag)::value;
-        const float slope = (p.f_flags & EPI_LEAKY) ? 0.1f : 1.f;
+        const float slope = (p.f_epi.flags & EPI_LEAKY) ? 0.1f : 1.f;
         const int nb = bt.wn * 32 + 4 * lh;
         float vmax = 0.f;
 #pragma unroll
         for (int i = 0; i < TM2; ++i) {
             const uint32_t m = tile_m * BM + (uint32_t)((bt.wm * TM2 + i) * 32 + li);
             if (m >= (uint32_t)p.M) continue;
-            const uint64_t idx_row = p.f_idx_base + (uint64_t)m * (uint64_t)p.f_N + (uint64_t)nb;
-            const epi::DropRow drow(idx_row, p.f_k1);
+            const uint64_t idx_row = p.f_epi.idx_base + (uint64_t)m * (uint64_t)p.f_N + (uint64_t)nb;
+            const epi::DropRow drow(idx_row, p.f_epi.k1);
             float* d = p.f_dst + (size_t)m * p.f_ldc + nb;
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int dn = 8 * g, n0 = nb + dn;
                 if (n0 >= p.f_N) continue;
-                const f32x4 sc4 = *reinterpret_cast<const f32x4*>(p.f_scale + n0);
-                const f32x4 sf4 = *reinterpret_cast<const f32x4*>(p.f_shift + n0);
+                const f32x4 sc4 = *reinterpret_cast<const f32x4*>(p.f_epi.scale + n0);
+                const f32x4 sf4 = *reinterpret_cast<const f32x4*>(p.f_epi.shift + n0);
                 f32x4 a4;
 #pragma unroll
                 for (int q = 0; q < 4; ++q) a4[q] = acc2[i][0][4 * g + q];
                 bool keep[4] = {true, true, true, true};
-                if constexpr (DROP) epi::keep4(drow, dn, p.f_k0, p.f_thr, keep);
+                if constexpr (DROP) epi::keep4(drow, dn, p.f_epi.k0, p.f_epi.thr, keep);
                 const f32x4 v = epi::bn_act4_pk(a4, sc4, sf4, keep, slope);
                 if constexpr (SPLIT_OUT) vmax = epi::absmax4(vmax, v);
                 if constexpr (SPLIT_OUT) *reinterpret_cast<f32x4*>(d + dn) = epi::split_encode4(v);
                 else *reinterpret_cast<f32x4*>(d + dn) = v;
             }
         }
-        if (SPLIT_OUT && p.status && vmax >= 65520.f) { atomicOr(p.status, 1u); atomicMin(p.status + 1, (unsigned)p.f_layer_idx); }
+        if (SPLIT_OUT && p.epi.status && vmax >= 65520.f) { atomicOr(p.epi.status, 1u); atomicMin(p.epi.status + 1, (unsigned)p.f_epi.layer_idx); }
     };
-    if (p.f_flags & EPI_F32OUT) {                 // a detection head: plain fp32 rows
-        if (p.f_flags & EPI_DROPOUT) follower(std::true_type{}, std::false_type{}); else follower(std::false_type{}, std::false_type{});
-    } else if (p.f_flags & EPI_DROPOUT) follower(std::true_type{}, std::true_type{});
+    if (p.f_epi.flags & EPI_F32OUT) {                 // a detection head: plain fp32 rows
+        if (p.f_epi.flags & EPI_DROPOUT) follower(std::true_type{}, std::false_type{}); else follower(std::false_type{}, std::false_type{});
+    } else if (p.f_epi.flags & EPI_DROPOUT) follower(std::true_type{}, std::true_type{});
     else follower(std::false_type{}, std::true_type{});
 }
 
@@ -1133,8 +1133,8 @@ size_t conv_split_slab_bytes(const ConvSplit& sp, int tile) {
 // ConvParams::plain (finish_plain)
 static bool conv_epilogue_is_plain(const ConvParams& p) {
     // (p.no_plain: byolo_plan_opts.plain_epilogue = 0 -- finish_tile everywhere, the A/B of tests/test_gpu_parity.py)
-    return !p.no_plain && p.split == 1 && !p.addend && p.rep <= 1 && !(p.flags & (EPI_F32OUT | EPI_RAW)) && !p.mask_bits &&
-           !((p.flags & EPI_RESIDUAL) && (p.flags & EPI_DROPOUT)) && ((p.N | p.ldc) & 3) == 0 && (p.N % 32) == 0;
+    return !p.no_plain && p.split == 1 && !p.addend && p.rep <= 1 && !(p.epi.flags & (EPI_F32OUT | EPI_RAW)) && !p.epi.mask_bits &&
+           !((p.epi.flags & EPI_RESIDUAL) && (p.epi.flags & EPI_DROPOUT)) && ((p.N | p.ldc) & 3) == 0 && (p.N % 32) == 0;
 }
 
 template <int BM, int BN, int WM, int WN, bool SPLITCFG = false>

@@ -72,20 +72,20 @@ __global__ __launch_bounds__(256) void conv_stem3x3_kernel(const ConvParams p) {
             for (int q = 0; q < 4; ++q) acc[n + q] = fmaf(x[k], w4[q], acc[n + q]);
         }
     __syncthreads();                              // the weights are read out: the rows take their place
-    const float slope = (p.flags & EPI_LEAKY) ? 0.1f : 1.f;
+    const float slope = (p.epi.flags & EPI_LEAKY) ? 0.1f : 1.f;
     float vmax = 0.f;
 #pragma unroll
     for (int n = 0; n < NOUT; n += 4) {
         f32x4 v;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const float y = acc[n + q] * p.scale[n + q] + p.shift[n + q];
+            const float y = acc[n + q] * p.epi.scale[n + q] + p.epi.shift[n + q];
             v[q] = fmaxf(y, slope * y);
         }
         vmax = epi::absmax4(vmax, v);
         *reinterpret_cast<f32x4*>(lds + threadIdx.x * ROWB + n * 4) = (p.split & 2) ? epi::split_encode4(v) : v;    // split precision: [4 hi | 4 lo]
     }
-    if (live && (p.split & 2) && p.status && vmax >= 65520.f) { atomicOr(p.status, 1u); atomicMin(p.status + 1, (unsigned)p.layer_idx); }   // conv_igemm.hip finish_tile
+    if (live && (p.split & 2) && p.epi.status && vmax >= 65520.f) { atomicOr(p.epi.status, 1u); atomicMin(p.epi.status + 1, (unsigned)p.epi.layer_idx); }   // conv_igemm.hip finish_tile
     __syncthreads();
     float* d = p.dst + (size_t)m0 * p.ldc;          // ldc == NOUT (launcher)
 #pragma unroll
@@ -157,16 +157,16 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(const ConvParams p, co
         float res[8];
         for (int o = 0; o < nv; ++o) {
             const int n = g * 8 + o;
-            float v = acc[o] * p.scale[n];                     // scale includes 1 / (1 - p) when the masks are on
-            if (p.flags & EPI_DROPOUT) {
+            float v = acc[o] * p.epi.scale[n];                     // scale includes 1 / (1 - p) when the masks are on
+            if (p.epi.flags & EPI_DROPOUT) {
                 const uint64_t el = (uint64_t)m * (uint64_t)N + (uint64_t)n;
-                const bool keep = p.mask_bits ? ((p.mask_bits[el >> 5] >> (uint32_t)(el & 31u)) & 1u)
-                                              : byolo_keep(p.idx_base + el, p.k0, p.k1, p.thr);
+                const bool keep = p.epi.mask_bits ? ((p.epi.mask_bits[el >> 5] >> (uint32_t)(el & 31u)) & 1u)
+                                              : byolo_keep(p.epi.idx_base + el, p.epi.k0, p.epi.k1, p.epi.thr);
                 if (!keep) v = 0.f;
             }
-            v += p.shift[n];
-            if (p.flags & EPI_LEAKY) v = fmaxf(v, 0.1f * v);
-            if (p.flags & EPI_RESIDUAL) v += act_at(p.residual + (size_t)m * p.ldc, n, in_split);
+            v += p.epi.shift[n];
+            if (p.epi.flags & EPI_LEAKY) v = fmaxf(v, 0.1f * v);
+            if (p.epi.flags & EPI_RESIDUAL) v += act_at(p.residual + (size_t)m * p.ldc, n, in_split);
             res[o] = v;
         }
         if (out_split) {
@@ -176,7 +176,7 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(const ConvParams p, co
                 vmax = epi::absmax4(vmax, v);
                 *reinterpret_cast<f32x4*>(d + o) = epi::split_encode4(v);
             }
-            if (p.status && vmax >= 65520.f) { atomicOr(p.status, 1u); atomicMin(p.status + 1, (unsigned)p.layer_idx); }
+            if (p.epi.status && vmax >= 65520.f) { atomicOr(p.epi.status, 1u); atomicMin(p.epi.status + 1, (unsigned)p.epi.layer_idx); }
         } else {
             for (int o = 0; o < nv; ++o) d[o] = res[o];
         }
@@ -184,7 +184,7 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(const ConvParams p, co
 }
 
 hipError_t launch_conv_direct(const ConvParams& p, hipStream_t st) {
-    if (p.ksize == 3 && p.C0 == 3 && p.C1 == 0 && p.sh0 == 0 && p.N == 32 && (p.flags & ~EPI_LEAKY) == 0 && !(p.split & 1) &&
+    if (p.ksize == 3 && p.C0 == 3 && p.C1 == 0 && p.sh0 == 0 && p.N == 32 && (p.epi.flags & ~EPI_LEAKY) == 0 && !(p.split & 1) &&
         p.ldc == 32 && p.rep == 1 && !p.addend) {
         hipLaunchKernelGGL(conv_stem3x3_kernel<32>, dim3((unsigned)((p.M + 255) / 256)), dim3(256), 0, st, p);
         return hipGetLastError();
@@ -226,8 +226,8 @@ template <int MODE>
 __global__ __launch_bounds__(256) void finish_upsampled_kernel(const FinishParams p) {
     const uint32_t n4 = (uint32_t)p.N >> 2, W = (uint32_t)p.W, hw = (uint32_t)(p.H * p.W), lw = W >> 1, lhw = hw >> 2;
     const uint64_t total = (uint64_t)p.S * lhw * n4;
-    const bool do_drop = p.flags & EPI_DROPOUT;
-    const float slope = (p.flags & EPI_LEAKY) ? 0.1f : 1.f;
+    const bool do_drop = p.epi.flags & EPI_DROPOUT;
+    const float slope = (p.epi.flags & EPI_LEAKY) ? 0.1f : 1.f;
     float vmax = 0.f;
     for (uint64_t gid = (uint64_t)blockIdx.x * 256u + threadIdx.x; gid < total; gid += (uint64_t)gridDim.x * 256u) {
         const uint32_t lm = (uint32_t)(gid / n4), g = (uint32_t)(gid - (uint64_t)lm * n4);        // (rows < 2^31: check_run)
@@ -244,7 +244,7 @@ __global__ __launch_bounds__(256) void finish_upsampled_kernel(const FinishParam
             if (p.part) a4[o] += *reinterpret_cast<const f32x4*>(p.part + (part_img + r[o]) * p.N + 4 * g);
         }
         f32x4 sc4, sf4;
-        if constexpr (MODE != 0) { sc4 = *reinterpret_cast<const f32x4*>(p.scale + 4 * g); sf4 = *reinterpret_cast<const f32x4*>(p.shift + 4 * g); }
+        if constexpr (MODE != 0) { sc4 = *reinterpret_cast<const f32x4*>(p.epi.scale + 4 * g); sf4 = *reinterpret_cast<const f32x4*>(p.epi.shift + 4 * g); }
 #pragma unroll
         for (int o = 0; o < 4; ++o) {
             const size_t m = (size_t)s * hw + r[o];
@@ -252,14 +252,14 @@ __global__ __launch_bounds__(256) void finish_upsampled_kernel(const FinishParam
             if constexpr (MODE == 0) { *reinterpret_cast<f32x4*>(d) = a4[o]; continue; }
             bool keep[4] = {true, true, true, true};
             if (do_drop) {
-                const uint64_t idx = p.idx_base + (uint64_t)m * (uint64_t)p.N + 4u * g;
-                const epi::DropRow drow(idx, p.k1);
-                if (p.mask_bits) {                                      // injected masks (conv_igemm.hip finish_tile)
+                const uint64_t idx = p.epi.idx_base + (uint64_t)m * (uint64_t)p.N + 4u * g;
+                const epi::DropRow drow(idx, p.epi.k1);
+                if (p.epi.mask_bits) {                                      // injected masks (conv_igemm.hip finish_tile)
                     const uint32_t el = drow.el_lo();
-                    const uint32_t w = p.mask_bits[el >> 5] >> (el & 31u);
+                    const uint32_t w = p.epi.mask_bits[el >> 5] >> (el & 31u);
 #pragma unroll
                     for (int q = 0; q < 4; ++q) keep[q] = (w >> q) & 1u;
-                } else epi::keep4(drow, 0, p.k0, p.thr, keep);
+                } else epi::keep4(drow, 0, p.epi.k0, p.epi.thr, keep);
             }
             const f32x4 v = epi::bn_act4(a4[o], sc4, sf4, keep, slope);
             if constexpr (MODE == 2) { vmax = epi::absmax4(vmax, v); st4(d, epi::split_encode4(v)); }
@@ -267,7 +267,7 @@ __global__ __launch_bounds__(256) void finish_upsampled_kernel(const FinishParam
         }
     }
     if constexpr (MODE == 2) {
-        if (p.status && vmax >= 65520.f) { atomicOr(p.status, 1u); atomicMin(p.status + 1, (unsigned)p.layer_idx); }
+        if (p.epi.status && vmax >= 65520.f) { atomicOr(p.epi.status, 1u); atomicMin(p.epi.status + 1, (unsigned)p.epi.layer_idx); }
     }
 }
 hipError_t launch_finish_upsampled(const FinishParams& p, hipStream_t st) {

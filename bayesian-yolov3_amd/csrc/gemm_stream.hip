@@ -107,8 +107,8 @@ __global__ __launch_bounds__(256, 2) void gemm_stream_kernel(const GemmStreamPar
     const int nb = (int)(tile_n * BN) + t.wn * TN * 32 + 4 * t.lh;
     uint32_t row_tile = r0;
     const uint32_t hw = (uint32_t)p.hw;
-    const bool do_drop = p.flags & EPI_DROPOUT;
-    const float slope = (p.flags & EPI_LEAKY) ? 0.1f : 1.f;
+    const bool do_drop = p.epi.flags & EPI_DROPOUT;
+    const float slope = (p.epi.flags & EPI_LEAKY) ? 0.1f : 1.f;
     auto flush = [&]() {                          // one finished row tile
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
@@ -134,7 +134,7 @@ __global__ __launch_bounds__(256, 2) void gemm_stream_kernel(const GemmStreamPar
 #pragma unroll
                             for (int q = 0; q < 4; ++q) {
                                 const int n = nb + j * 32 + 8 * g + q;
-                                if (n < p.N) d[j * 32 + 8 * g + q] = acc[i][j][4 * g + q] + p.shift[n];
+                                if (n < p.N) d[j * 32 + 8 * g + q] = acc[i][j][4 * g + q] + p.epi.shift[n];
                             }
                 } else {
                     // N % 4 == 0: a lane's 4-channel group is entirely inside or outside N, its element index is a
@@ -144,7 +144,7 @@ __global__ __launch_bounds__(256, 2) void gemm_stream_kernel(const GemmStreamPar
                         const uint32_t img = fdiv(m, p.d_hw), pix = m - img * hw;
                         add_row = p.addend + (size_t)(fdiv(img, p.d_addT) * hw + pix) * p.N + nb;
                     }
-                    const epi::DropRow drow(p.idx_base + (uint64_t)m * (uint64_t)p.N + (uint64_t)nb, p.k1);
+                    const epi::DropRow drow(p.epi.idx_base + (uint64_t)m * (uint64_t)p.N + (uint64_t)nb, p.epi.k1);
                     f32x4 extra[TN * 4];
                     if (add_row) {
 #pragma unroll
@@ -159,14 +159,14 @@ __global__ __launch_bounds__(256, 2) void gemm_stream_kernel(const GemmStreamPar
                         for (int g = 0; g < 4; ++g) {
                             const int dn = j * 32 + 8 * g, n0 = nb + dn;
                             if (n0 >= p.N) continue;
-                            const f32x4 sc4 = *reinterpret_cast<const f32x4*>(p.scale + n0);   // x 1 / (1 - p) with the masks on (host)
-                            const f32x4 sf4 = *reinterpret_cast<const f32x4*>(p.shift + n0);
+                            const f32x4 sc4 = *reinterpret_cast<const f32x4*>(p.epi.scale + n0);   // x 1 / (1 - p) with the masks on (host)
+                            const f32x4 sf4 = *reinterpret_cast<const f32x4*>(p.epi.shift + n0);
                             f32x4 a4;
 #pragma unroll
                             for (int q = 0; q < 4; ++q) a4[q] = acc[i][j][4 * g + q];
                             if (add_row) a4 += extra[j * 4 + g];
                             bool keep[4] = {true, true, true, true};
-                            if (do_drop) epi::keep4(drow, dn, p.k0, p.thr, keep);
+                            if (do_drop) epi::keep4(drow, dn, p.epi.k0, p.epi.thr, keep);
                             *reinterpret_cast<f32x4*>(d + dn) = epi::bn_act4(a4, sc4, sf4, keep, slope);
                         }
                 }
@@ -223,8 +223,8 @@ static hipError_t launch_gs(const GemmStreamParams& p, hipStream_t st) {
 }
 
 hipError_t launch_gemm_stream(const GemmStreamParams& p, hipStream_t st) {
-    if (p.epi == GS_RAW) return launch_gs<128, GS_RAW>(p, st);
-    if (p.epi == GS_BIAS) return launch_gs<64, GS_BIAS>(p, st);
+    if (p.kind == GS_RAW) return launch_gs<128, GS_RAW>(p, st);
+    if (p.kind == GS_BIAS) return launch_gs<64, GS_BIAS>(p, st);
     return p.Npad % 128 == 0 ? launch_gs<128, GS_CONV>(p, st) : launch_gs<64, GS_CONV>(p, st);
 }
 

@@ -62,7 +62,7 @@ __global__ __launch_bounds__(256, 2) void wino_fused_kernel(const WinoFusedParam
     // of 4 channels waited on vmcnt -- which also counts the stores of the group before it -- and the epilogue ran at
     // memory latency (32 round trips per row tile).  (Visible after the pipeline's first barrier.)
     if (tid < 2 * BN)
-        reinterpret_cast<float*>(lds + SS_BASE)[tid] = tid < BN ? p.scale[tile_n * BN + tid] : p.shift[tile_n * BN + tid - BN];
+        reinterpret_cast<float*>(lds + SS_BASE)[tid] = tid < BN ? p.epi.scale[tile_n * BN + tid] : p.epi.shift[tile_n * BN + tid - BN];
 
     // ---- load stream: K-tile (row tile, xi, chunk), chunk fastest -----------------------------------------------------
     const int a_q = bt.a_q, a_r = bt.a_r;
@@ -142,8 +142,8 @@ __global__ __launch_bounds__(256, 2) void wino_fused_kernel(const WinoFusedParam
     };
 
     // ---- epilogue of one finished row tile (128 output tiles): lane = tile li (+32 per t), 4 x 4 consecutive channels ----
-    const bool do_drop = p.flags & EPI_DROPOUT, do_res = p.flags & EPI_RESIDUAL;
-    const float slope = (p.flags & EPI_LEAKY) ? 0.1f : 1.f;
+    const bool do_drop = p.epi.flags & EPI_DROPOUT, do_res = p.epi.flags & EPI_RESIDUAL;
+    const float slope = (p.epi.flags & EPI_LEAKY) ? 0.1f : 1.f;
     const int nb = (int)(tile_n * BN) + wn * 32 + 4 * lh;          // first channel of this lane's group g = 0
     const uint32_t tt = (uint32_t)(p.th * p.tw);
     auto epilogue = [&](const uint32_t row_tile) {
@@ -161,7 +161,7 @@ __global__ __launch_bounds__(256, 2) void wino_fused_kernel(const WinoFusedParam
                     const uint64_t pix = ((uint64_t)(p.s0 + s) * p.H + oy) * p.W + ox;
                     const size_t off = (size_t)pix * p.N + nb;
                     // pair index of the pixel's first element here and the key word of its high half: once per pixel
-                    const epi::DropRow drow(p.idx_base + pix * (uint64_t)p.N + (uint64_t)nb, p.k1);
+                    const epi::DropRow drow(p.epi.idx_base + pix * (uint64_t)p.N + (uint64_t)nb, p.epi.k1);
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
                         if constexpr ((WFA & 2) != 0) {
@@ -175,7 +175,7 @@ __global__ __launch_bounds__(256, 2) void wino_fused_kernel(const WinoFusedParam
                         const f32x4 sc = *reinterpret_cast<const f32x4*>(lds + SS_BASE + (wn * 32 + 4 * lh + 8 * g) * 4);
                         const f32x4 sf = *reinterpret_cast<const f32x4*>(lds + SS_BASE + (BN + wn * 32 + 4 * lh + 8 * g) * 4);
                         bool keep[4] = {true, true, true, true};
-                        if (do_drop) epi::keep4(drow, 8 * g, p.k0, p.thr, keep);
+                        if (do_drop) epi::keep4(drow, 8 * g, p.epi.k0, p.epi.thr, keep);
                         f32x4 y4;
 #pragma unroll
                         for (int q = 0; q < 4; ++q) y4[q] = Y[o][t][4 * g + q];

@@ -191,8 +191,8 @@ __global__ __launch_bounds__(256) void wino_split_input2_kernel(const WinoParams
         emit(s, u);
     } else {
         // ---- the producer's epilogue at one position of one sample (gs = the sample's index in the call's [S, H, W, C] tensor) ----
-        const f32x4 sc4 = *reinterpret_cast<const f32x4*>(p.src_scale + c4 * 4), sf4 = *reinterpret_cast<const f32x4*>(p.src_shift + c4 * 4);
-        const float slope = (p.src_flags & EPI_LEAKY) ? 0.1f : 1.f;
+        const f32x4 sc4 = *reinterpret_cast<const f32x4*>(p.src.scale + c4 * 4), sf4 = *reinterpret_cast<const f32x4*>(p.src.shift + c4 * 4);
+        const float slope = (p.src.flags & EPI_LEAKY) ? 0.1f : 1.f;
         float vmax = 0.f;
         // (the element index = the lane's index at patch position (1, 1), always inside the image, + a block-uniform offset per position)
         auto finish = [&](const f32x4 a4, const uint32_t gs, const int i, const int j) __attribute__((always_inline)) -> f32x4 {
@@ -200,13 +200,13 @@ __global__ __launch_bounds__(256) void wino_split_input2_kernel(const WinoParams
             if constexpr (DROP != 0) {
                 const uint64_t pix = ((uint64_t)gs * p.H + (uint32_t)(y0 + 1)) * p.W + (uint32_t)(x0 + 1);
                 const int64_t off = (int64_t)(((i - 1) * p.W + (j - 1)) * p.C);
-                const epi::DropRow drow(p.src_idx_base + pix * (uint64_t)p.C + (uint64_t)(c4 * 4) + (uint64_t)off, p.src_k1);
+                const epi::DropRow drow(p.src.idx_base + pix * (uint64_t)p.C + (uint64_t)(c4 * 4) + (uint64_t)off, p.src.k1);
                 if constexpr (DROP == 2) {                                  // injected masks (conv_igemm.hip finish_tile)
                     const uint32_t el = drow.el_lo();
-                    const uint32_t w = p.src_mask_bits[el >> 5] >> (el & 31u);
+                    const uint32_t w = p.src.mask_bits[el >> 5] >> (el & 31u);
 #pragma unroll
                     for (int k = 0; k < 4; ++k) keep[k] = (w >> k) & 1u;
-                } else epi::keep4(drow, 0, p.src_k0, p.src_thr, keep);
+                } else epi::keep4(drow, 0, p.src.k0, p.src.thr, keep);
             }
             const f32x4 v = epi::bn_act4(a4, sc4, sf4, keep, slope);
             vmax = epi::absmax4(vmax, v);
@@ -279,14 +279,14 @@ __global__ __launch_bounds__(256) void wino_split_input2_kernel(const WinoParams
             }
             emit(s, u);
         }
-        if (p.src_status && vmax >= 65520.f) { atomicOr(p.src_status, 1u); atomicMin(p.src_status + 1, (unsigned)p.src_layer_idx); }
+        if (p.src.status && vmax >= 65520.f) { atomicOr(p.src.status, 1u); atomicMin(p.src.status + 1, (unsigned)p.src.layer_idx); }
     }
 }
 
 template <int FEED>
 static void launch_input_feed(const WinoParams& p, unsigned grid, hipStream_t st, int twp, uint32_t groups, uint32_t img_lo, uint32_t nsl) {
     const FastDiv a = make_fastdiv((uint32_t)twp), b = make_fastdiv((uint32_t)(p.th * twp)), c = make_fastdiv((uint32_t)p.th), d = make_fastdiv(nsl);
-    const int drop = !(p.src_flags & EPI_DROPOUT) ? 0 : (p.src_mask_bits ? 2 : 1);
+    const int drop = !(p.src.flags & EPI_DROPOUT) ? 0 : (p.src.mask_bits ? 2 : 1);
     if constexpr (FEED == 0) hipLaunchKernelGGL((wino_split_input2_kernel<0, 0>), dim3(grid), dim3(256), 0, st, p, a, b, twp, c, groups, img_lo, d, nsl);
     else if (drop == 0) hipLaunchKernelGGL((wino_split_input2_kernel<FEED, 0>), dim3(grid), dim3(256), 0, st, p, a, b, twp, c, groups, img_lo, d, nsl);
     else if (drop == 1) hipLaunchKernelGGL((wino_split_input2_kernel<FEED, 1>), dim3(grid), dim3(256), 0, st, p, a, b, twp, c, groups, img_lo, d, nsl);
@@ -299,7 +299,7 @@ hipError_t launch_wino_split_input(const WinoParams& p, hipStream_t st) {
     uint32_t groups = ns, img_lo = 0, nsl = 1;
     if (p.feed < 0 || p.feed > 2) return hipErrorInvalidValue;
     if (p.feed) {
-        if (!p.src_low || !p.src_scale || !p.src_shift || p.src_T < 1 || ns < 1 || (p.feed == 2 && ((p.H | p.W) & 1))) return hipErrorInvalidValue;
+        if (!p.src_low || !p.src.scale || !p.src.shift || p.src_T < 1 || ns < 1 || (p.feed == 2 && ((p.H | p.W) & 1))) return hipErrorInvalidValue;
     }
     if (p.feed == 1) {                                       // thread groups = (images the chunk touches) x (slices of an image's T samples)
         img_lo = (uint32_t)p.s0 / (uint32_t)p.src_T;
@@ -438,7 +438,7 @@ __global__ __launch_bounds__(WINO_BN * 2, 2) void wino_split_kernel(const WinoSp
     // matrix-pipe time, and a block-uniform branch per channel group costs scalar spills and hazard no-ops (conv_igemm.hip finish_plain)
     auto epilogue = [&](auto mode_tag, uint32_t rt, uint32_t ct) __attribute__((always_inline)) {
         constexpr int MODE = decltype(mode_tag)::value;
-        const float slope = (p.flags & EPI_LEAKY) ? 0.1f : 1.f;
+        const float slope = (p.epi.flags & EPI_LEAKY) ? 0.1f : 1.f;
         const uint32_t tt = (uint32_t)(p.th * p.tw);
         // the lane's position from a thread index the compiler cannot see through: otherwise everything the epilogue derives from it
         // is hoisted out of the unit loop and lives in registers through all K loops, which have none to spare (896 spilled bytes)
@@ -450,8 +450,8 @@ __global__ __launch_bounds__(WINO_BN * 2, 2) void wino_split_kernel(const WinoSp
         f32x4 sc4[4], sf4[4];
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            sc4[g] = *reinterpret_cast<const f32x4*>(p.scale + nb + 8 * g);
-            sf4[g] = *reinterpret_cast<const f32x4*>(p.shift + nb + 8 * g);
+            sc4[g] = *reinterpret_cast<const f32x4*>(p.epi.scale + nb + 8 * g);
+            sf4[g] = *reinterpret_cast<const f32x4*>(p.epi.shift + nb + 8 * g);
         }
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
@@ -464,8 +464,8 @@ __global__ __launch_bounds__(WINO_BN * 2, 2) void wino_split_kernel(const WinoSp
                 const uint32_t oy = 2 * ty + (o >> 1), ox = 2 * tx + (o & 1);
                 if (oy >= (uint32_t)p.H || ox >= (uint32_t)p.W) continue;
                 const uint64_t pix = ((uint64_t)(p.s0 + s) * p.H + oy) * p.W + ox;
-                const uint64_t idx_row = p.idx_base + pix * (uint64_t)p.N + (uint64_t)nb;
-                const epi::DropRow drow(idx_row, p.k1);
+                const uint64_t idx_row = p.epi.idx_base + pix * (uint64_t)p.N + (uint64_t)nb;
+                const epi::DropRow drow(idx_row, p.epi.k1);
                 float* d = p.y + (size_t)pix * p.N + nb;
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
@@ -476,17 +476,17 @@ __global__ __launch_bounds__(WINO_BN * 2, 2) void wino_split_kernel(const WinoSp
                     bool keep[4] = {true, true, true, true};
                     if constexpr (MODE == 2) {                              // injected masks (conv_igemm.hip finish_tile)
                         const uint32_t el = drow.el_lo() + (uint32_t)dn;
-                        const uint32_t w = p.mask_bits[el >> 5] >> (el & 31u);
+                        const uint32_t w = p.epi.mask_bits[el >> 5] >> (el & 31u);
 #pragma unroll
                         for (int q = 0; q < 4; ++q) keep[q] = (w >> q) & 1u;
-                    } else if constexpr (MODE == 1) epi::keep4(drow, dn, p.k0, p.thr, keep);
+                    } else if constexpr (MODE == 1) epi::keep4(drow, dn, p.epi.k0, p.epi.thr, keep);
                     const f32x4 v = epi::bn_act4_pk(a4, sc4[g], sf4[g], keep, slope);
                     vmax = epi::absmax4(vmax, v);
                     *reinterpret_cast<f32x4*>(d + dn) = epi::split_encode4(v);
                 }
             }
         }
-        if (p.status && vmax >= 65520.f) { atomicOr(p.status, 1u); atomicMin(p.status + 1, (unsigned)p.layer_idx); }
+        if (p.epi.status && vmax >= 65520.f) { atomicOr(p.epi.status, 1u); atomicMin(p.epi.status + 1, (unsigned)p.epi.layer_idx); }
     };
 
     // ---- the same with a residual added after the activation and no dropout (the darknet blocks' `inputs + shortcut`, lib_yolo/layers.py:
@@ -497,7 +497,7 @@ __global__ __launch_bounds__(WINO_BN * 2, 2) void wino_split_kernel(const WinoSp
     // 0.07 ms per launch of 173 MB (+22 % at 256 -> 512 channels, +8 % at 512 -> 1024) whatever the distance of the fetch -- all CUs
     // reach their epilogues together and the round's 67 MB of residual reads, which block, join its 67 MB of writes, which do not.
     auto epilogue_res = [&](uint32_t rt, uint32_t ct) __attribute__((always_inline)) {
-        const float slope = (p.flags & EPI_LEAKY) ? 0.1f : 1.f;
+        const float slope = (p.epi.flags & EPI_LEAKY) ? 0.1f : 1.f;
         const uint32_t tt = (uint32_t)(p.th * p.tw);
         int tid_e = (int)threadIdx.x;
         asm volatile("" : "+v"(tid_e));
@@ -507,8 +507,8 @@ __global__ __launch_bounds__(WINO_BN * 2, 2) void wino_split_kernel(const WinoSp
         f32x4 sc4[4], sf4[4];
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            sc4[g] = *reinterpret_cast<const f32x4*>(p.scale + nb + 8 * g);
-            sf4[g] = *reinterpret_cast<const f32x4*>(p.shift + nb + 8 * g);
+            sc4[g] = *reinterpret_cast<const f32x4*>(p.epi.scale + nb + 8 * g);
+            sf4[g] = *reinterpret_cast<const f32x4*>(p.epi.shift + nb + 8 * g);
         }
         const bool keep[4] = {true, true, true, true};
         auto row_of = [&](int k, bool& ok) __attribute__((always_inline)) -> size_t {        // k = 4 i + o
@@ -549,7 +549,7 @@ __global__ __launch_bounds__(WINO_BN * 2, 2) void wino_split_kernel(const WinoSp
 #pragma unroll
             for (int a = 0; a < AHEAD; ++a) { okv[a] = okv[a + 1]; rowv[a] = rowv[a + 1]; }
         }
-        if (p.status && vmax >= 65520.f) { atomicOr(p.status, 1u); atomicMin(p.status + 1, (unsigned)p.layer_idx); }
+        if (p.epi.status && vmax >= 65520.f) { atomicOr(p.epi.status, 1u); atomicMin(p.epi.status + 1, (unsigned)p.epi.layer_idx); }
     };
 
     // The walk.  Static (persist 1): unit k + (workgroups of the XCD) is next.  Dynamic (persist 2): the XCD's workgroups claim units
@@ -611,8 +611,8 @@ __global__ __launch_bounds__(WINO_BN * 2, 2) void wino_split_kernel(const WinoSp
                 }
             }
         if (p.residual) epilogue_res(rt, ct);
-        else if (!(p.flags & EPI_DROPOUT)) epilogue(std::integral_constant<int, 0>{}, rt, ct);
-        else if (p.mask_bits) epilogue(std::integral_constant<int, 2>{}, rt, ct);
+        else if (!(p.epi.flags & EPI_DROPOUT)) epilogue(std::integral_constant<int, 0>{}, rt, ct);
+        else if (p.epi.mask_bits) epilogue(std::integral_constant<int, 2>{}, rt, ct);
         else epilogue(std::integral_constant<int, 1>{}, rt, ct);
     }
 }
@@ -632,7 +632,7 @@ static hipError_t launch_wino_split_bn(const WinoSplitParams& p, hipStream_t st)
     return hipGetLastError();
 }
 hipError_t launch_wino_split(const WinoSplitParams& p, hipStream_t st) {
-    if (p.bm != 64 || (p.residual && (p.flags & EPI_DROPOUT))) return hipErrorInvalidValue;      // (no reference model drops out in front of a residual add: byolo_plan.hip keeps such a layer direct)
+    if (p.bm != 64 || (p.residual && (p.epi.flags & EPI_DROPOUT))) return hipErrorInvalidValue;      // (no reference model drops out in front of a residual add: byolo_plan.hip keeps such a layer direct)
     return p.bn == 256 ? launch_wino_split_bn<256>(p, st) : launch_wino_split_bn<128>(p, st);
 }
 

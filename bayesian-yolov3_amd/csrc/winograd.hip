@@ -96,10 +96,10 @@ __global__ __launch_bounds__(256) void wino_output_kernel(const WinoParams p) {
         u[0][j] = a[0][j] + a[1][j] + a[2][j];
         u[1][j] = a[1][j] - a[2][j] - a[3][j];
     }
-    const f32x4 sc = *reinterpret_cast<const f32x4*>(p.scale + n0);     // includes 1 / (1 - p) when the masks are on
-    const f32x4 sf = *reinterpret_cast<const f32x4*>(p.shift + n0);
-    const bool do_drop = p.flags & EPI_DROPOUT;
-    const float slope = (p.flags & EPI_LEAKY) ? 0.1f : 1.f;
+    const f32x4 sc = *reinterpret_cast<const f32x4*>(p.epi.scale + n0);     // includes 1 / (1 - p) when the masks are on
+    const f32x4 sf = *reinterpret_cast<const f32x4*>(p.epi.shift + n0);
+    const bool do_drop = p.epi.flags & EPI_DROPOUT;
+    const float slope = (p.epi.flags & EPI_LEAKY) ? 0.1f : 1.f;
 #pragma unroll
     for (int dy = 0; dy < 2; ++dy)
 #pragma unroll
@@ -108,9 +108,9 @@ __global__ __launch_bounds__(256) void wino_output_kernel(const WinoParams p) {
             if (oy >= (uint32_t)p.H || ox >= (uint32_t)p.W) continue;
             const f32x4 yv = dx == 0 ? u[dy][0] + u[dy][1] + u[dy][2] : u[dy][1] - u[dy][2] - u[dy][3];   // (A^T m) A
             const uint64_t pix = ((uint64_t)(p.s0 + s) * p.H + oy) * p.W + ox;
-            const uint64_t idx0 = p.idx_base + pix * (uint64_t)p.N + (uint64_t)n0;
+            const uint64_t idx0 = p.epi.idx_base + pix * (uint64_t)p.N + (uint64_t)n0;
             bool keep[4] = {true, true, true, true};
-            if (do_drop) epi::keep4(epi::DropRow(idx0, p.k1), 0, p.k0, p.thr, keep);     // N % 4 == 0: idx0 is a multiple of 4
+            if (do_drop) epi::keep4(epi::DropRow(idx0, p.epi.k1), 0, p.epi.k0, p.epi.thr, keep);     // N % 4 == 0: idx0 is a multiple of 4
             f32x4 o = epi::bn_act4(yv, sc, sf, keep, slope);
             const size_t off = (size_t)pix * p.N + n0;
             if (p.residual) o += *reinterpret_cast<const f32x4*>(p.residual + off);
