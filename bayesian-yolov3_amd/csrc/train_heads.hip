@@ -443,7 +443,8 @@ static int32_t trainer_build(byolo_trainer_t* tr) {
             for (auto& p : v) p.sh += 1;
             view[i] = v; break;
         }
-        default: throw std::runtime_error("head layer '" + l.scope + "': only convolution, route, upsample and detection layers train");
+        default:                                             // (a residual or a stack has no scope: the layer's index names it)
+            throw std::runtime_error("head layer " + std::to_string(i) + ": only convolution, route, upsample and detection layers train");
         }
     }
     if (tr->det_convs.empty()) throw std::runtime_error("the graph has no detection layer after byolo_mark_backbone_end");

@@ -229,9 +229,10 @@ class Graph:
     """Shape and view bookkeeping of one graph (what csrc/byolo_api.hip's builder derives), and -- with `eng` -- the builder calls
     themselves.  A layer is a dict; `view` lists the tensors a reader sees through it: (layer index, upsampled, T-fold tile)."""
 
-    def __init__(self, H, W, B, T=1, eng=None):
-        self.H, self.W, self.B, self.T, self.eng = H, W, B, T, eng
+    def __init__(self, H, W, B, T=1, eng=None, cls_cnt=2):
+        self.H, self.W, self.B, self.T, self.eng, self.cls_cnt = H, W, B, T, eng, cls_cnt
         self.L, self.by_name, self.shapes, self.n_drop = [], {}, {}, 0
+        self.first, self.n_backbone_shapes = None, 0       # mark(): index of the first head layer, variables in front of it
 
     def _push(self, name, idx, **d):
         assert idx is None or idx == len(self.L), (name, idx, len(self.L))
@@ -267,14 +268,22 @@ class Graph:
 
     def det(self, name, kind, check=None):
         x = self._prev()
-        filters = 21 if kind == 0 else 42                  # 3 * (5 + 2) | 3 * 2 * (5 + 2) at two classes
+        filters = (3 if kind == 0 else 6) * (5 + self.cls_cnt)      # 21 | 42 at two classes
         idx = self.eng.add_detection(name, kind, PRIORS) if self.eng else None
+        if self.eng:                                       # the builder's own count (the handle's cls_cnt)
+            filters = self.eng.param_shapes()[name + "/conv2d/kernel"][3]
         self.shapes[name + "/conv2d/kernel"] = (1, 1, x["C"], filters)
         self.shapes[name + "/conv2d/bias"] = (filters,)
         d = self._push(name, idx, op="det", k=1, stride=1, Cin=x["C"], C=filters, H=x["H"], W=x["W"], stacked=x["stacked"],
                        src=x["view"], inH=x["H"], inW=x["W"], drop=None, shortcut=None, check=check, det=True)
         d["view"], d["out"] = [(d["idx"], False, False)], d["idx"]
         return d
+
+    def mark(self):
+        """byolo_mark_backbone_end: the layers from here on are the head a trainer trains (tests/_head_graphs.py)"""
+        if self.eng:
+            self.eng.mark_backbone_end()
+        self.first, self.n_backbone_shapes = len(self.L), len(self.shapes)
 
     def up(self, name):
         x = self._prev()
