@@ -86,6 +86,16 @@ class VoteCfg(ctypes.Structure):
                [("ale_col", ctypes.c_int32), ("epi_col", ctypes.c_int32)]
 
 
+SOFT_NMS_LINEAR, SOFT_NMS_GAUSSIAN = 0, 1                          # BYOLO_SOFT_NMS_*
+SOFT_NMS_RESIDENT = 8192       # BYOLO_SOFT_NMS_RESIDENT: candidates of one (image, class) the soft-NMS holds in registers
+
+
+class SoftNmsCfg(ctypes.Structure):
+    """include/byolo.h byolo_soft_nms_cfg (field for field; tests/test_soft_nms_cpu.py compares the two)."""
+    _fields_ = [("struct_bytes", ctypes.c_int32), ("method", ctypes.c_int32)] + \
+               [(n, ctypes.c_float) for n in ("sigma", "iou_soft", "iou_hard", "min_score")]
+
+
 _i32, _i64, _f32 = ctypes.c_int32, ctypes.c_int64, ctypes.c_float
 _vp, _cp, _sz, _u64 = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint64
 _P = ctypes.POINTER
@@ -193,6 +203,9 @@ PROTOTYPES = {
     "byolo_box_vote": (_i32, [_vp, _vp, _i32, _i64, _i32, _i32, _i32, _i32, _P(VoteCfg), _P(EvalLocCfg), _vp, _vp, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
     "byolo_set_box_vote": (_i32, [_vp, _P(VoteCfg)]),
     "byolo_box_vote_counts": (_i32, [_vp, _vp, _i32, _i32, _vp]),
+    "byolo_soft_nms_workspace_bytes": (_sz, [_i32, _i64, _i32, _i32]),
+    "byolo_soft_nms": (_i32, [_vp, _vp, _i32, _i64, _i32, _i32, _i32, _i32, _i32, _P(SoftNmsCfg), _vp, _sz, _vp, _vp, _vp, _vp]),
+    "byolo_set_soft_nms": (_i32, [_vp, _P(SoftNmsCfg)]),
 }
 
 

@@ -38,6 +38,7 @@ class Engine:
         self._twin = None
         self._trainers = weakref.WeakSet()       # byolo.train.HeadTrainer objects bound to this handle (closed before it)
         self._box_vote = None            # the settings set_box_vote() switched variance voting on with (None: off)
+        self._soft_nms = None            # the settings set_soft_nms() switched the soft-NMS on with (None: off, the hard NMS)
 
     # ---- arithmetic of the convolution stack (include/byolo.h: BYOLO_PREC_*) ----------------------------
     @property
@@ -167,6 +168,8 @@ class Engine:
         t.set_precision(precision)
         if self._box_vote is not None:
             t.set_box_vote(self._box_vote)
+        if self._soft_nms is not None:
+            t.set_soft_nms(self._soft_nms)
         t.set_params(self.get_params())
         t.finalize()
         return t
@@ -511,6 +514,72 @@ class Engine:
                                           ctypes.byref(loc) if loc is not None else None, p(rows_in), p(kept), p(count), cap, p(rows),
                                           p(vote_n), p(ws), wsb, ctypes.c_void_p(stream)))
         return dict(rows=rows, vote_n=vote_n)
+
+    # ---- soft-NMS (include/byolo.h "soft-NMS"; INTEGRATION.md "Soft-NMS") -----------------------------------------
+    SOFT_METHODS = {"linear": _lib.SOFT_NMS_LINEAR, "gaussian": _lib.SOFT_NMS_GAUSSIAN}
+    SOFT_DEFAULTS = dict(method="gaussian", sigma=0.5, iou_soft=0.3, iou_hard=1.0, min_score=0.001)
+
+    @classmethod
+    def _soft_cfg(cls, settings):
+        """byolo_soft_nms_cfg of a settings dict (method, sigma, iou_soft, iou_hard, min_score).  The defaults are those of Bodla
+        et al.; nobody has tuned them on this detector.  ValueError names the field a value is refused for."""
+        s = dict(cls.SOFT_DEFAULTS, **dict(settings))
+        unknown = sorted(set(s) - set(cls.SOFT_DEFAULTS))
+        if unknown:
+            raise TypeError("soft_nms: unknown settings %s" % unknown)
+        if s["method"] not in cls.SOFT_METHODS:
+            raise ValueError("soft_nms: method is one of %s, not %r" % (sorted(cls.SOFT_METHODS), s["method"]))
+        v = {}
+        for k in ("sigma", "iou_soft", "iou_hard", "min_score"):
+            if isinstance(s[k], (bool, str)) or s[k] is None:
+                raise ValueError("soft_nms: %s must be a number, not %r" % (k, s[k]))
+            v[k] = float(np.float32(s[k]))
+        if not (v["sigma"] > 0.0 and np.isfinite(v["sigma"])):
+            raise ValueError("soft_nms: sigma %r must be > 0 and finite" % (s["sigma"],))
+        for k in ("iou_soft", "iou_hard"):
+            if not 0.0 <= v[k] <= 1.0:
+                raise ValueError("soft_nms: %s %r outside [0, 1]" % (k, s[k]))
+        if not (v["min_score"] >= 0.0 and np.isfinite(v["min_score"])):
+            raise ValueError("soft_nms: min_score %r must be >= 0 and finite" % (s["min_score"],))
+        return _lib.SoftNmsCfg(struct_bytes=ctypes.sizeof(_lib.SoftNmsCfg), method=cls.SOFT_METHODS[s["method"]], **v)
+
+    def set_soft_nms(self, settings=True):
+        """The soft-NMS inside forward() in place of the hard NMS: True or a dict of settings switches it on -- the obj_idx column
+        of 'rows' is then the decayed score a row was picked with --, False / None switches it off (the default; forward() is then
+        what it was).  Variance voting (set_box_vote) votes behind it."""
+        if settings is None or settings is False:
+            check(self._h, lib.byolo_set_soft_nms(self._h, None))
+            self._soft_nms = None
+            return
+        settings = {} if settings is True else dict(settings)
+        cfg = self._soft_cfg(settings)
+        check(self._h, lib.byolo_set_soft_nms(self._h, ctypes.byref(cfg)))
+        self._soft_nms = settings
+        self.drop_twin()                                  # a twin carries the setting it was made with
+
+    def soft_nms(self, boxes, obj_idx, cls_start_idx, nms_mode=None, max_out=None, **settings):
+        """The soft-NMS by itself (byolo_soft_nms) on boxes [B, N, D]: the dict sort_nms returns -- rows in pick order with the
+        obj_idx column replaced by the score at the pick, kept, count and (NMS_PER_CLASS) class_counts."""
+        torch = _torch()
+        assert boxes.is_cuda and boxes.dtype == torch.float32 and boxes.is_contiguous() and boxes.dim() == 3
+        B, N, D = boxes.shape
+        nms_mode = self.cfg.nms_mode if nms_mode is None else nms_mode
+        max_out = self.cfg.max_out if max_out is None else max_out
+        cfg = self._soft_cfg(settings)
+        cap = self.nms_cap(nms_mode, max_out, self.cfg.cls_cnt)
+        wsb = int(lib.byolo_soft_nms_workspace_bytes(B, N, int(nms_mode), self.cfg.cls_cnt))
+        ws = torch.empty(max(wsb, 8), dtype=torch.uint8, device=boxes.device)
+        rows = torch.empty((B, cap, D), dtype=torch.float32, device=boxes.device)
+        kept = torch.empty((B, cap), dtype=torch.int32, device=boxes.device)
+        count = torch.empty((B, 2), dtype=torch.int32, device=boxes.device)
+        stream = torch.cuda.current_stream(boxes.device).cuda_stream
+        p = lambda t: ctypes.c_void_p(t.data_ptr())
+        check(self._h, lib.byolo_soft_nms(self._h, p(boxes), B, N, D, int(obj_idx), int(cls_start_idx), int(nms_mode), int(max_out),
+                                          ctypes.byref(cfg), p(ws), wsb, p(rows), p(kept), p(count), ctypes.c_void_p(stream)))
+        res = dict(rows=rows, kept=kept, count=count)
+        if int(nms_mode) == _lib.NMS_PER_CLASS:
+            res["class_counts"] = self._class_counts(B, boxes.device, stream)
+        return res
 
     def layer_output(self, idx):
         """Copy of layer `idx`'s output after a forward (needs keep_all_outputs=True)."""

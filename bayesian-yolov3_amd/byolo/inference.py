@@ -437,7 +437,11 @@ class InferenceLoop:
             if flags[0] or flags[1]:
                 return None, flags
             rows = eng.finish_tshard(buf[:N * D].view(1, N, D), T)
-            res = eng.sort_nms(rows, self.model.obj_idx, self.model.cls_start_idx)
+            soft = getattr(eng, '_soft_nms', None)
+            if soft is not None:                           # engine_options['soft_nms']: in place of the hard NMS, as in byolo_forward
+                res = eng.soft_nms(rows, self.model.obj_idx, self.model.cls_start_idx, **soft)
+            else:
+                res = eng.sort_nms(rows, self.model.obj_idx, self.model.cls_start_idx)
             vote = getattr(eng, '_box_vote', None)
             if vote is not None:                           # engine_options['box_vote']: what byolo_forward does behind its own NMS
                 res.update(eng.box_vote(rows, res, self.model.obj_idx, self.model.cls_start_idx, geom=self.model.det_layers, **vote))

@@ -14,6 +14,7 @@
 //                                                          writing rows at their concat_bbox offset
 //   concat_bbox -> non_max_suppression -> gather          the pc_* launches of launch_sort_nms
 #include "byolo_internal.h"
+#include <cfloat>
 
 static thread_local std::string g_err;
 
@@ -924,6 +925,7 @@ extern "C" const char* byolo_precision_note(const byolo_t* h) { return h ? h->pr
 static int32_t forward_piece(byolo_t* h, const float* d_img, int32_t B, int32_t T, uint64_t seed, int32_t dropout_on,
                              const uint32_t* d_mask_bits, void* d_workspace, size_t workspace_bytes, float* d_boxes, float* d_rows,
                              int32_t* d_kept, int32_t* d_count, void* stream);
+static SoftNmsParams soft_params(const byolo_soft_nms_cfg& c);
 struct FwdArgs { const float* d_img; int32_t B, T; uint64_t seed; int32_t dropout_on; const uint32_t* d_mask_bits; void* d_workspace;
                  float* d_boxes; float* d_rows; int32_t* d_kept; int32_t* d_count; };
 static int32_t enqueue_forward(byolo_t* h, const FwdArgs& a, hipStream_t st, bool capturing, bool wait_convs, bool heads_only = false);
@@ -1014,7 +1016,8 @@ static int32_t forward_piece(byolo_t* h, const float* d_img, int32_t B, int32_t 
     if (d_rows && h->cfg.nms_mode == BYOLO_NMS_PER_CLASS) {
         // refused before anything is enqueued (a replayed graph never comes back through enqueue_forward)
         if (h->cls_start + h->cfg.cls_cnt > h->row_len) return fail(h, BYOLO_ERR_ARG, "byolo_forward: per-class NMS: class columns outside the row");
-        h->pc_counts = nms_class_counts_ptr(static_cast<char*>(d_workspace) + h->plan.nms_off, B, h->n_boxes, h->cfg.cls_cnt);
+        h->pc_counts = h->soft_on ? soft_nms_class_counts_ptr(static_cast<char*>(d_workspace) + h->plan.soft_off, B, h->n_boxes, h->cfg.cls_cnt)
+                                  : nms_class_counts_ptr(static_cast<char*>(d_workspace) + h->plan.nms_off, B, h->n_boxes, h->cfg.cls_cnt);
         h->pc_B = B; h->pc_C = h->cfg.cls_cnt;
     }
     if (d_rows && h->vote_on) {                             // refused here as well: a variance kind the handle's rows do not have
@@ -1314,7 +1317,11 @@ static int32_t enqueue_forward(byolo_t* h, const FwdArgs& a, hipStream_t st, boo
         n.ws = ws + h->plan.nms_off; n.ws_bytes = nms_workspace_bytes_ex(B, h->n_boxes, h->cfg.nms_mode, h->cfg.cls_cnt);
         n.rows = d_rows; n.kept = d_kept; n.count = d_count; n.general_only = h->opts.nms_general != 0;
         if (h->cfg.nms_mode == BYOLO_NMS_TWO_CLASS && h->cfg.cls_cnt != 2) return fail(h, BYOLO_ERR_ARG, "byolo_forward: 2-class NMS needs cls_cnt == 2");
-        HIPCHK(h, launch_sort_nms(n, st));
+        if (h->soft_on) {                                   // the soft-NMS in place of the hard one (tail_kernels.hip soft_*)
+            SoftNmsParams sp = soft_params(h->soft_cfg);
+            sp.n = n; sp.n.ws = ws + h->plan.soft_off; sp.n.ws_bytes = soft_nms_workspace_bytes(B, h->n_boxes, n.C);
+            HIPCHK(h, launch_soft_nms(sp, st));
+        } else HIPCHK(h, launch_sort_nms(n, st));
         if (h->vote_on) {                                   // variance voting, in place on the kept rows (box_vote.hip)
             VoteParams v;
             rc = byolo_vote_from_handle(h, &v, "byolo_forward"); if (rc) return rc;
@@ -1450,6 +1457,66 @@ extern "C" int32_t byolo_nms_class_counts(byolo_t* h, int32_t* d_class_counts, i
     if (B != h->pc_B || cls_cnt != h->pc_C) return fail(h, BYOLO_ERR_ARG, "byolo_nms_class_counts: the last per-class NMS ran [%d, %d], asked for [%d, %d]", h->pc_B, h->pc_C, B, cls_cnt);
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipMemcpyAsync(d_class_counts, h->pc_counts, (size_t)B * cls_cnt * sizeof(int32_t), hipMemcpyDeviceToDevice, reinterpret_cast<hipStream_t>(stream)));
+    return BYOLO_OK;
+}
+
+// ---- soft-NMS (include/byolo.h "soft-NMS") ---------------------------------------------------------------------------------
+static_assert(BYOLO_SOFT_NMS_LINEAR == SOFT_NMS_LINEAR && BYOLO_SOFT_NMS_GAUSSIAN == SOFT_NMS_GAUSSIAN, "byolo_kernels.h restates the methods");
+static_assert(BYOLO_SOFT_NMS_RESIDENT == SOFT_NMS_RESIDENT_CAP, "include/byolo.h names the resident capacity");
+static int32_t soft_check_settings(byolo_t* h, const byolo_soft_nms_cfg* c, const char* what) {
+    if (c->struct_bytes != (int32_t)sizeof *c) return fail(h, BYOLO_ERR_ARG, "%s: struct_bytes %d, this library's byolo_soft_nms_cfg has %d (include/byolo.h)", what, c->struct_bytes, (int)sizeof *c);
+    if (c->method != BYOLO_SOFT_NMS_LINEAR && c->method != BYOLO_SOFT_NMS_GAUSSIAN) return fail(h, BYOLO_ERR_ARG, "%s: unknown method %d (BYOLO_SOFT_NMS_*)", what, c->method);
+    if (!(c->sigma > 0.f) || !(c->sigma <= FLT_MAX)) return fail(h, BYOLO_ERR_ARG, "%s: sigma %g must be > 0 and finite", what, (double)c->sigma);
+    if (!(c->iou_soft >= 0.f && c->iou_soft <= 1.f)) return fail(h, BYOLO_ERR_ARG, "%s: iou_soft %g outside [0, 1]", what, (double)c->iou_soft);
+    if (!(c->iou_hard >= 0.f && c->iou_hard <= 1.f)) return fail(h, BYOLO_ERR_ARG, "%s: iou_hard %g outside [0, 1]", what, (double)c->iou_hard);
+    if (!(c->min_score >= 0.f) || !(c->min_score <= FLT_MAX)) return fail(h, BYOLO_ERR_ARG, "%s: min_score %g must be >= 0 and finite", what, (double)c->min_score);
+    return BYOLO_OK;
+}
+static SoftNmsParams soft_params(const byolo_soft_nms_cfg& c) {
+    SoftNmsParams p; memset(&p, 0, sizeof p);
+    p.method = c.method; p.sigma = c.sigma; p.iou_soft = c.iou_soft; p.iou_hard = c.iou_hard; p.min_score = c.min_score;
+    return p;
+}
+
+extern "C" size_t byolo_soft_nms_workspace_bytes(int32_t B, int64_t N, int32_t nms_mode, int32_t cls_cnt) {
+    if (B < 1 || N < 1 || nms_mode < BYOLO_NMS_AGNOSTIC || nms_mode > BYOLO_NMS_PER_CLASS) return 0;
+    if (nms_mode == BYOLO_NMS_PER_CLASS && (cls_cnt < 1 || cls_cnt > BYOLO_NMS_MAX_CLASSES)) return 0;
+    return soft_nms_workspace_bytes(B, N, nms_classes(nms_mode, cls_cnt));
+}
+
+extern "C" int32_t byolo_soft_nms(byolo_t* h, const float* d_boxes, int32_t B, int64_t N, int32_t D, int32_t obj_idx,
+                                  int32_t cls_start_idx, int32_t nms_mode, int32_t max_out, const byolo_soft_nms_cfg* cfg,
+                                  void* d_ws, size_t ws_bytes, float* d_rows, int32_t* d_kept, int32_t* d_count, void* stream) {
+    const char* what = "byolo_soft_nms";
+    if (!h || !d_boxes || !cfg || !d_ws || !d_rows || !d_kept || !d_count) return fail(h, BYOLO_ERR_ARG, "%s: null argument", what);
+    if (B < 1 || B > 65535 || N < 1 || N >= (1ll << 31) || D < 5 || obj_idx < 4 || obj_idx >= D) return fail(h, BYOLO_ERR_ARG, "%s: bad shape", what);
+    if (max_out < 1 || max_out > 2048) return fail(h, BYOLO_ERR_ARG, "%s: max_out out of [1,2048]", what);
+    if (nms_mode < BYOLO_NMS_AGNOSTIC || nms_mode > BYOLO_NMS_PER_CLASS) return fail(h, BYOLO_ERR_ARG, "%s: unknown nms_mode %d", what, nms_mode);
+    const bool per_class = nms_mode == BYOLO_NMS_PER_CLASS;
+    const int32_t C = nms_classes(nms_mode, h->cfg.cls_cnt);
+    if (C < 1 || C > BYOLO_NMS_MAX_CLASSES) return fail(h, BYOLO_ERR_ARG, "%s: per-class NMS takes 1 .. %d classes", what, BYOLO_NMS_MAX_CLASSES);
+    if (C > 1 && (cls_start_idx < 0 || (int64_t)cls_start_idx + C > D)) return fail(h, BYOLO_ERR_ARG, "%s: bad cls_start_idx (class columns outside the row)", what);
+    int32_t rc = soft_check_settings(h, cfg, what); if (rc) return rc;
+    if (ws_bytes < soft_nms_workspace_bytes(B, N, C)) return fail(h, BYOLO_ERR_NOMEM, "%s: workspace %zu < byolo_soft_nms_workspace_bytes = %zu", what, ws_bytes, soft_nms_workspace_bytes(B, N, C));
+    HIPCHK(h, hipSetDevice(h->device));
+    SoftNmsParams p = soft_params(*cfg);
+    p.n.boxes = d_boxes; p.n.B = B; p.n.N = N; p.n.D = D; p.n.obj_idx = obj_idx; p.n.cls_start = cls_start_idx; p.n.C = C; p.n.max_out = max_out;
+    p.n.ws = d_ws; p.n.ws_bytes = ws_bytes; p.n.rows = d_rows; p.n.kept = d_kept; p.n.count = d_count; p.n.general_only = h->opts.nms_general != 0;
+    HIPCHK(h, launch_soft_nms(p, reinterpret_cast<hipStream_t>(stream)));
+    if (per_class) { h->pc_counts = soft_nms_class_counts_ptr(d_ws, B, N, C); h->pc_B = B; h->pc_C = C; }
+    return BYOLO_OK;
+}
+
+extern "C" int32_t byolo_set_soft_nms(byolo_t* h, const byolo_soft_nms_cfg* cfg) {
+    if (!h) return fail(nullptr, BYOLO_ERR_ARG, "byolo_set_soft_nms: null handle");
+    if (cfg) {
+        int32_t rc = soft_check_settings(h, cfg, "byolo_set_soft_nms"); if (rc) return rc;
+        h->soft_cfg = *cfg;
+    }
+    h->soft_on = cfg != nullptr;
+    h->pc_counts = nullptr;
+    // the stage's workspace is part of the plan, and a captured forward holds the launches of the old setting
+    h->plan.B = -1; h->plan.T = -1; ++h->plan_epoch; h->wsm_B = -1;
     return BYOLO_OK;
 }
 

@@ -120,6 +120,7 @@ struct Plan {
     int B = -1, T = -1;
     std::vector<int64_t> off;      // per layer tensor offset in bytes (-1: none)
     size_t arena = 0, boxes_off = 0, nms_off = 0, stats_off = 0, total = 0;
+    size_t soft_off = 0;                   // soft-NMS (byolo_set_soft_nms): the stage's workspace; no bytes while it is off
     size_t vote_n_off = 0, vote_off = 0;   // box voting (byolo_set_box_vote): vote_n [B, cap] and the stage's workspace; no bytes while it is off
     size_t img_split_off = 0;      // split precision: the image as hi/lo pairs, for a matrix-pipe convolution that reads it (img_c % 32 == 0)
     size_t slab_off = 0, slab_bytes = 0, cnt_off = 0, cnt_bytes = 0;   // split-K slabs (shared by all steps), per-step ticket counters
@@ -219,6 +220,8 @@ struct byolo {
     // byolo_set_box_vote: byolo_forward votes in place behind the NMS (box_vote.hip).  vn_ptr: where the last such forward left
     // vote_n [vn_B, vn_cap] -- inside that call's workspace, or in vn_own (a forward that ran in pieces)
     bool vote_on = false; byolo_vote_cfg vote_cfg = {};
+    // byolo_set_soft_nms: byolo_forward runs the soft-NMS (tail_kernels.hip soft_*) in place of the hard one
+    bool soft_on = false; byolo_soft_nms_cfg soft_cfg = {};
     const int32_t* vn_ptr = nullptr; int32_t vn_B = 0, vn_cap = 0;
     int32_t* vn_own = nullptr; size_t vn_own_cap = 0;
     int64_t first_image = 0;       // position of a call's first image in the logical batch (dropout stream)

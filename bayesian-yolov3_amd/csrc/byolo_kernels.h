@@ -283,6 +283,18 @@ struct NmsParams {
 const int32_t* nms_class_counts_ptr(void* ws, int B, int64_t N, int C);   // the kept-per-class counts [B, C] of a run with C classes, inside ws
 hipError_t launch_sort_nms(const NmsParams& p, hipStream_t st);
 
+// ---- soft-NMS (tail_kernels.hip soft_*; include/byolo.h "soft-NMS"): the decaying greedy pass in place of launch_sort_nms ----
+constexpr int SOFT_NMS_RESIDENT_CAP = 8192;   // candidates of one (image, class) the resident path holds in registers (BYOLO_SOFT_NMS_RESIDENT)
+constexpr int SOFT_NMS_LINEAR = 0, SOFT_NMS_GAUSSIAN = 1;      // BYOLO_SOFT_NMS_* (byolo_api.hip asserts the two agree)
+struct SoftNmsParams {
+    NmsParams n;             // as launch_sort_nms takes it; iou_thr is not read
+    int method;              // BYOLO_SOFT_NMS_*
+    float sigma, iou_soft, iou_hard, min_score;
+};
+size_t soft_nms_workspace_bytes(int B, int64_t N, int C);
+const int32_t* soft_nms_class_counts_ptr(void* ws, int B, int64_t N, int C);
+hipError_t launch_soft_nms(const SoftNmsParams& p, hipStream_t st);
+
 // ---- variance voting behind the NMS (box_vote.hip; include/byolo.h "variance voting") ------------------------------------
 struct VoteGeom { int layer_col, prior_col, n_layers; int lh[8], lw[8], n_priors[8]; };      // byolo_eval_loc_cfg without the priors
 struct VoteParams {

@@ -226,6 +226,8 @@ void make_plan(byolo_t* h, int B, int T, bool inject) {
     p.boxes_off = p.arena;
     size_t o = p.boxes_off + align_up((size_t)B * h->n_boxes * h->row_len * sizeof(float), 256);
     p.nms_off = o; o += align_up(nms_workspace_bytes_ex(B, h->n_boxes, h->cfg.nms_mode, h->cfg.cls_cnt), 256);
+    p.soft_off = o;
+    if (h->soft_on) o += align_up(soft_nms_workspace_bytes(B, h->n_boxes, nms_classes(h->cfg.nms_mode, h->cfg.cls_cnt)), 256);
     p.vote_n_off = p.vote_off = o;
     if (h->vote_on) {
         o += align_up((size_t)B * nms_out_cap(h) * sizeof(int32_t), 256);

@@ -37,6 +37,19 @@ __device__ __forceinline__ float iou_value(const NBox& i, const NBox& j) {
     if (i.area <= 0.f || j.area <= 0.f) return 0.f;
     return iou_of(i, j);
 }
+// iou_value with one rounding per operation whatever the file's contraction mode: for callers that hand the VALUE on -- the
+// soft-NMS multiplies scores by a weight of it -- and are compared bit for bit with numpy.  Plain operators under the pragma: the
+// __f*_rn intrinsics above are inlined header functions whose operators keep the contraction mode of the file, and the product
+// `inter` then fuses into the subtraction behind it.  (A float32 quotient is correctly rounded in every mode of this build.)
+__device__ __forceinline__ float iou_value_rn(const NBox& i, const NBox& j) {
+#pragma clang fp contract(off)
+    if (i.area <= 0.f || j.area <= 0.f) return 0.f;
+    const float iy0 = smax_(i.y0, j.y0), ix0 = smax_(i.x0, j.x0);
+    const float iy1 = smin_(i.y1, j.y1), ix1 = smin_(i.x1, j.x1);
+    const float inter = smax_(iy1 - iy0, 0.f) * smax_(ix1 - ix0, 0.f);
+    const float uni = (i.area + j.area) - inter;
+    return inter / uni;
+}
 
 // ---- score and class of a row, as the NMS pipeline (tail_kernels.hip pc_*) and the vote stage (box_vote.hip) decide them ----
 __device__ __forceinline__ unsigned int score_key(float f) {

@@ -883,10 +883,13 @@ __global__ __launch_bounds__(NMS_THREADS) void pc_general_kernel(const float* bo
     if (tid == 0) w.cnt[(size_t)b * C + c] = nk;
 }
 
-__global__ __launch_bounds__(256) void pc_finish_kernel(const float* boxes, int64_t N, int D, int C, int max_out, PcWs w,
-                                                        float* rows, int32_t* kept, int32_t* count) {
+// SCORE: the soft-NMS's gather -- column obj_idx of a kept row is its output score kscore[b][c][k] instead of the source row's
+template <bool SCORE>
+__device__ __forceinline__ void pc_finish_body(const float* boxes, int64_t N, int D, int C, int max_out, const PcWs& w,
+                                               float* rows, int32_t* kept, int32_t* count, int obj_idx, const float* kscore) {
     __shared__ int pre[BYOLO_MAX_CLASSES + 1];               // kept before class c
     __shared__ int src[PC_ROWS];                             // source row of each output row of this workgroup, -1 = none
+    __shared__ float ksc[SCORE ? PC_ROWS : 1];
     const int b = blockIdx.y, tid = threadIdx.x;
     const int* cnt = w.cnt + (size_t)b * C;
     for (int c = tid; c < C; c += 256) pre[c + 1] = cnt[c];
@@ -902,6 +905,7 @@ __global__ __launch_bounds__(256) void pc_finish_kernel(const float* boxes, int6
             int lo = 0, hi = C - 1;                          // the last class with pre[c] <= k
             while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (pre[mid] <= k) lo = mid; else hi = mid - 1; }
             idx = w.kidx[((size_t)b * C + lo) * NMS_MAXK + (k - pre[lo])];
+            if (SCORE) ksc[tid] = kscore[((size_t)b * C + lo) * NMS_MAXK + (k - pre[lo])];
         }
         src[tid] = idx;
         kept[(size_t)b * cap + k] = idx;
@@ -911,9 +915,13 @@ __global__ __launch_bounds__(256) void pc_finish_kernel(const float* boxes, int6
     float* ro = rows + ((size_t)b * cap + k0) * D;
     for (int e = tid; e < nrow * D; e += 256) {
         const int k = e / D, col = e - k * D;
-        ro[e] = src[k] >= 0 ? bx[(size_t)src[k] * D + col] : 0.f;
+        ro[e] = src[k] >= 0 ? ((SCORE && col == obj_idx) ? ksc[k] : bx[(size_t)src[k] * D + col]) : 0.f;
     }
     if (blockIdx.x == 0 && tid == 0) { count[2 * b] = total; count[2 * b + 1] = cnt[0]; }
+}
+__global__ __launch_bounds__(256) void pc_finish_kernel(const float* boxes, int64_t N, int D, int C, int max_out, PcWs w,
+                                                        float* rows, int32_t* kept, int32_t* count) {
+    pc_finish_body<false>(boxes, N, D, C, max_out, w, rows, kept, count, -1, nullptr);
 }
 
 hipError_t launch_sort_nms(const NmsParams& p, hipStream_t st) {
@@ -949,6 +957,296 @@ hipError_t launch_sort_nms(const NmsParams& p, hipStream_t st) {
     hipLaunchKernelGGL(pc_general_kernel, by_class, dim3(NMS_THREADS), 0, st, p.boxes, p.N, p.D, C, p.max_out, p.iou_thr, w);
     hipLaunchKernelGGL(pc_finish_kernel, dim3((unsigned)(((int64_t)C * p.max_out + PC_ROWS - 1) / PC_ROWS), p.B), dim3(256), 0, st,
                        p.boxes, p.N, p.D, C, p.max_out, w, p.rows, p.kept, p.count);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// Soft-NMS (Bodla et al., ICCV 2017, Algorithm 1; include/byolo.h "soft-NMS"): per (image, class) the candidate with the largest
+// CURRENT score is picked, and every remaining candidate's score is multiplied by a weight of its IoU with the pick -- linear
+// (1 - v above iou_soft) or Gaussian (exp(-v^2 / sigma), formed in float64, rounded once) -- until max_out rows are picked or no
+// candidate's score is above min_score; a candidate also leaves when its IoU with a pick exceeds iou_hard.  The class segments are
+// the hard pipeline's (pc_classify / pc_offsets / pc_scatter); then
+//   soft_pick     grid (class, image), one 512-thread workgroup: the members with score > min_score are compacted, then the
+//                 pick loop.  A pick is one arg-max over the workgroup -- every thread keeps the best (score bits, ~row index) key
+//                 of its own candidates up to date while it applies the decay, a wave reduction and 8 LDS words do the rest --
+//                 and one broadcast of the picked box through LDS: two barriers.  The key orders equal scores by the lower row
+//                 index, so the result does not depend on where the (atomically ordered) compaction put a candidate.
+//                   resident path: up to SOFT_NMS_RESIDENT_CAP candidates, 16 per thread in registers (box, area, score, index),
+//                                  walked with fully unrolled loops; slots beyond the candidate count are skipped uniformly
+//                   general path:  any count (and every class under byolo_plan_opts.nms_general): the current scores live in the
+//                                  workspace, boxes are re-read from the rows for every pick -- exact, slow
+//                 Both take soft_iou / soft_gauss / soft_apply on the same values in the same order per candidate: the same bytes.
+//   soft_finish   pc_finish's gather with the obj_idx column replaced by the output score
+// The float64 part is skipped where the IoU is 0 (the weight is exactly 1 there).
+// ------------------------------------------------------------------------------------------------
+static constexpr int SOFT_THREADS = 512;                      // 8 waves, two per SIMD: 256 registers a lane for the 16 resident slots
+static constexpr int SOFT_SLOTS = SOFT_NMS_RESIDENT_CAP / SOFT_THREADS;
+static_assert(SOFT_SLOTS * SOFT_THREADS == SOFT_NMS_RESIDENT_CAP, "the resident capacity is whole slots of the workgroup");
+
+struct SoftCfg { int method; float sigma, iou_soft, iou_hard, min_score; };
+struct SoftWs {
+    PcWs pc;                                                 // mask and cand stay null: the prefix path does not run
+    int* cidx;                                               // [B][N] row indices of the candidates (score > min_score), by class segment
+    float* cur;                                              // [B][N] current scores of the general path, beside cidx
+    float* kscore;                                           // [B][C][NMS_MAXK] output scores, beside pc.kidx
+};
+static size_t soft_ws_layout(int B, int64_t N, int C, char* base, SoftWs* w) {
+    size_t o = 0;
+    auto take = [&](size_t bytes) { char* p = base ? base + o : nullptr; o += (bytes + 255) / 256 * 256; return p; };
+    const size_t ci = (size_t)B * (C + 1) * 4;
+    char* hc = take(2 * ci);                                 // hist + cursor: cleared by one launch_zero_words
+    char* so = take(ci); char* ro = take(ci); char* to = take(ci); char* nc = take(ci); char* mo = take(ci); char* ne = take(ci);
+    char* cn = take((size_t)B * C * 4);
+    char* cl = take((size_t)B * N);
+    char* sg = take((size_t)B * N * 8);
+    char* ki = take((size_t)B * C * NMS_MAXK * 4); char* ks = take((size_t)B * C * NMS_MAXK * 4);
+    char* cx = take((size_t)B * N * 4); char* cu = take((size_t)B * N * 4);
+    if (w) { *w = SoftWs{};
+             w->pc.hist = (int*)hc; w->pc.cursor = (int*)(hc ? hc + ci : nullptr); w->pc.seg_off = (int*)so; w->pc.row_off = (int*)ro;
+             w->pc.tile_off = (int*)to; w->pc.n_cand = (int*)nc; w->pc.more = (int*)mo; w->pc.need = (int*)ne; w->pc.cnt = (int*)cn;
+             w->pc.cls = (unsigned char*)cl; w->pc.seg = (unsigned long long*)sg; w->pc.kidx = (int*)ki;
+             w->kscore = (float*)ks; w->cidx = (int*)cx; w->cur = (float*)cu; }
+    return o;
+}
+size_t soft_nms_workspace_bytes(int B, int64_t N, int C) { return soft_ws_layout(B, N, C, nullptr, nullptr); }
+const int32_t* soft_nms_class_counts_ptr(void* ws, int B, int64_t N, int C) {
+    SoftWs w;
+    soft_ws_layout(B, N, C, reinterpret_cast<char*>(ws), &w);
+    return w.pc.cnt;
+}
+
+// What one pick `pk` does to a live candidate `me` of current score s, in three steps that both paths take in this order.  One
+// rounding per float32 operation; the Gaussian weight one operation per line in float64, rounded once (plain operators with
+// contraction off: see iou_value_rn).
+__device__ __forceinline__ float soft_iou(const NBox& pk, const NBox& me) {
+    const float v = iou_value_rn(pk, me);
+    return (v >= 0.f) ? v : 0.f;                             // a NaN counts as 0
+}
+__device__ __forceinline__ float soft_linear(float v) {
+#pragma clang fp contract(off)
+    return 1.f - v;
+}
+__device__ __forceinline__ float soft_gauss(float v, float sigma) {
+#pragma clang fp contract(off)
+    const double vv = (double)v * (double)v;
+    const double q = vv / (double)sigma;
+    return (float)exp(-q);
+}
+// the new score, 0 = the candidate leaves.  (A live score is > min_score >= 0, so 0 marks the dead.)
+__device__ __forceinline__ float soft_apply(float s, float v, float wgt, const SoftCfg& c) {
+#pragma clang fp contract(off)
+    s = s * wgt;
+    return (v > c.iou_hard || !(s > c.min_score)) ? 0.f : s;
+}
+// arg-max key of a live candidate: larger score first, then the LOWER row index
+__device__ __forceinline__ unsigned long long soft_key(float s, int idx) {
+    return ((unsigned long long)__float_as_uint(s) << 32) | (0xFFFFFFFFu - (unsigned int)idx);
+}
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long k) {
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned int lo = __shfl_xor((unsigned int)k, o), hi = __shfl_xor((unsigned int)(k >> 32), o);
+        const unsigned long long q = ((unsigned long long)hi << 32) | lo;
+        k = q > k ? q : k;
+    }
+    return k;
+}
+struct SoftLds { unsigned long long wmax[SOFT_THREADS / 64]; float pk[5]; };
+// The workgroup's best key from every thread's: 0 = no live candidate (uniform).  One barrier; the caller's second barrier (behind
+// the owner's broadcast) also separates this call's reads of wmax from the next call's writes.
+__device__ __forceinline__ unsigned long long soft_argmax(SoftLds& L, unsigned long long best) {
+    const unsigned long long wb = wave_max_u64(best);
+    if ((threadIdx.x & 63) == 0) L.wmax[threadIdx.x >> 6] = wb;
+    __syncthreads();
+    unsigned long long g = 0ull;
+#pragma unroll
+    for (int k = 0; k < SOFT_THREADS / 64; ++k) { const unsigned long long q = L.wmax[k]; g = q > g ? q : g; }
+    return g;
+}
+
+template <class Emit>
+__device__ __forceinline__ int soft_walk_resident(SoftLds& L, const float* bx, int D, int obj_idx, const int* cidx, int nc,
+                                                  int max_out, const SoftCfg& c, Emit emit) {
+    const int tid = threadIdx.x;
+    float y0[SOFT_SLOTS], x0[SOFT_SLOTS], y1[SOFT_SLOTS], x1[SOFT_SLOTS], ar[SOFT_SLOTS], sc[SOFT_SLOTS];
+    int ix[SOFT_SLOTS];
+    const int nslot = (nc + SOFT_THREADS - 1) / SOFT_THREADS;  // slots >= nslot are empty in every thread
+    unsigned long long best = 0ull;
+    int bs = 0;
+#pragma unroll
+    for (int s = 0; s < SOFT_SLOTS; ++s) {
+        const int i = s * SOFT_THREADS + tid;
+        y0[s] = x0[s] = y1[s] = x1[s] = ar[s] = sc[s] = 0.f; ix[s] = 0;
+        if (i < nc) {
+            const int idx = cidx[i];
+            const float* r = bx + (size_t)idx * D;
+            const NBox me = make_box(r[0], r[1], r[2], r[3]);
+            y0[s] = me.y0; x0[s] = me.x0; y1[s] = me.y1; x1[s] = me.x1; ar[s] = me.area; sc[s] = r[obj_idx]; ix[s] = idx;
+            const unsigned long long k = soft_key(sc[s], idx);
+            if (k > best) { best = k; bs = s; }
+        }
+    }
+    int nk = 0;
+    while (nk < max_out) {
+        const unsigned long long g = soft_argmax(L, best);
+        if (g == 0ull) break;
+        if (best == g) {                                     // the owner: row indices are unique, so exactly one thread
+#pragma unroll
+            for (int s = 0; s < SOFT_SLOTS; ++s)
+                if (s == bs) { L.pk[0] = y0[s]; L.pk[1] = x0[s]; L.pk[2] = y1[s]; L.pk[3] = x1[s]; L.pk[4] = ar[s]; sc[s] = 0.f; }
+            emit(nk, (int)(0xFFFFFFFFu - (unsigned int)g), __uint_as_float((unsigned int)(g >> 32)));
+        }
+        ++nk;
+        __syncthreads();
+        if (nk >= max_out) break;                            // the last pick decays nobody who could still be picked
+        const NBox pk = {L.pk[0], L.pk[1], L.pk[2], L.pk[3], L.pk[4]};
+        // the IoU of every live slot; the float64 weights are then formed at ONE place, for the slots that overlap the pick at all
+        // (v == 0: the weight is exactly 1) -- sixteen inlined copies of exp() would not fit the register file
+        float wv[SOFT_SLOTS];                                // the slot's weight (Gaussian, until its turn below: its IoU)
+        unsigned int need = 0u, hard = 0u;
+#pragma unroll
+        for (int s = 0; s < SOFT_SLOTS; ++s) {
+            wv[s] = 1.f;
+            if (s < nslot && sc[s] != 0.f) {
+                const NBox me = {y0[s], x0[s], y1[s], x1[s], ar[s]};
+                const float v = soft_iou(pk, me);
+                if (v > c.iou_hard) hard |= 1u << s;
+                if (c.method == SOFT_NMS_LINEAR) { if (v > c.iou_soft) wv[s] = soft_linear(v); }
+                else if (v != 0.f) { wv[s] = v; need |= 1u << s; }
+            }
+        }
+        while (need) {
+            const int s0 = __builtin_ctz(need);
+            need &= need - 1u;
+            float v = 0.f;
+#pragma unroll
+            for (int s = 0; s < SOFT_SLOTS; ++s) if (s == s0) v = wv[s];
+            const float wgt = soft_gauss(v, c.sigma);
+#pragma unroll
+            for (int s = 0; s < SOFT_SLOTS; ++s) if (s == s0) wv[s] = wgt;
+        }
+        best = 0ull; bs = 0;
+#pragma unroll
+        for (int s = 0; s < SOFT_SLOTS; ++s) {
+            if (s < nslot && sc[s] != 0.f) {
+                sc[s] = soft_apply(sc[s], ((hard >> s) & 1u) ? 2.f : 0.f, wv[s], c);         // (2 > iou_hard <= 1: the slot's IoU was)
+                if (sc[s] != 0.f) {
+                    const unsigned long long k = soft_key(sc[s], ix[s]);
+                    if (k > best) { best = k; bs = s; }
+                }
+            }
+        }
+    }
+    return nk;
+}
+
+// Any candidate count: candidate i belongs to thread i % 512 for the whole walk, so cur[i] is read and written by one thread alone.
+template <class Emit>
+__device__ __forceinline__ int soft_walk_general(SoftLds& L, const float* bx, int D, int obj_idx, const int* cidx, float* cur, int nc,
+                                                 int max_out, const SoftCfg& c, Emit emit) {
+    const int tid = threadIdx.x;
+    unsigned long long best = 0ull;
+    int bp = 0;
+    for (int i = tid; i < nc; i += SOFT_THREADS) {
+        const int idx = cidx[i];
+        const float s = bx[(size_t)idx * D + obj_idx];
+        cur[i] = s;
+        const unsigned long long k = soft_key(s, idx);
+        if (k > best) { best = k; bp = i; }
+    }
+    int nk = 0;
+    while (nk < max_out) {
+        const unsigned long long g = soft_argmax(L, best);
+        if (g == 0ull) break;
+        if (best == g) {
+            const float* r = bx + (size_t)cidx[bp] * D;
+            const NBox me = make_box(r[0], r[1], r[2], r[3]);
+            L.pk[0] = me.y0; L.pk[1] = me.x0; L.pk[2] = me.y1; L.pk[3] = me.x1; L.pk[4] = me.area;
+            cur[bp] = 0.f;
+            emit(nk, (int)(0xFFFFFFFFu - (unsigned int)g), __uint_as_float((unsigned int)(g >> 32)));
+        }
+        ++nk;
+        __syncthreads();
+        if (nk >= max_out) break;
+        const NBox pk = {L.pk[0], L.pk[1], L.pk[2], L.pk[3], L.pk[4]};
+        best = 0ull; bp = 0;
+        for (int i = tid; i < nc; i += SOFT_THREADS) {
+            float s = cur[i];
+            if (s == 0.f) continue;
+            const int idx = cidx[i];
+            const float* r = bx + (size_t)idx * D;
+            const float v = soft_iou(pk, make_box(r[0], r[1], r[2], r[3]));
+            float wgt = 1.f;
+            if (c.method == SOFT_NMS_LINEAR) { if (v > c.iou_soft) wgt = soft_linear(v); }
+            else if (v != 0.f) wgt = soft_gauss(v, c.sigma);
+            s = soft_apply(s, v, wgt, c);
+            cur[i] = s;
+            if (s != 0.f) {
+                const unsigned long long k = soft_key(s, idx);
+                if (k > best) { best = k; bp = i; }
+            }
+        }
+    }
+    return nk;
+}
+
+__global__ __launch_bounds__(SOFT_THREADS) void soft_pick_kernel(const float* boxes, int64_t N, int D, int obj_idx, int C, int max_out,
+                                                                int general_only, SoftCfg c, SoftWs w) {
+    __shared__ SoftLds L;
+    __shared__ int s_nc;
+    const int cl = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, CS = C + 1;
+    const size_t bc = (size_t)b * CS + cl;
+    const int n = w.pc.hist[bc];
+    if (n == 0) return;                                      // cnt = 0 from pc_offsets
+    const size_t off = (size_t)b * N + w.pc.seg_off[bc];
+    const float* bx = boxes + (size_t)b * N * D;
+    const unsigned long long* seg = w.pc.seg + off;
+    int* cidx = w.cidx + off;
+    if (tid == 0) s_nc = 0;
+    __syncthreads();
+    for (int i = tid; i < n; i += SOFT_THREADS) {             // the members above min_score, in any order (see soft_key)
+        const int idx = (int)(seg[i] & 0xFFFFFFFFull);
+        if (bx[(size_t)idx * D + obj_idx] > c.min_score) cidx[atomicAdd(&s_nc, 1)] = idx;
+    }
+    __syncthreads();
+    const int nc = s_nc;
+    int* kidx = w.pc.kidx + ((size_t)b * C + cl) * NMS_MAXK;
+    float* ksc = w.kscore + ((size_t)b * C + cl) * NMS_MAXK;
+    auto emit = [&](int pos, int idx, float score) { kidx[pos] = idx; ksc[pos] = score; };
+    int nk;
+    if (nc <= SOFT_NMS_RESIDENT_CAP && !general_only) nk = soft_walk_resident(L, bx, D, obj_idx, cidx, nc, max_out, c, emit);
+    else nk = soft_walk_general(L, bx, D, obj_idx, cidx, w.cur + off, nc, max_out, c, emit);
+    if (tid == 0) w.pc.cnt[(size_t)b * C + cl] = nk;
+}
+
+__global__ __launch_bounds__(256) void soft_finish_kernel(const float* boxes, int64_t N, int D, int obj_idx, int C, int max_out, SoftWs w,
+                                                          float* rows, int32_t* kept, int32_t* count) {
+    pc_finish_body<true>(boxes, N, D, C, max_out, w.pc, rows, kept, count, obj_idx, w.kscore);
+}
+
+hipError_t launch_soft_nms(const SoftNmsParams& sp, hipStream_t st) {
+    const NmsParams& p = sp.n;
+    const int C = p.C;
+    if (p.max_out > NMS_MAXK || p.max_out < 1 || C < 1 || C > BYOLO_MAX_CLASSES) return hipErrorInvalidValue;
+    if (C > 1 && (p.cls_start < 0 || p.cls_start + C > p.D)) return hipErrorInvalidValue;
+    if (p.obj_idx < 0 || p.obj_idx >= p.D) return hipErrorInvalidValue;
+    if (p.N >= (1ll << 31) || p.ws_bytes < soft_ws_layout(p.B, p.N, C, nullptr, nullptr)) return hipErrorInvalidValue;
+    if (sp.method != SOFT_NMS_LINEAR && sp.method != SOFT_NMS_GAUSSIAN) return hipErrorInvalidValue;
+    if (!(sp.min_score >= 0.f)) return hipErrorInvalidValue;  // 0 marks a dead candidate: live scores are above min_score >= 0
+    SoftWs w;
+    soft_ws_layout(p.B, p.N, C, reinterpret_cast<char*>(p.ws), &w);
+    const SoftCfg c = {sp.method, sp.sigma, sp.iou_soft, sp.iou_hard, sp.min_score};
+    const dim3 by_row((unsigned)((p.N + 255) / 256), p.B), by_tile((unsigned)((p.N + PC_TILE - 1) / PC_TILE), p.B), by_class(C, p.B);
+    if (hipError_t e = launch_zero_words(w.pc.hist, (int64_t)2 * p.B * (C + 1), st); e != hipSuccess) return e;
+    if (C <= PC_DIRECT_C)
+        hipLaunchKernelGGL(pc_classify_kernel, by_row, dim3(256), 0, st, p.boxes, p.N, p.D, p.obj_idx, p.cls_start, C, w.pc.cls, w.pc.hist);
+    else
+        hipLaunchKernelGGL(pc_classify_tiled_kernel, by_tile, dim3(256), 0, st, p.boxes, p.N, p.D, p.obj_idx, p.cls_start, C, w.pc.cls, w.pc.hist);
+    hipLaunchKernelGGL(pc_offsets_kernel, dim3(p.B), dim3(64), 0, st, C, 0, w.pc);
+    hipLaunchKernelGGL(pc_scatter_kernel, by_row, dim3(256), 0, st, p.boxes, p.N, p.D, p.obj_idx, C, w.pc);
+    hipLaunchKernelGGL(soft_pick_kernel, by_class, dim3(SOFT_THREADS), 0, st, p.boxes, p.N, p.D, p.obj_idx, C, p.max_out,
+                       p.general_only != 0 ? 1 : 0, c, w);
+    hipLaunchKernelGGL(soft_finish_kernel, dim3((unsigned)(((int64_t)C * p.max_out + PC_ROWS - 1) / PC_ROWS), p.B), dim3(256), 0, st,
+                       p.boxes, p.N, p.D, p.obj_idx, C, p.max_out, w, p.rows, p.kept, p.count);
     return hipGetLastError();
 }
 

@@ -24,6 +24,12 @@ batch is also matched at each of these thresholds in the same pass (one more ker
 result gains 'ladder': AP and LAMR per class and threshold and their mean -- AP50, AP75 and the averaged AP of the detection
 benchmarks.  With `box_vote_compare` both evaluators carry the ladder and the two are logged side by side per threshold.
 
+`soft_nms` (True or a dict of settings, as `engine_options['soft_nms']`; INTEGRATION.md "Soft-NMS"): the model runs the soft-NMS in
+place of the hard one and its rows -- with the decayed scores -- are scored.  With `soft_nms_compare: True` the model runs the hard
+NMS, `Engine.soft_nms` runs on the same pre-NMS rows of every batch, a second evaluator scores them and metrics.json carries the two
+result dicts under 'nms' and 'soft_nms' (the ladder included when `iou_thresholds` is set), logged side by side per class and
+threshold.  `soft_nms_compare` together with `box_vote_compare` is refused: one comparison per run.
+
 `box_vote_sweep` (a list of at most 8 settings dicts; needs `box_vote_compare: True`): the model still runs ONCE per batch with
 voting off; every entry gets its own `Engine.box_vote` call on that batch's rows and its own evaluator, metrics.json gains
 'box_vote_sweep': [{'settings': ..., **result}, ...] and a table of mean AP per entry is logged -- the tool for choosing `sigma_t`
@@ -79,6 +85,26 @@ def check_config(config, model='bayesian'):
         raise ValueError('box_vote_compare: True needs box_vote')
     if cfg['box_vote'] and not cfg['box_vote_compare']:              # the model votes in place; the comparison votes beside the NMS rows
         cfg['engine_options'] = dict(cfg.get('engine_options', {}), box_vote=cfg['box_vote'])
+    # soft_nms / soft_nms_compare: both keys stay absent when absent (metrics.json carries the config)
+    if cfg.get('soft_nms') is not None or cfg.get('soft_nms_compare') is not None:
+        soft = cfg.setdefault('soft_nms', None)
+        cfg.setdefault('soft_nms_compare', False)
+        if soft is not None and soft is not True and soft is not False and not isinstance(soft, dict):
+            raise ValueError('soft_nms is True or a dict of settings')
+        if cfg['soft_nms_compare'] not in (True, False):
+            raise ValueError('soft_nms_compare is True or False')
+        if cfg['soft_nms_compare'] and cfg['box_vote_compare']:
+            raise ValueError('soft_nms_compare together with box_vote_compare: one comparison per run')
+        if cfg['soft_nms_compare'] and not soft:
+            soft = cfg['soft_nms'] = True                            # the comparison alone: the default settings
+        if soft:
+            from byolo.engine import Engine
+            try:
+                Engine._soft_cfg({} if soft is True else soft)
+            except TypeError as e:
+                raise ValueError(str(e))
+            if not cfg['soft_nms_compare']:                          # the model runs the soft-NMS itself; the comparison runs it beside the hard one
+                cfg['engine_options'] = dict(cfg.get('engine_options', {}), soft_nms=soft)
     from byolo.evaluate import ladder_thresholds
     ladder_thresholds(cfg.get('iou_thresholds'))                     # ValueError on a bad ladder; both keys stay absent when absent
     if cfg.get('box_vote_sweep') is not None:
@@ -133,21 +159,31 @@ def build_model(cfg):
     return m, checkpoint
 
 
-def score(model, feed, evaluator, seed=0, max_batches=None, points=None, vote=None, vote_evaluator=None, sweep=()):
+def score(model, feed, evaluator, seed=0, max_batches=None, points=None, vote=None, vote_evaluator=None, sweep=(), soft=None,
+          soft_evaluator=None):
     """Model.run -> Evaluator.add over the batches of `feed` (the 'eval' split of lib_yolo.dataset_utils._Feed); returns the
     number of images.  points: a list that receives (time, images so far) after every batch.  vote (settings) and
     vote_evaluator: every batch's NMS rows are also voted (Engine.box_vote) and the voted rows scored by vote_evaluator.
-    sweep: [(settings, evaluator)], each voted and scored the same way on the same rows of the one forward."""
+    sweep: [(settings, evaluator)], each voted and scored the same way on the same rows of the one forward.  soft (settings) and
+    soft_evaluator: Engine.soft_nms runs on every batch's pre-NMS rows beside the model's hard NMS (and, where the model votes, is
+    voted with the same settings) and its rows are scored by soft_evaluator."""
     images = 0
     for step, b in enumerate(feed):
         if max_batches is not None and step >= max_batches:
             break
-        res = model.run(b['img'], seed=seed + step, want_boxes=vote_evaluator is not None)
+        res = model.run(b['img'], seed=seed + step, want_boxes=vote_evaluator is not None or soft_evaluator is not None)
         evaluator.add(res['rows'], res['count'][:, 0], b['boxes'], b['labels'], b['counts'])
         for settings, vev in ([(vote, vote_evaluator)] if vote_evaluator is not None else []) + list(sweep):
             voted = res.get('engine', model.engine).box_vote(res['boxes'], res, model.obj_idx, model.cls_start_idx,
                                                              geom=model.det_layers, **({} if settings is True else dict(settings)))
             vev.add(voted['rows'], res['count'][:, 0], b['boxes'], b['labels'], b['counts'])
+        if soft_evaluator is not None:
+            eng = res.get('engine', model.engine)
+            sres = eng.soft_nms(res['boxes'], model.obj_idx, model.cls_start_idx, **({} if soft is True else dict(soft)))
+            if vote and vote_evaluator is None:           # the model voted behind its hard NMS: the same behind the soft one
+                sres.update(eng.box_vote(res['boxes'], sres, model.obj_idx, model.cls_start_idx, geom=model.det_layers,
+                                         **({} if vote is True else dict(vote))))
+            soft_evaluator.add(sres['rows'], sres['count'][:, 0], b['boxes'], b['labels'], b['counts'])
         images += int(b['img'].shape[0])
         if points is not None:
             points.append((time.perf_counter(), images))
@@ -174,9 +210,9 @@ def _ap_at(lad_class, thresholds, t):
     return lad_class['ap'][hits[0]] if hits else None
 
 
-def ladder_lines(lad, voted=None):
+def ladder_lines(lad, voted=None, names=('NMS rows', 'voted rows')):
     """Log lines of a 'ladder' result: per class AP50 / AP75 (where the ladder holds them) and the mean; with `voted` (the voted
-    rows' ladder) the two side by side per threshold."""
+    rows' ladder, or the soft-NMS rows' under other `names`) the two side by side per threshold."""
     thr = lad['iou_thresholds']
     lines = []
     for c in lad['classes']:
@@ -186,9 +222,9 @@ def ladder_lines(lad, voted=None):
     if voted is not None:
         for c, v in zip(lad['classes'], voted['classes']):
             for k, t in enumerate(thr):
-                lines.append('class {:3d}: AP at IoU {:.2f}: NMS rows {:.4f}, voted rows {:.4f}'.format(c['class'], t, c['ap'][k], v['ap'][k]))
-            lines.append('class {:3d}: mean AP: NMS rows {:.4f}, voted rows {:.4f}'.format(c['class'], c['ap_mean'], v['ap_mean']))
-        lines.append('mean AP: NMS rows {:.4f}, voted rows {:.4f}'.format(lad['ap_mean'], voted['ap_mean']))
+                lines.append('class {:3d}: AP at IoU {:.2f}: {} {:.4f}, {} {:.4f}'.format(c['class'], t, names[0], c['ap'][k], names[1], v['ap'][k]))
+            lines.append('class {:3d}: mean AP: {} {:.4f}, {} {:.4f}'.format(c['class'], names[0], c['ap_mean'], names[1], v['ap_mean']))
+        lines.append('mean AP: {} {:.4f}, {} {:.4f}'.format(names[0], lad['ap_mean'], names[1], voted['ap_mean']))
     return lines
 
 
@@ -223,13 +259,15 @@ def evaluate(config, model='bayesian'):
     ev = new_ev()
     ev_vote = new_ev() if cfg['box_vote_compare'] else None
     sweep = [(settings, new_ev()) for settings in (cfg.get('box_vote_sweep') or [])]
+    ev_soft = new_ev() if cfg.get('soft_nms_compare') else None
     feed = dataset_utils._Feed(cfg, 'data', 'eval', device=m.engine.torch_device)
     try:
         t0 = time.time()
         points = []
         images = score(m, feed, ev, seed=int(cfg['seed']), max_batches=cfg['eval_batches'], points=points, vote=cfg['box_vote'],
-                       vote_evaluator=ev_vote, sweep=sweep)
+                       vote_evaluator=ev_vote, sweep=sweep, soft=cfg.get('soft_nms'), soft_evaluator=ev_soft)
         metrics = ev.finish()
+        soft_metrics = ev_soft.finish() if ev_soft is not None else None
         voted_metrics = ev_vote.finish() if ev_vote is not None else None
         sweep_metrics = [e.finish() for _, e in sweep]
         loop_seconds = time.time() - t0
@@ -240,6 +278,12 @@ def evaluate(config, model='bayesian'):
             ev_vote.close()
         for _, e in sweep:
             e.close()
+        if ev_soft is not None:
+            ev_soft.close()
+    if soft_metrics is not None:
+        for c, v in zip(metrics['classes'], soft_metrics['classes']):
+            logging.info('class {:3d}: AP at IoU {:.2f}: NMS rows {:.4f}, soft-NMS rows {:.4f}; LAMR {:.4f}, {:.4f}'.format(
+                c['class'], cfg['iou_thresh'], c['ap'], v['ap'], c['lamr'], v['lamr']))
     if voted_metrics is not None:
         for c, v in zip(metrics['classes'], voted_metrics['classes']):
             logging.info('class {:3d}: AP at IoU {:.2f}: NMS rows {:.4f}, voted rows {:.4f}'.format(c['class'], cfg['iou_thresh'], c['ap'], v['ap']))
@@ -250,7 +294,9 @@ def evaluate(config, model='bayesian'):
             name, u['tp']['mean'], u['tp']['finite'], u['tp']['nonfinite'], u['fp']['mean'], u['fp']['finite'], u['fp']['nonfinite'],
             u['auroc_fp']))
     if 'ladder' in metrics:
-        for line in ladder_lines(metrics['ladder'], voted_metrics['ladder'] if voted_metrics is not None else None):
+        other = voted_metrics if voted_metrics is not None else soft_metrics
+        for line in ladder_lines(metrics['ladder'], other['ladder'] if other is not None else None,
+                                 names=('NMS rows', 'voted rows' if soft_metrics is None else 'soft-NMS rows')):
             logging.info(line)
     for line in sweep_lines(cfg.get('box_vote_sweep') or [], sweep_metrics, cfg['iou_thresh']):
         logging.info(line)
@@ -264,6 +310,9 @@ def evaluate(config, model='bayesian'):
     if voted_metrics is not None:                         # both result dicts side by side; the figures logged above are the NMS rows'
         metrics = dict({k: v for k, v in metrics.items() if k not in voted_metrics}, nms={k: metrics[k] for k in voted_metrics},
                        box_vote=voted_metrics)
+    if soft_metrics is not None:                          # likewise: the hard NMS's result beside the soft-NMS's
+        metrics = dict({k: v for k, v in metrics.items() if k not in soft_metrics}, nms={k: metrics[k] for k in soft_metrics},
+                       soft_nms=soft_metrics)
     if sweep:
         metrics['box_vote_sweep'] = [dict(r, settings=settings) for (settings, _), r in zip(sweep, sweep_metrics)]
     with open(os.path.join(out_path, 'metrics.json'), 'w') as f:

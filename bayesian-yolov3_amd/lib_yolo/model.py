@@ -79,6 +79,8 @@ class ModelBuilder:
         opts = dict(engine_options or {})
         # 'box_vote': True | {settings}: variance voting behind the NMS (Engine.set_box_vote), switched on once the detection layers exist
         self.__box_vote = opts.pop('box_vote', None)
+        # 'soft_nms': True | {settings}: the soft-NMS in place of the hard one (Engine.set_soft_nms)
+        self.__soft_nms = opts.pop('soft_nms', None)
         self.engine = Engine(img_size=shape[1:], cls_cnt=cls_cnt, **opts)
         self.T = 1
 
@@ -107,6 +109,8 @@ class ModelBuilder:
 
     def get_model(self, obj_idx, cls_start_idx):
         assert obj_idx < cls_start_idx
+        if self.__soft_nms:
+            self.engine.set_soft_nms(self.__soft_nms)
         if self.__box_vote:
             self.engine.set_box_vote(self.__box_vote)
         return Model(self.__layers, self.__det_layers, self.__cls_cnt, obj_idx, cls_start_idx, builder=self)

@@ -727,6 +727,39 @@ BYOLO_API int32_t byolo_box_vote(byolo_t* h, const float* d_boxes, int32_t B, in
 BYOLO_API int32_t byolo_set_box_vote(byolo_t* h, const byolo_vote_cfg* cfg);
 BYOLO_API int32_t byolo_box_vote_counts(byolo_t* h, int32_t* d_vote_n, int32_t B, int32_t cap, void* stream);
 
+/* ---- soft-NMS (Bodla, Singh, Chellappa, Davis, ICCV 2017, Algorithm 1; no counterpart in the reference; csrc/tail_kernels.hip
+ * soft_*; INTEGRATION.md "Soft-NMS" has the definition in full, tests/_soft_nms_ref.py restates it) ---------------------------
+ * In place of the hard greedy NMS: per (image, class) -- the classes of byolo_sort_nms for the same nms_mode -- the candidate with
+ * the largest CURRENT score is picked (ties: lower row index), and the current score of every remaining candidate i is multiplied
+ * by a weight of v = the NMS's float32 IoU(pick, i):
+ *   BYOLO_SOFT_NMS_LINEAR     w = 1 - v where v > iou_soft, else 1
+ *   BYOLO_SOFT_NMS_GAUSSIAN   w = float32(exp(-(v * v) / sigma)), formed in float64
+ * Candidates are the class's members with score > min_score; a candidate leaves when v > iou_hard (1: never) or its score is no
+ * longer > min_score.  The walk ends after max_out picks or when no candidate is left.
+ * Outputs as byolo_sort_nms (d_rows [B, cap, D] in pick order, class 0's first; d_kept; d_count; byolo_nms_class_counts), except
+ * that column obj_idx of a kept row holds its score at the moment it was picked; within a class these are non-increasing.
+ * Up to BYOLO_SOFT_NMS_RESIDENT candidates of one (image, class) are held in registers; beyond that (and for every class under
+ * byolo_plan_opts.nms_general) a slower path keeps the current scores in the workspace -- same bytes.  Deterministic.
+ * The defaults (Gaussian, sigma 0.5, iou_soft 0.3, iou_hard 1, min_score 0.001) are the paper's; nobody has tuned them on this
+ * detector.  Refused with BYOLO_ERR_ARG, the field named in byolo_last_error: a wrong struct_bytes, an unknown method, sigma not
+ * > 0 and finite, iou_soft / iou_hard outside [0, 1], min_score negative or not finite.
+ * d_ws >= byolo_soft_nms_workspace_bytes(B, N, nms_mode, cls_cnt) (0 for arguments the mode refuses).
+ * byolo_set_soft_nms(h, cfg): byolo_forward runs this stage in place of the hard NMS (cfg NULL: off, the default; with it off every
+ * output is what it was without this entry point); box voting (byolo_set_box_vote) then votes behind it.  Its workspace is part
+ * of byolo_workspace_bytes while it is on. */
+#define BYOLO_SOFT_NMS_RESIDENT 8192
+enum { BYOLO_SOFT_NMS_LINEAR = 0, BYOLO_SOFT_NMS_GAUSSIAN = 1 };
+typedef struct byolo_soft_nms_cfg {
+    int32_t struct_bytes;          /* sizeof(byolo_soft_nms_cfg) of the caller's header: a mismatch is BYOLO_ERR_ARG */
+    int32_t method;                /* BYOLO_SOFT_NMS_* */
+    float sigma, iou_soft, iou_hard, min_score;
+} byolo_soft_nms_cfg;
+BYOLO_API size_t byolo_soft_nms_workspace_bytes(int32_t B, int64_t N, int32_t nms_mode, int32_t cls_cnt);
+BYOLO_API int32_t byolo_soft_nms(byolo_t* h, const float* d_boxes, int32_t B, int64_t N, int32_t D, int32_t obj_idx,
+                                 int32_t cls_start_idx, int32_t nms_mode, int32_t max_out, const byolo_soft_nms_cfg* cfg,
+                                 void* d_ws, size_t ws_bytes, float* d_rows, int32_t* d_kept, int32_t* d_count, void* stream);
+BYOLO_API int32_t byolo_set_soft_nms(byolo_t* h, const byolo_soft_nms_cfg* cfg);
+
 #ifdef __cplusplus
 }
 #endif
