@@ -13,7 +13,7 @@ of the sums (16-product MFMA blocks, K slices, the Winograd fold) and the epilog
 that a correction term lost in ONE 32-channel chunk at one tap, one image column or one transform point is >= 4 x that bound on every
 one of these layers.  No exclusions: every element counts, NaN / inf fail.  From the profile of the same forward each case asserts that
 the kernel it was written for ran (3000 + BN the shared-tap tile, 2000 + BN the 1x1 loop, 1000 + BN the general loop, 140 / -4 the
-Winograd pair and its channels per workgroup, ksplit = 3 / a stream-K grid).  {E, S, F} go to record_parity in units of max(S, F).
+Winograd pair and its channels per workgroup, ksplit = 3 / a stream-K grid; -1 the direct small-Cin kernels, which serve both precisions).  {E, S, F} go to record_parity in units of max(S, F).
 
 The fused paths leave no layer to read (back-to-back 3x3 + 1x1, the fed Winograd transform): the same graph is built twice, the handle
 that keeps every output is held to float64 as above, the other one's raw detection outputs must equal its bits."""
@@ -89,6 +89,8 @@ def _where(g, d, launches, worst):
         tile = (s % chunk) * th * tw + (y // 2) * tw + x // 2
         return "Winograd chunk %d of %d, output tile %d, unit (row tile %d, column tile %d of %d channels)" % (s // chunk, n_chunks, tile, tile // 64, c // bn, bn)
     l = launches[-1]
+    if l["variant"] == -1:
+        return "row %d of %d, 8-channel group %d of the direct kernel; K = %d" % ((s * d["H"] + y) * d["W"] + x, l["M"], c // 8, l["K"])
     bn = l["variant"] % 1000
     row = (s * d["H"] + y) * d["W"] + x
     return ("row %d of %d: row tile %d, column tile %d of %d channels; K = %d in %s" %
@@ -101,6 +103,9 @@ def _check_kernel(name, g, d, launches, opts):
     want = d["check"]
     variants = [l["variant"] for l in launches]
     if want.get("multi"):
+        return
+    if "v" in want and "loop" not in want:                 # the launch list itself (the direct small-Cin kernels: variant -1)
+        assert variants == want["v"], (name, d["name"], variants, want["v"])
         return
     if "wino" in want and not (140 not in variants and "fallback" in want):
         n = variants.count(140)
