@@ -1615,8 +1615,20 @@ static int32_t calibrate_bn_impl(byolo_t* h, const float* d_img, int32_t B, void
     float* d_var = d_mean + h->maxC;
     std::vector<float> sc, sf;
     const FwdArgs cal{d_img, B, 1, 0, 0, nullptr, d_workspace, nullptr, nullptr, nullptr, nullptr};      // a call without dropout
-    if (h->precision == 1 && h->img_split)
-        HIPCHK(h, launch_f32_to_split(d_img, reinterpret_cast<float*>(ws + h->plan.img_split_off), (int64_t)B * h->cfg.img_h * h->cfg.img_w * h->cfg.img_c, ACT_SCALE, st));
+    // Split precision: every activation this call stores is range-checked like a forward's (BYOLO_ERR_RANGE naming the layer, never a
+    // stored inf).  The words are read after each layer -- the next layer's statistics would be those of the inf -- so a flag an
+    // asynchronous forward left unread is reported first, under its own name, rather than taken for a layer of this call.
+    auto range_check = [&](const char* what) -> int32_t {
+        unsigned f = 0, ly = 0xFFFFFFFFu;
+        int32_t rc = read_status(h, st, &f, &ly); if (rc) return rc;
+        if (f) { (void)byolo_clear_status(h, stream); return range_error(h, what, f, ly); }
+        return BYOLO_OK;
+    };
+    if (h->precision == 1) { rc = range_check("byolo_calibrate_bn: left by an earlier byolo_forward"); if (rc) return rc; }
+    if (h->precision == 1 && h->img_split) {
+        HIPCHK(h, launch_f32_to_split(d_img, reinterpret_cast<float*>(ws + h->plan.img_split_off), (int64_t)B * h->cfg.img_h * h->cfg.img_w * h->cfg.img_c, ACT_SCALE, st, h->d_status));
+        rc = range_check("byolo_calibrate_bn"); if (rc) return rc;
+    }
     for (const Step& s : h->steps) {
         Layer& l = h->layers[s.layer];
         const bool split = h->precision == 1;
@@ -1669,8 +1681,10 @@ static int32_t calibrate_bn_impl(byolo_t* h, const float* d_img, int32_t B, void
         }
         const float* res = l.fused_residual >= 0
             ? reinterpret_cast<const float*>(ws + h->plan.off[h->layers[l.fused_residual].ref[0]]) : nullptr;
-        HIPCHK(h, launch_bn_act_inplace(p.dst, p.M, N, dptr(h, l.scale_off), dptr(h, l.shift_off), res, 1, split, st));
+        HIPCHK(h, launch_bn_act_inplace(p.dst, p.M, N, dptr(h, l.scale_off), dptr(h, l.shift_off), res, 1, split, st, split ? h->d_status : nullptr, s.layer));
+        if (split) { rc = range_check("byolo_calibrate_bn"); if (rc) return rc; }
     }
+    if (h->precision == 1) return range_check("byolo_calibrate_bn");     // (a trailing element-wise add; waits for the stream)
     HIPCHK(h, hipStreamSynchronize(st));
     return BYOLO_OK;
 }

@@ -241,7 +241,7 @@ hipError_t launch_channel_stats(const float* x, int64_t M, int C, float* d_mean,
 // in place: x = [residual +] leaky(x * scale + shift)
 // split: x holds fp32 on entry and [4 hi | 4 lo] groups on exit (C % 4 == 0), the residual is a split-f16 tensor
 hipError_t launch_bn_act_inplace(float* x, int64_t M, int C, const float* scale, const float* shift,
-                                 const float* residual, int leaky, bool split, hipStream_t st);
+                                 const float* residual, int leaky, bool split, hipStream_t st, unsigned* status = nullptr, int layer = 0);   // split: status as finish_tile raises it
 // scale = gamma * rsqrt(var + eps), shift = beta - mean * scale   (device-side fold)
 hipError_t launch_fold_bn(const float* gamma, const float* beta, const float* mean, const float* var, float eps,
                           float* scale, float* shift, int C, hipStream_t st);

@@ -429,9 +429,11 @@ __global__ void bn_act_inplace_kernel(float* x, int64_t total, int C, const floa
         x[i] = v;
     }
 }
-// split precision: fp32 in, [4 hi | 4 lo] groups out (in place, one group per thread); the residual is a split-f16 tensor
+// split precision: fp32 in, [4 hi | 4 lo] groups out (in place, one group per thread); the residual is a split-f16 tensor.
+// A value beyond the format's range raises the status words like every other kernel that stores activations (finish_tile).
 __global__ void bn_act_inplace_split_kernel(f32x4* x, int64_t total4, int C4, const float* scale, const float* shift,
-                                            const f32x4* residual, int leaky) {
+                                            const f32x4* residual, int leaky, unsigned* status, int layer) {
+    float vmax = 0.f;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += (int64_t)gridDim.x * blockDim.x) {
         const int c = (int)(i % C4) * 4;
         f32x4 v = x[i];
@@ -441,18 +443,20 @@ __global__ void bn_act_inplace_split_kernel(f32x4* x, int64_t total4, int C4, co
             if (leaky) v[q] = fmaxf(v[q], 0.1f * v[q]);
         }
         if (residual) v += epi::split_decode4(residual[i]);
+        vmax = epi::absmax4(vmax, v);
         x[i] = epi::split_encode4(v);
     }
+    if (status && vmax >= 65520.f) { atomicOr(status, 1u); atomicMin(status + 1, (unsigned)layer); }
 }
 hipError_t launch_bn_act_inplace(float* x, int64_t M, int C, const float* scale, const float* shift,
-                                 const float* residual, int leaky, bool split, hipStream_t st) {
+                                 const float* residual, int leaky, bool split, hipStream_t st, unsigned* status, int layer) {
     const int64_t total = M * C;
     int64_t blocks = (total + 255) / 256;
     if (blocks > 8192) blocks = 8192;
     if (split) {
         if (C & 3) return hipErrorInvalidValue;
         hipLaunchKernelGGL(bn_act_inplace_split_kernel, dim3((unsigned)blocks), dim3(256), 0, st, reinterpret_cast<f32x4*>(x), total / 4,
-                           C / 4, scale, shift, reinterpret_cast<const f32x4*>(residual), leaky);
+                           C / 4, scale, shift, reinterpret_cast<const f32x4*>(residual), leaky, status, layer);
         return hipGetLastError();
     }
     hipLaunchKernelGGL(bn_act_inplace_kernel, dim3((unsigned)blocks), dim3(256), 0, st, x, total, C, scale, shift,

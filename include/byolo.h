@@ -407,7 +407,9 @@ BYOLO_API int32_t byolo_loss(byolo_t* h, int32_t kind, int32_t aleatoric_loss, i
  *     byolo_layer_output reads the (B, T = 1) run the calibration left in d_workspace.
  * Frames that give fewer than about 9 rows at the coarsest grid (B * h * w at stride 32) produce near-zero variances: the folded
  * 1 / sqrt(var + 1e-5) then amplifies rounding by up to 316 per layer and the weights are ill conditioned.  Statistics that are
- * not finite are BYOLO_ERR_ARG. */
+ * not finite are BYOLO_ERR_ARG.  BYOLO_PREC_SPLIT_F16: the activations the call stores are range-checked like a forward's -- one
+ * beyond |v| < 16380 (the image included) ends the call with BYOLO_ERR_RANGE naming the layer, its statistics already set, the
+ * layers behind it untouched and the status words cleared; words an asynchronous forward left raised are reported first, the same way. */
 BYOLO_API int32_t byolo_calibrate_bn(byolo_t* h, const float* d_img, int32_t B, void* d_workspace, size_t workspace_bytes,
                            void* stream);
 

@@ -288,10 +288,12 @@ def applicable_f32(k, stride, H, W, wino=None):
     return [1, 2] + ([3] if k == 3 else []) + [4]
 
 
-def layer_split(sources, p, scope, k, stride, bn=True, drop=None, residual=None, det=False, wino=False, mutant=None, direct=False):
+def layer_split(sources, p, scope, k, stride, bn=True, drop=None, residual=None, det=False, wino=False, mutant=None, direct=False,
+                halves=False):
     """S: the layer in emulated split-f16 arithmetic.  mutant: a key of MUTANTS (see applicable()).  direct: one of the small-Cin
     kernels (csrc/conv_kernels.hip: Cin not a multiple of 32) -- an fp32 convolution of the decoded input with the fp32 weights, the
-    output rounded to hi + lo; its defects 1 .. 3 are MUTANTS_F32's, 4 is the residual's hi half as everywhere in this mode."""
+    output rounded to hi + lo; its defects 1 .. 3 are MUTANTS_F32's, 4 is the residual's hi half as everywhere in this mode.
+    halves: the stored pair (hi, lo) itself, in units of the value (tests/_range_plant.py: an element beyond the range has hi = inf)."""
     x = gather(sources, torch.float32)
     w = p[scope + "/conv2d/kernel"].float()
     if direct:
@@ -306,6 +308,8 @@ def layer_split(sources, p, scope, k, stride, bn=True, drop=None, residual=None,
     y, _ = _epilogue(z, None, p, scope, torch.float32, bn, drop, residual, det)
     if not det:                                            # a detection head's raw output stays fp32
         hi, lo = _split(y, ACT_SCALE)
+        if halves:
+            return hi, lo
         y = hi + lo
     return y
 
