@@ -70,6 +70,16 @@ class EvalLadderCfg(ctypes.Structure):
     _fields_ = [("struct_bytes", ctypes.c_int32), ("n_thr", ctypes.c_int32), ("thresholds", ctypes.c_float * EVAL_LADDER_MAX)]
 
 
+EVAL_SUBSETS_MAX = 16                                                    # BYOLO_EVAL_SUBSETS_MAX
+
+
+class EvalSubsetsCfg(ctypes.Structure):
+    """include/byolo.h byolo_eval_subsets_cfg (field for field; tests/test_eval_subsets_cpu.py compares the two)."""
+    _fields_ = [("struct_bytes", ctypes.c_int32), ("n_subsets", ctypes.c_int32), ("lo", ctypes.c_float * EVAL_SUBSETS_MAX),
+                ("hi", ctypes.c_float * EVAL_SUBSETS_MAX), ("img_h", ctypes.c_float), ("ignore_thresh", ctypes.c_float),
+                ("height_slack", ctypes.c_float), ("ignore_other_classes", ctypes.c_int32)]
+
+
 class EvalSummary(ctypes.Structure):
     """include/byolo.h byolo_eval_summary."""
     _fields_ = [(n, ctypes.c_int32) for n in ("struct_bytes", "overflow", "record_words", "reserved")] + \
@@ -199,6 +209,11 @@ PROTOTYPES = {
     "byolo_eval_ladder_bytes": (_sz, [_i64, _i32]),
     "byolo_eval_set_ladder": (_i32, [_vp, _P(EvalLadderCfg), _vp]),
     "byolo_eval_ladder_records": (_i32, [_vp, _vp, _i64, _i64, _vp]),
+    "byolo_eval_subsets_bytes": (_sz, [_i64, _i32]),
+    "byolo_eval_subsets_state_bytes": (_sz, [_i32, _i32]),
+    "byolo_eval_set_subsets": (_i32, [_vp, _P(EvalSubsetsCfg), _vp, _vp]),
+    "byolo_eval_subsets_records": (_i32, [_vp, _vp, _i64, _i64, _vp]),
+    "byolo_eval_subsets_counts": (_i32, [_vp, _P(_i64), _i32, _vp]),
     "byolo_box_vote_workspace_bytes": (_sz, [_i32, _i64]),
     "byolo_box_vote": (_i32, [_vp, _vp, _i32, _i64, _i32, _i32, _i32, _i32, _P(VoteCfg), _P(EvalLocCfg), _vp, _vp, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
     "byolo_set_box_vote": (_i32, [_vp, _P(VoteCfg)]),

@@ -13,7 +13,12 @@ positive and its matched box back to the raw location values at the detection's 
 
 With a ladder of IoU thresholds (`iou_thresholds`), `add` launches one more kernel that matches every image once per threshold
 -- the matching differs per threshold, so the ladder cannot be derived from the records of one -- and `finish` adds AP and LAMR
-per threshold and their mean (AP50, AP75, AP over 0.50 : 0.05 : 0.95) from ONE sorted table."""
+per threshold and their mean (AP50, AP75, AP over 0.50 : 0.05 : 0.95) from ONE sorted table.
+
+With subsets of the ground truth by pixel height (`subsets`), `add` launches one more kernel that matches every image once per
+subset under the ignore rule of the pedestrian benchmarks -- a detection on an `ignore` box, on a box outside the subset's height
+range or far outside that range itself is neither a true nor a false positive -- and `finish` adds AP and LAMR per subset and
+class over the detections that are not ignored, from the same sorted table."""
 import ctypes
 
 import numpy as np
@@ -138,6 +143,70 @@ def ladder_metrics(thresholds, cum_tp, cum_fp, class_start, class_gt, n_images):
             'ap_mean': float(_seq_sum(with_gt) / np.float64(len(with_gt))) if with_gt else float('nan')}
 
 
+ECP_HEIGHTS = [{'name': 'reasonable', 'min_height': 40.0}, {'name': 'small', 'min_height': 30.0, 'max_height': 60.0},
+               {'name': 'all', 'min_height': 20.0}]
+
+
+def height_subsets(subsets):
+    """[(name, float32 lo, float32 hi)] of the half-open height ranges [lo, hi) in pixels: None (off), the preset 'ecp_heights'
+    or a list of 1 .. 16 dicts {'name', 'min_height', 'max_height'} (absent bounds: 0 and inf).  Raises ValueError on anything
+    else.  'ecp_heights' is reasonable [40, inf), small [30, 60) and all [20, inf): the HEIGHT halves of the EuroCity Persons
+    subsets of those names.  The records of the shards carry no occlusion tags, so the other half of the benchmark's definition
+    -- how much of a person may be hidden -- is not applied; every box of the height range is counted whatever hides it."""
+    if subsets is None:
+        return None
+    what = "subsets is None, 'ecp_heights' or a list of {'name', 'min_height', 'max_height'} dicts, not %r"
+    if isinstance(subsets, str):
+        if subsets != 'ecp_heights':
+            raise ValueError(what % (subsets,))
+        subsets = ECP_HEIGHTS
+    if not isinstance(subsets, (list, tuple)) or not all(isinstance(e, dict) for e in subsets):
+        raise ValueError(what % (subsets,))
+    if not 1 <= len(subsets) <= _lib.EVAL_SUBSETS_MAX:
+        raise ValueError('subsets holds %d entries, not 1 .. %d' % (len(subsets), _lib.EVAL_SUBSETS_MAX))
+    out = []
+    for k, e in enumerate(subsets):
+        unknown = sorted(set(e) - {'name', 'min_height', 'max_height'})
+        if unknown or not isinstance(e.get('name'), str):
+            raise ValueError("subsets[%d] needs a 'name' and may have 'min_height' and 'max_height', not %r" % (k, e))
+        try:
+            lo, hi = np.float32(e.get('min_height', 0.0)), np.float32(e.get('max_height', float('inf')))
+        except (TypeError, ValueError):
+            raise ValueError('subsets[%d]: the bounds are numbers, not %r' % (k, e))
+        if not (lo >= 0 and lo < hi):                              # NaN fails both
+            raise ValueError('subsets[%d]: the height range [%r, %r) is NaN, negative or inverted' % (k, float(lo), float(hi)))
+        out.append((e['name'], lo, hi))
+    return out
+
+
+def subset_metrics(subsets, state, cum_tp, cum_fp, class_start, counts, n_images):
+    """The 'subsets' part of the result.  state [S, n]: the 2-bit states of the sorted table (0 false positive, 1 true positive,
+    2 ignored by a region, 3 ignored by its height); cum_tp / cum_fp [S, n]: the cumulative integers per class in that order,
+    which an ignored record leaves as they are; counts [S][C]: the counted boxes.  The ignored records are REMOVED before
+    `ap_lamr` sees the integers -- carried along, a run of them at the head of a class would be 0 / 0."""
+    out = []
+    for s, (name, lo, hi) in enumerate(subsets):
+        classes = []
+        for c in range(len(counts[s])):
+            a, b = int(class_start[c]), int(class_start[c + 1])
+            st = np.asarray(state[s, a:b])
+            kept = st < 2
+            n_gt = int(counts[s][c])
+            ap, lamr = ap_lamr(np.asarray(cum_tp[s, a:b])[kept], np.asarray(cum_fp[s, a:b])[kept], n_gt, n_images)
+            classes.append({'class': c, 'n_gt': n_gt, 'n_det': int(kept.sum()), 'n_ignored_region': int((st == 2).sum()),
+                            'n_ignored_height': int((st == 3).sum()), 'n_tp': int((st == 1).sum()), 'ap': ap, 'lamr': lamr})
+        out.append({'name': name, 'height_range': [float(lo), float(hi)], 'classes': classes})
+    return out
+
+
+def subset_lines(subsets):
+    """One log line per subset and class of a 'subsets' result."""
+    return ['subset {:12s} [{:g}, {:g}) class {:3d}: n_gt {:6d}, n_det {:7d}, ignored {:6d} by a region and {:6d} by height, n_tp {:6d}, '
+            'AP {:.4f}, LAMR {:.4f}'.format(e['name'], e['height_range'][0], e['height_range'][1], c['class'], c['n_gt'], c['n_det'],
+                                           c['n_ignored_region'], c['n_ignored_height'], c['n_tp'], c['ap'], c['lamr'])
+            for e in subsets for c in e['classes']]
+
+
 class Evaluator:
     """Evaluator(model_or_layout): a lib_yolo Model, or a dict with row_len, obj_idx, cls_start_idx, cls_cnt and optionally
     unc_cols ({name: column}; default: the variant's table above).  capacity: records the device table holds (28 + 4 per
@@ -146,10 +215,18 @@ class Evaluator:
     geometry of model.det_layers, and for a dict layout with a 'det_layers' entry ([(lh, lw, [(prior_h, prior_w), ...]), ...] or
     DetLayer objects) whose rows carry the ids and variances; off otherwise.  True where it cannot be: ValueError.
     iou_thresholds: the ladder (`ladder_thresholds`: None, 'coco' or 1 .. 16 values); 4 * (1 + K) more bytes per record.  The
-    main table, the loc table and every other key of the result are the same with and without it."""
+    main table, the loc table and every other key of the result are the same with and without it.
+    subsets: the height subsets (`height_subsets`: None, 'ecp_heights' or 1 .. 16 ranges); 4 * (1 + S) more bytes per record, and
+    the result gains 'subsets'.  img_h: the pixel height of the frame the boxes are normalised to (needed with subsets).
+    ignore_thresh: the share of its own area a detection has inside an ignore region to be ignored.  height_slack: an unmatched
+    detection is ignored when its own height is below min_height / height_slack or at least max_height * height_slack.
+    ignore_other_classes: boxes of the other classes are ignore regions too.  A ground-truth label outside [0, cls_cnt) -- the
+    feed's -1 for a record label 0 under implicit_background_class -- is an ignore region of every class.  The shards carry no
+    occlusion tags: a subset is a height range and nothing else.  Everything else is the same with and without subsets."""
 
     def __init__(self, model_or_layout, iou_thresh=0.5, min_score=0.0, capacity=1 << 20, device=None, table=None, loc=None, loc_table=None,
-                 iou_thresholds=None, ladder_table=None):
+                 iou_thresholds=None, ladder_table=None, subsets=None, img_h=None, ignore_thresh=0.5, height_slack=1.25,
+                 ignore_other_classes=False, subsets_table=None):
         import torch
         lay = model_or_layout
         if not isinstance(lay, dict):
@@ -184,6 +261,9 @@ class Evaluator:
         self.iou_thresholds, self.ladder_table = ladder_thresholds(iou_thresholds), None
         if self.iou_thresholds is not None:
             self._setup_ladder(ladder_table)
+        self.subsets, self.subsets_table = height_subsets(subsets), None
+        if self.subsets is not None:
+            self._setup_subsets(img_h, ignore_thresh, height_slack, ignore_other_classes, subsets_table)
 
     def _side_table(self, given, words):
         """A table of `words` int32 words per record: a new one, or the caller's tensor (tests put a guard region behind it)."""
@@ -204,6 +284,33 @@ class Evaluator:
         for k, t in enumerate(thresholds[:_lib.EVAL_LADDER_MAX]):
             cfg.thresholds[k] = float(t)
         return lib.byolo_eval_set_ladder(self._h, ctypes.byref(cfg), ctypes.c_void_p(ptr))
+
+    def _setup_subsets(self, img_h, ignore_thresh, height_slack, ignore_other_classes, subsets_table):
+        import torch
+        if img_h is None or not (np.float32(img_h) > 0 and np.isfinite(np.float32(img_h))):
+            raise ValueError('subsets need img_h, the pixel height of the frame the boxes are normalised to: finite and > 0, not %r' % (img_h,))
+        if not (np.float32(ignore_thresh) >= 0 and np.float32(ignore_thresh) <= 1):
+            raise ValueError('ignore_thresh %r is NaN or outside [0, 1]' % (ignore_thresh,))
+        if not (np.float32(height_slack) >= 1 and np.isfinite(np.float32(height_slack))):
+            raise ValueError('height_slack %r is not finite and >= 1' % (height_slack,))
+        self.img_h, self.ignore_thresh, self.height_slack = float(np.float32(img_h)), float(np.float32(ignore_thresh)), float(np.float32(height_slack))
+        self.ignore_other_classes = bool(ignore_other_classes)
+        S = len(self.subsets)
+        assert lib.byolo_eval_subsets_bytes(self.capacity, S) == 4 * (1 + S) * self.capacity
+        assert lib.byolo_eval_subsets_state_bytes(S, self.cls_cnt) == 4 * S * self.cls_cnt
+        self.subsets_table = self._side_table(subsets_table, 1 + S)
+        self._subsets_counts = torch.zeros(S * self.cls_cnt, dtype=torch.int32, device=self.device)
+        self._check(self._set_subsets([(lo, hi) for _, lo, hi in self.subsets], self.subsets_table.data_ptr(), self._subsets_counts.data_ptr()))
+
+    def _set_subsets(self, ranges, ptr, counts_ptr, struct_bytes=None, **kw):
+        """byolo_eval_set_subsets with this evaluator's parameters (kw: others); returns its code."""
+        cfg = _lib.EvalSubsetsCfg(struct_bytes=ctypes.sizeof(_lib.EvalSubsetsCfg) if struct_bytes is None else struct_bytes, n_subsets=len(ranges),
+                                  img_h=kw.get('img_h', getattr(self, 'img_h', 1.0)), ignore_thresh=kw.get('ignore_thresh', getattr(self, 'ignore_thresh', 0.5)),
+                                  height_slack=kw.get('height_slack', getattr(self, 'height_slack', 1.25)),
+                                  ignore_other_classes=int(kw.get('ignore_other_classes', getattr(self, 'ignore_other_classes', False))))
+        for k, (lo, hi) in enumerate(ranges[:_lib.EVAL_SUBSETS_MAX]):
+            cfg.lo[k], cfg.hi[k] = float(lo), float(hi)
+        return lib.byolo_eval_set_subsets(self._h, ctypes.byref(cfg), ctypes.c_void_p(ptr), ctypes.c_void_p(counts_ptr))
 
     def _setup_loc(self, lay, loc, loc_table):
         """Decides whether the residuals are recorded, and hands the geometry table and the loc table to the library."""
@@ -352,6 +459,15 @@ class Evaluator:
             zk = torch.zeros((K, 1), dtype=torch.int64, device=self.device)
             first = start[:-1][seg]
             lad = torch.stack([lctp - torch.cat([zk, lctp], 1)[:, first], lcfp - torch.cat([zk, lcfp], 1)[:, first]])
+        sub = None
+        if self.subsets_table is not None:                     # the same order again; an ignored record moves neither integer
+            S = len(self.subsets)
+            sw = self.subsets_table.view(-1)[:n * (1 + S)].view(n, 1 + S)[:, 0][order]
+            sst = (sw[None, :] >> (2 * torch.arange(S, device=self.device, dtype=torch.int32))[:, None]) & 3
+            sctp, scfp = torch.cumsum((sst == 1).to(torch.int64), 1), torch.cumsum((sst == 0).to(torch.int64), 1)
+            zs = torch.zeros((S, 1), dtype=torch.int64, device=self.device)
+            first = start[:-1][seg]
+            sub = torch.stack([sst.to(torch.int64), sctp - torch.cat([zs, sctp], 1)[:, first], scfp - torch.cat([zs, scfp], 1)[:, first]])
         host = torch.cat([start.to(torch.float64), ustat.reshape(-1), usum.reshape(-1)]).cpu().numpy()      # the host wait
         two_u_h = two_u.cpu().numpy()
         ints = torch.stack([cum_tp, cum_fp]).cpu().numpy()
@@ -386,6 +502,10 @@ class Evaluator:
             lad_h = lad.cpu().numpy()
             self.sorted['ladder_cum_tp'], self.sorted['ladder_cum_fp'] = lad_h[0], lad_h[1]
             out['ladder'] = ladder_metrics(self.iou_thresholds, lad_h[0], lad_h[1], start_h, [int(v) for v in class_gt], self.n_images)
+        if sub is not None:
+            sub_h = sub.cpu().numpy()
+            self.sorted['subsets_state'], self.sorted['subsets_cum_tp'], self.sorted['subsets_cum_fp'] = sub_h[0].astype(np.int32), sub_h[1], sub_h[2]
+            out['subsets'] = subset_metrics(self.subsets, self.sorted['subsets_state'], sub_h[1], sub_h[2], start_h, self.subsets_counts(), self.n_images)
         return out
 
     # ---- localisation: residuals against predicted variances ---------------------------------------------------------------
@@ -457,10 +577,29 @@ class Evaluator:
         n = int(self._summary()[1].n_records)
         return self._fetch(lib.byolo_eval_ladder_records, np.zeros((n, 1 + len(self.iou_thresholds)), dtype=np.int32), n)
 
+    def subsets_records(self):
+        """The subsets table as an [n, 1 + S] int32 array, one row per record of `records()`: word 0 bits 2s, 2s + 1 = the state
+        in subset s (0 false positive, 1 true positive, 2 ignored by a region, 3 ignored by its height), word 1 + s the box
+        matched there (state 1), the region (state 2) or -1."""
+        if self.subsets_table is None:
+            raise RuntimeError('no height subsets are set for this evaluator')
+        n = int(self._summary()[1].n_records)
+        return self._fetch(lib.byolo_eval_subsets_records, np.zeros((n, 1 + len(self.subsets)), dtype=np.int32), n)
+
+    def subsets_counts(self):
+        """[S][C]: the counted ground-truth boxes per subset and class so far (waits for the stream)."""
+        if self.subsets_table is None:
+            raise RuntimeError('no height subsets are set for this evaluator')
+        S, C = len(self.subsets), self.cls_cnt
+        h = (ctypes.c_int64 * (S * C))()
+        self._check(lib.byolo_eval_subsets_counts(self._h, h, S * C, self._stream()))
+        return [[int(h[s * C + c]) for c in range(C)] for s in range(S)]
+
     def records(self, sorted=False):
         """The record table as a numpy structured array (`record_dtype`): in the order the kernel wrote it, or
         (sorted=True, after finish()) a dict with the table in evaluation order, the cumulative TP / FP integers and the class
-        boundaries."""
+        boundaries; with a ladder 'ladder_cum_tp' / 'ladder_cum_fp' [K, n]; with subsets 'subsets_state', 'subsets_cum_tp' and
+        'subsets_cum_fp' [S, n], where a record whose state is 2 or 3 repeats the integers before it."""
         if sorted:
             if self.sorted is None:
                 raise RuntimeError('records(sorted=True) needs finish() first')

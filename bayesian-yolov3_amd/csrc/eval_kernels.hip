@@ -35,6 +35,12 @@
 // the records go to a third table, 1 + n_thr words each, at the record's own index.  Neither the main table nor the device
 // state is written.
 //
+// eval_subset_kernel (byolo_eval_set_subsets): behind the match kernel on the same stream, one workgroup per image and one wave64
+// per subset of the ground truth by pixel height -- the protocol of the pedestrian benchmarks.  Stages 1 - 4 as the ladder runs
+// them; stage 5 is a pass of its own (ev_subset_pass) in which a detection that finds no counted box may be excused by an ignore
+// region or by its own height.  The 2-bit states of a detection meet in the upper half of its sorted key; the records go to a
+// fourth table, 1 + n_subsets words each, and the counted boxes per (subset, class) to a state buffer of the table's own.
+//
 // eval_loc_kernel (byolo_eval_set_loc): right behind the match kernel on the same stream, one thread per record of the launch.
 // A true positive's box and its matched ground-truth box are taken back to the raw location values t_x, t_y, t_w, t_h at the
 // detection's own cell and prior (the row's layer_id / prior_id columns), in float64, one operation per line as
@@ -298,6 +304,153 @@ __global__ __launch_bounds__(64 * LAD_MAX) void eval_ladder_kernel(const LadderA
     }
 }
 
+// ---- the subsets: the matching per height range of the ground truth, with ignore regions ----------------------------------------
+static constexpr int SUB_MAX = BYOLO_EVAL_SUBSETS_MAX;          // subsets = waves of the workgroup
+
+struct SubsetArgs {
+    EvalArgs e;                                                  // table is not written, state is read only
+    int32_t* sub;                                                // 1 + n_sub words per record
+    int32_t* counts;                                             // n_sub * C: the counted boxes per (subset, class)
+    int32_t n_sub, other;
+    float img_h, ignore_thresh, slack;
+    float lo[SUB_MAX], hi[SUB_MAX];
+};
+
+struct SubsetLds {
+    EvalLds L;
+    float lo[SUB_MAX], hi[SUB_MAX];
+};
+
+// pixel height of a box made by make_box
+__device__ __forceinline__ float ev_height(float y0, float y1, float img_h) { return __fmul_rn(__fsub_rn(y1, y0), img_h); }
+
+// arg-max over the lanes: larger value, then lower index; every lane ends with the result
+__device__ __forceinline__ void ev_argmax(float& bi, int& bg) {
+#pragma unroll
+    for (int sft = 1; sft < 64; sft <<= 1) {
+        const float vi = __shfl_xor(bi, sft);
+        const int vg = __shfl_xor(bg, sft);
+        if (vi > bi || (vi == bi && vg < bg)) { bi = vi; bg = vg; }
+    }
+}
+
+// 5' -- the pass of one wave for the subset [lo, hi): the walk of ev_greedy_pass with two searches per detection.  A box is
+// COUNTED when its label is a class and its height is inside the range; a detection takes the counted, not yet matched box of
+// its class with the largest IoU (state 1 iff that IoU >= thr); failing that it looks for the ignore region -- a box without a
+// class, a box of its class that is not counted, with `other` a box of another class -- that covers most of the detection's own
+// area (state 2 iff inter / det.area >= ignore_thresh; regions are never used up); failing that its own height decides between
+// state 3 (outside [lo / slack, hi * slack)) and 0.  Every detection's lane hands write(d, state, box or region or -1).
+// Adds the counted boxes to counts[0 .. C).
+template <class Write>
+__device__ __forceinline__ void ev_subset_pass(EvalLds& L, const SubsetArgs& sa, const EvalImage& im, float lo_s, float hi_s, int32_t* counts,
+                                               int lane, Write write) {
+    const EvalArgs& a = sa.e;
+    const int G = im.G, ns = im.ns;
+    const int passes = (G + 63) >> 6;                        // <= EV_MAX_GT / 64 = 16 bits of `matched` and `counted`
+    const float dlo = __fdiv_rn(lo_s, sa.slack), dhi = __fmul_rn(hi_s, sa.slack);
+    unsigned int counted = 0;                                // bit p: ground-truth box p * 64 + lane is counted in this subset
+    for (int p = 0; p < passes; ++p) {
+        const int g = (p << 6) + lane;
+        if (g < G && L.label[g] >= 0) {
+            const float h = ev_height(L.y0[g], L.y1[g], sa.img_h);
+            if (h >= lo_s && h < hi_s) {                     // a NaN height fails the first comparison
+                counted |= 1u << p;
+                atomicAdd(&counts[L.label[g]], 1);
+            }
+        }
+    }
+    unsigned int matched = 0;                                // bit p: ground-truth box p * 64 + lane is taken
+    for (int d0 = 0; d0 < ns; d0 += 64) {
+        const int d = d0 + lane;
+        const bool have = d < ns;
+        const unsigned int kw = have ? ev_key_word(L, d, 0) : 0u;
+        const int my_row = (int)(kw >> 8), my_cls = (int)(kw & 255u);
+        const float* r = im.rows + (size_t)my_row * a.D;
+        NBox me = make_box(0.f, 0.f, 0.f, 0.f);
+        if (have) me = make_box(r[0], r[1], r[2], r[3]);
+        int my_state = 0, my_ref = -1;
+        const int nd = min(64, ns - d0);
+        for (int j = 0; j < nd; ++j) {
+            NBox o;
+            o.y0 = __shfl(me.y0, j); o.x0 = __shfl(me.x0, j); o.y1 = __shfl(me.y1, j); o.x1 = __shfl(me.x1, j);
+            o.area = __shfl(me.area, j);
+            const int oc = __shfl(my_cls, j);
+            float bi = -1.f, ri = -1.f;                      // best counted box / best region of this lane's boxes
+            int bg = 0x7fffffff, rg = 0x7fffffff;
+            for (int p = 0; p < passes; ++p) {
+                const int g = (p << 6) + lane;
+                if (g >= G) continue;
+                const int lab = L.label[g];
+                const bool cnt = (counted >> p) & 1u;
+                const bool open = lab == oc && cnt && !((matched >> p) & 1u);
+                const bool region = lab < 0 || (lab == oc ? !cnt : sa.other != 0);
+                if (!open && !region) continue;
+                NBox q; q.y0 = L.y0[g]; q.x0 = L.x0[g]; q.y1 = L.y1[g]; q.x1 = L.x1[g]; q.area = L.ar[g];
+                if (open) {
+                    float v = iou_value(o, q);
+                    if (!(v >= 0.f)) v = 0.f;                // non-finite coordinates: no overlap
+                    if (v > bi) { bi = v; bg = g; }
+                } else {
+                    float v = 0.f;
+                    if (!(o.area <= 0.f || q.area <= 0.f)) {
+                        const float iy0 = smax_(o.y0, q.y0), ix0 = smax_(o.x0, q.x0);
+                        const float iy1 = smin_(o.y1, q.y1), ix1 = smin_(o.x1, q.x1);
+                        const float inter = __fmul_rn(smax_(__fsub_rn(iy1, iy0), 0.f), smax_(__fsub_rn(ix1, ix0), 0.f));
+                        v = __fdiv_rn(inter, o.area);
+                    }
+                    if (!(v >= 0.f && v <= FLT_MAX)) v = 0.f;
+                    if (v > ri) { ri = v; rg = g; }
+                }
+            }
+            // a search succeeds iff some lane's best reaches the threshold, and then the winner is among those lanes: the
+            // arg-max runs only where its result is used.  The branches are uniform: the ballots are the wave's
+            int state = 0, ref = -1;
+            if (__ballot(bg != 0x7fffffff && bi >= a.iou_thresh)) {
+                ev_argmax(bi, bg);
+                state = 1; ref = bg;
+                if ((bg & 63) == lane) matched |= 1u << (bg >> 6);
+            } else {
+                if (__ballot(rg != 0x7fffffff && ri >= sa.ignore_thresh)) {
+                    ev_argmax(ri, rg);
+                    state = 2; ref = rg;
+                } else {
+                    const float h = ev_height(o.y0, o.y1, sa.img_h);
+                    if (h < dlo || h >= dhi) state = 3;      // a NaN height fails both: a false positive
+                }
+            }
+            if (lane == j) { my_state = state; my_ref = ref; }
+        }
+        if (have) write(d, my_state, my_ref);
+    }
+}
+
+__global__ __launch_bounds__(64 * SUB_MAX) void eval_subset_kernel(const SubsetArgs sa) {
+    __shared__ SubsetLds S;
+    EvalLds& L = S.L;
+    const EvalArgs& a = sa.e;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nthreads = 64 * sa.n_sub;
+    if (tid < sa.n_sub) { S.lo[tid] = sa.lo[tid]; S.hi[tid] = sa.hi[tid]; }
+    const EvalImage im = ev_stage_and_sort<false>(L, a, blockIdx.x, tid, nthreads);
+    // the score half of a key has done its work: it collects the detection's 2-bit states
+    for (int d = tid; d < im.ns; d += nthreads) ev_key_word(L, d, 1) = 0u;
+    __syncthreads();
+
+    // 6 -- this wave's subset: its state, and the box or region behind it
+    const int rec_words = 1 + sa.n_sub;
+    ev_subset_pass(L, sa, im, S.lo[wave], S.hi[wave], sa.counts + (size_t)wave * a.C, lane, [&](int d, int state, int ref) {
+        const long long pos = im.base + d;
+        if (state) atomicOr(&ev_key_word(L, d, 1), (unsigned int)state << (2 * wave));     // LDS
+        if (pos < a.capacity) sa.sub[(size_t)pos * rec_words + 1 + wave] = ref;
+    });
+    __syncthreads();
+    // word 0: the states of every subset
+    for (int d = tid; d < im.ns; d += nthreads) {
+        const long long pos = im.base + d;
+        if (pos < a.capacity) sa.sub[(size_t)pos * rec_words] = (int32_t)ev_key_word(L, d, 1);
+    }
+}
+
 // ---- localisation residuals --------------------------------------------------------------------------------------------------
 static constexpr int LOC_WORDS = BYOLO_EVAL_LOC_WORDS;
 static constexpr int LOC_L = BYOLO_EVAL_LOC_MAX_LAYERS, LOC_P = BYOLO_EVAL_LOC_MAX_PRIORS;
@@ -403,6 +556,9 @@ struct byolo_eval {
     int32_t* d_loc = nullptr;
     byolo_eval_ladder_cfg ladder;                               // valid while d_ladder is set (byolo_eval_set_ladder)
     int32_t* d_ladder = nullptr;
+    byolo_eval_subsets_cfg subsets;                             // valid while d_subsets is set (byolo_eval_set_subsets)
+    int32_t* d_subsets = nullptr;
+    int32_t* d_subset_counts = nullptr;
     std::string err;
 };
 
@@ -456,6 +612,9 @@ extern "C" int32_t byolo_eval_destroy(byolo_eval_t* ev) { delete ev; return BYOL
 extern "C" int32_t byolo_eval_reset(byolo_eval_t* ev, void* stream) {
     if (!ev) return efail(nullptr, BYOLO_ERR_ARG, "byolo_eval_reset: null handle");
     EVHIP(ev, hipMemsetAsync(ev->d_state, 0, sizeof(int32_t) * (size_t)state_words(ev->cfg.cls_cnt), static_cast<hipStream_t>(stream)));
+    if (ev->d_subsets)
+        EVHIP(ev, hipMemsetAsync(ev->d_subset_counts, 0, sizeof(int32_t) * (size_t)ev->subsets.n_subsets * (size_t)ev->cfg.cls_cnt,
+                                 static_cast<hipStream_t>(stream)));
     ev->launches = 0;
     ev->images = 0;
     return BYOLO_OK;
@@ -503,6 +662,22 @@ extern "C" int32_t byolo_eval_add(byolo_eval_t* ev, const float* d_rows, int32_t
         hipLaunchKernelGGL(byk::eval_ladder_kernel, dim3(B), dim3(64 * la.n_thr), 0, static_cast<hipStream_t>(stream), la);
         EVHIP(ev, hipGetLastError());
     }
+    if (ev->d_subsets) {                                        // likewise; the main table and the state are only read
+        byk::SubsetArgs sa;
+        sa.e = a;
+        sa.e.table = nullptr;
+        sa.sub = ev->d_subsets;
+        sa.counts = ev->d_subset_counts;
+        sa.n_sub = ev->subsets.n_subsets;
+        sa.other = ev->subsets.ignore_other_classes ? 1 : 0;
+        sa.img_h = ev->subsets.img_h; sa.ignore_thresh = ev->subsets.ignore_thresh; sa.slack = ev->subsets.height_slack;
+        for (int k = 0; k < byk::SUB_MAX; ++k) {
+            sa.lo[k] = k < sa.n_sub ? ev->subsets.lo[k] : 0.f;
+            sa.hi[k] = k < sa.n_sub ? ev->subsets.hi[k] : 0.f;
+        }
+        hipLaunchKernelGGL(byk::eval_subset_kernel, dim3(B), dim3(64 * sa.n_sub), 0, static_cast<hipStream_t>(stream), sa);
+        EVHIP(ev, hipGetLastError());
+    }
     ev->launches += 1;
     ev->images += B;
     return BYOLO_OK;
@@ -531,7 +706,7 @@ extern "C" int32_t byolo_eval_finish(byolo_eval_t* ev, byolo_eval_summary* out, 
     return BYOLO_OK;
 }
 
-// byolo_eval_records / _loc_records / _ladder_records (fn): n_records records of `words` words from `first` of d_table on
+// byolo_eval_records / _loc_records / _ladder_records / _subsets_records (fn): n_records records of `words` words from `first` of d_table on
 static int32_t fetch_records(byolo_eval_t* ev, const char* fn, const int32_t* d_table, size_t words, int64_t first, int64_t n_records,
                              int32_t* h_dst, void* stream) {
     if (first < 0 || n_records < 0 || first + n_records > ev->capacity) return efail(ev, BYOLO_ERR_ARG, "%s: records outside the table", fn);
@@ -548,7 +723,7 @@ extern "C" int32_t byolo_eval_records(byolo_eval_t* ev, int32_t* h_dst, int64_t 
     return fetch_records(ev, "byolo_eval_records", ev->d_table, (size_t)record_words(ev->cfg), first, n_records, h_dst, stream);
 }
 
-// byolo_eval_set_loc / _set_ladder (fn): everything around the checks of the cfg's own fields (`fields`: BYOLO_OK, or it has
+// byolo_eval_set_loc / _set_ladder / _set_subsets (fn): everything around the checks of the cfg's own fields (`fields`: BYOLO_OK, or it has
 // failed).  A NULL table switches the side table off
 template <class Cfg, class Fields>
 static int32_t set_side_table(byolo_eval_t* ev, const char* fn, const Cfg* cfg, const char* cfg_name, void* d_table, const char* table_name,
@@ -616,4 +791,52 @@ extern "C" int32_t byolo_eval_ladder_records(byolo_eval_t* ev, int32_t* h_dst, i
     if (!ev) return efail(nullptr, BYOLO_ERR_ARG, "byolo_eval_ladder_records: null handle");
     if (!ev->d_ladder) return efail(ev, BYOLO_ERR_STATE, "byolo_eval_ladder_records: no ladder table is set (byolo_eval_set_ladder)");
     return fetch_records(ev, "byolo_eval_ladder_records", ev->d_ladder, (size_t)(1 + ev->ladder.n_thr), first, n_records, h_dst, stream);
+}
+
+// ---- the subsets -------------------------------------------------------------------------------------------------------------
+extern "C" size_t byolo_eval_subsets_bytes(int64_t capacity, int32_t n_subsets) {
+    if (capacity < 1 || capacity > 0x7fffffffll || n_subsets < 1 || n_subsets > BYOLO_EVAL_SUBSETS_MAX) return 0;
+    return sizeof(int32_t) * (size_t)(1 + n_subsets) * (size_t)capacity;
+}
+
+extern "C" size_t byolo_eval_subsets_state_bytes(int32_t n_subsets, int32_t cls_cnt) {
+    if (n_subsets < 1 || n_subsets > BYOLO_EVAL_SUBSETS_MAX || cls_cnt < 1 || cls_cnt > BYOLO_NMS_MAX_CLASSES) return 0;
+    return sizeof(int32_t) * (size_t)n_subsets * (size_t)cls_cnt;
+}
+
+extern "C" int32_t byolo_eval_set_subsets(byolo_eval_t* ev, const byolo_eval_subsets_cfg* cfg, void* d_subsets_table, void* d_subsets_counts) {
+    const char* fn = "byolo_eval_set_subsets";
+    return set_side_table(ev, fn, cfg, "byolo_eval_subsets_cfg", d_subsets_table, "d_subsets_table", &byolo_eval::subsets, &byolo_eval::d_subsets, [&]() -> int32_t {
+        if (cfg->n_subsets < 1 || cfg->n_subsets > BYOLO_EVAL_SUBSETS_MAX) return efail(ev, BYOLO_ERR_ARG, "%s: n_subsets outside 1 .. %d", fn, BYOLO_EVAL_SUBSETS_MAX);
+        for (int k = 0; k < cfg->n_subsets; ++k)
+            if (!(cfg->lo[k] >= 0.f && cfg->lo[k] < cfg->hi[k]))                 // NaN fails both
+                return efail(ev, BYOLO_ERR_ARG, "%s: height range %d is NaN, negative or inverted", fn, k);
+        if (!(cfg->img_h > 0.f && cfg->img_h <= 3.402823466e38f)) return efail(ev, BYOLO_ERR_ARG, "%s: img_h is not finite and > 0", fn);
+        if (!(cfg->ignore_thresh >= 0.f && cfg->ignore_thresh <= 1.f)) return efail(ev, BYOLO_ERR_ARG, "%s: ignore_thresh is NaN or outside [0, 1]", fn);
+        if (!(cfg->height_slack >= 1.f && cfg->height_slack <= 3.402823466e38f)) return efail(ev, BYOLO_ERR_ARG, "%s: height_slack is not finite and >= 1", fn);
+        if (!d_subsets_counts) return efail(ev, BYOLO_ERR_ARG, "%s: null d_subsets_counts", fn);
+        if (reinterpret_cast<uintptr_t>(d_subsets_counts) & 3) return efail(ev, BYOLO_ERR_ARG, "%s: d_subsets_counts must be 4-byte aligned", fn);
+        if (reinterpret_cast<uintptr_t>(d_subsets_table) & 3) return efail(ev, BYOLO_ERR_ARG, "%s: d_subsets_table must be 4-byte aligned", fn);
+        ev->d_subset_counts = static_cast<int32_t*>(d_subsets_counts);       // the last check: nothing fails behind it
+        return BYOLO_OK;
+    });
+}
+
+extern "C" int32_t byolo_eval_subsets_records(byolo_eval_t* ev, int32_t* h_dst, int64_t first, int64_t n_records, void* stream) {
+    if (!ev) return efail(nullptr, BYOLO_ERR_ARG, "byolo_eval_subsets_records: null handle");
+    if (!ev->d_subsets) return efail(ev, BYOLO_ERR_STATE, "byolo_eval_subsets_records: no subsets table is set (byolo_eval_set_subsets)");
+    return fetch_records(ev, "byolo_eval_subsets_records", ev->d_subsets, (size_t)(1 + ev->subsets.n_subsets), first, n_records, h_dst, stream);
+}
+
+extern "C" int32_t byolo_eval_subsets_counts(byolo_eval_t* ev, int64_t* h_counts, int32_t n_counts, void* stream) {
+    if (!ev) return efail(nullptr, BYOLO_ERR_ARG, "byolo_eval_subsets_counts: null handle");
+    if (!ev->d_subsets) return efail(ev, BYOLO_ERR_STATE, "byolo_eval_subsets_counts: no subsets table is set (byolo_eval_set_subsets)");
+    const int n = ev->subsets.n_subsets * ev->cfg.cls_cnt;
+    if (!h_counts || n_counts != n) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_subsets_counts: h_counts has %d entries, the evaluator %d subsets x %d classes", n_counts, ev->subsets.n_subsets, ev->cfg.cls_cnt);
+    int32_t st[BYOLO_EVAL_SUBSETS_MAX * BYOLO_NMS_MAX_CLASSES];
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    EVHIP(ev, hipMemcpyAsync(st, ev->d_subset_counts, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
+    EVHIP(ev, hipStreamSynchronize(s));
+    for (int k = 0; k < n; ++k) h_counts[k] = st[k];
+    return BYOLO_OK;
 }

@@ -35,6 +35,16 @@ voting off; every entry gets its own `Engine.box_vote` call on that batch's rows
 'box_vote_sweep': [{'settings': ..., **result}, ...] and a table of mean AP per entry is logged -- the tool for choosing `sigma_t`
 and `var_floor`.
 
+`eval_subsets` ('ecp_heights', or a list of 1 .. 16 dicts {'name', 'min_height', 'max_height'} in pixels; absent: off, metrics.json
+is what it was): every batch is also matched once per height subset of the ground truth under the ignore rule of the pedestrian
+benchmarks (INTEGRATION.md "Evaluation"; one more kernel per batch), and every result dict -- the NMS rows', the voted rows', the
+soft-NMS rows', every sweep entry's -- gains 'subsets': per subset and class n_gt, the detections that count, those ignored by a
+region and by their height, AP and LAMR.  A box whose record label is 0 (`ignore`; the feed hands it on as label -1 under
+`implicit_background_class`) is an ignore region of every class.  `eval_ignore_thresh` (0.5), `eval_height_slack` (1.25) and
+`eval_ignore_other_classes` (False) are the rule's parameters; the pixel height is that of the frame the 'eval' split normalises
+the boxes to (`crop_img_size[0]` when `crop`, else `full_img_size[0]`).  The shards carry no occlusion tags: 'ecp_heights' is the
+height half of the EuroCity Persons subsets reasonable [40, inf), small [30, 60) and all [20, inf).
+
 `Model.run` -> `Evaluator.add` per batch (byolo/evaluate.py: one matching kernel per batch on the forward's stream); batches
 run one after the other (`Model.run` re-runs a batch that leaves the split-f16 range in fp32 by itself).  One process, one
 GPU: multi-GPU evaluation is out of scope.  Writes `<out_path>_<step>/metrics.json`: the dict of `Evaluator.finish`, the
@@ -105,8 +115,26 @@ def check_config(config, model='bayesian'):
                 raise ValueError(str(e))
             if not cfg['soft_nms_compare']:                          # the model runs the soft-NMS itself; the comparison runs it beside the hard one
                 cfg['engine_options'] = dict(cfg.get('engine_options', {}), soft_nms=soft)
-    from byolo.evaluate import ladder_thresholds
+    from byolo.evaluate import height_subsets, ladder_thresholds
     ladder_thresholds(cfg.get('iou_thresholds'))                     # ValueError on a bad ladder; both keys stay absent when absent
+    height_subsets(cfg.get('eval_subsets'))                          # likewise; the rule's parameters stay absent without subsets
+    given = [k for k in ('eval_ignore_thresh', 'eval_height_slack', 'eval_ignore_other_classes') if k in cfg]
+    if cfg.get('eval_subsets') is None:
+        if given:
+            raise ValueError('{} need eval_subsets'.format(given))
+    else:
+        cfg.setdefault('eval_ignore_thresh', 0.5)
+        cfg.setdefault('eval_height_slack', 1.25)
+        cfg.setdefault('eval_ignore_other_classes', False)
+        for name in ('eval_ignore_thresh', 'eval_height_slack'):
+            if isinstance(cfg[name], bool) or not isinstance(cfg[name], (int, float)):
+                raise ValueError('{} must be a number, not {!r}'.format(name, cfg[name]))
+        if not 0.0 <= cfg['eval_ignore_thresh'] <= 1.0:
+            raise ValueError('eval_ignore_thresh outside [0, 1]')
+        if not 1.0 <= cfg['eval_height_slack'] < float('inf'):
+            raise ValueError('eval_height_slack must be finite and at least 1')
+        if cfg['eval_ignore_other_classes'] not in (True, False):
+            raise ValueError('eval_ignore_other_classes is True or False')
     if cfg.get('box_vote_sweep') is not None:
         sweep = cfg['box_vote_sweep']
         if not cfg['box_vote_compare']:
@@ -242,6 +270,16 @@ def sweep_lines(sweep, results, iou_thresh):
     return lines
 
 
+def subset_options(cfg):
+    """The Evaluator arguments of the config's eval_subsets keys ({} without them).  img_h: the frame the 'eval' split of the
+    feed normalises the boxes to."""
+    if cfg.get('eval_subsets') is None:
+        return {}
+    return dict(subsets=cfg['eval_subsets'], img_h=(cfg['crop_img_size'] if cfg['crop'] else cfg['full_img_size'])[0],
+                ignore_thresh=cfg.get('eval_ignore_thresh', 0.5), height_slack=cfg.get('eval_height_slack', 1.25),
+                ignore_other_classes=cfg.get('eval_ignore_other_classes', False))
+
+
 def evaluate(config, model='bayesian'):
     """Scores the checkpoint and writes <out_path>_<step>/metrics.json; returns its content."""
     from byolo import inference as _inf
@@ -255,7 +293,7 @@ def evaluate(config, model='bayesian'):
     out_path = '{}_{}'.format(cfg['out_path'], _inf.step_of(checkpoint))
     os.makedirs(out_path)                                 # like the inference scripts: refuses to overwrite an existing run
     new_ev = lambda: Evaluator(m, iou_thresh=cfg['iou_thresh'], min_score=cfg['min_score'], capacity=cfg['eval_capacity'], loc=cfg['localisation'],
-                               iou_thresholds=cfg.get('iou_thresholds'))
+                               iou_thresholds=cfg.get('iou_thresholds'), **subset_options(cfg))
     ev = new_ev()
     ev_vote = new_ev() if cfg['box_vote_compare'] else None
     sweep = [(settings, new_ev()) for settings in (cfg.get('box_vote_sweep') or [])]
@@ -297,6 +335,10 @@ def evaluate(config, model='bayesian'):
         other = voted_metrics if voted_metrics is not None else soft_metrics
         for line in ladder_lines(metrics['ladder'], other['ladder'] if other is not None else None,
                                  names=('NMS rows', 'voted rows' if soft_metrics is None else 'soft-NMS rows')):
+            logging.info(line)
+    if 'subsets' in metrics:
+        from byolo.evaluate import subset_lines
+        for line in subset_lines(metrics['subsets']):
             logging.info(line)
     for line in sweep_lines(cfg.get('box_vote_sweep') or [], sweep_metrics, cfg['iou_thresh']):
         logging.info(line)
@@ -342,6 +384,7 @@ def main(argv=None):
         'implicit_background_class': True,
         'iou_thresh': 0.5,
         'min_score': 0.0,
+        # 'eval_subsets': 'ecp_heights',  # LAMR / AP per height subset with ignore regions, as the pedestrian benchmarks score
         'data': {
             'path': '$HOME/data/ecp/tfrecords',  # edit
             'file_pattern': 'ecp-day-val-*-of-*',  # edit: LABELLED shards

@@ -194,6 +194,13 @@ def run(model_cls, config):
     return start(model_cls, config)
 
 
+def evsub_line(step, subsets):
+    """The hook's log line for the 'subsets' part of a result (byolo/evaluate.py): every subset and class in order."""
+    return '{:5d} evsub >>> '.format(step) + '; '.join(
+        '{} class {}: LAMR {:.4f}, AP {:.4f}, n_gt {}'.format(e['name'], c['class'], c['lamr'], c['ap'], c['n_gt'])
+        for e in subsets for c in e['classes'])
+
+
 class EvalHook:
     """config['eval_interval'] (absent: no hook, the run is what it was): every that many steps the trained heads are handed
     to an inference model (built once, at the evaluation size: the centre crop when config['crop'], else the full frame) and
@@ -201,7 +208,9 @@ class EvalHook:
     (byolo/evaluate.py).  Logs '{step} eval  >>> class c: LAMR .., AP ..; ...' and, for the models whose rows carry
     variances, '{step} evloc >>> ale x: rmse .., sigma_scale .., nll ..; ...'.  config['eval_iou_thresholds'] (absent: off;
     'coco' or a list, as byolo.evaluate.Evaluator's iou_thresholds) adds '{step} evlad >>> class c: AP@0.50 .., ..., mean ..'.
-    Reads the trainer, never writes it; the
+    config['eval_subsets'] (absent: off; 'ecp_heights' or a list, as byolo.evaluate.Evaluator's subsets, with the optional
+    'eval_ignore_thresh', 'eval_height_slack' and 'eval_ignore_other_classes') adds
+    '{step} evsub >>> reasonable class 0: LAMR .., AP .., n_gt ..; ...' (`evsub_line`).  Reads the trainer, never writes it; the
     'eval' split draws no random number, so the training and validation streams are what they are without the hook."""
 
     def __init__(self, model_cls, config):
@@ -228,7 +237,12 @@ class EvalHook:
         if self.model is None:
             self._build()
         trainer.apply_to(self.model)
-        ev = Evaluator(self.model, capacity=int(self.config.get('eval_capacity', 1 << 18)), iou_thresholds=self.config.get('eval_iou_thresholds'))
+        cfg = self.config
+        sub = {} if cfg.get('eval_subsets') is None else dict(
+            subsets=cfg['eval_subsets'], img_h=(cfg['crop_img_size'] if cfg['crop'] else cfg['full_img_size'])[0],
+            ignore_thresh=cfg.get('eval_ignore_thresh', 0.5), height_slack=cfg.get('eval_height_slack', 1.25),
+            ignore_other_classes=cfg.get('eval_ignore_other_classes', False))
+        ev = Evaluator(self.model, capacity=int(cfg.get('eval_capacity', 1 << 18)), iou_thresholds=cfg.get('eval_iou_thresholds'), **sub)
         feed = dataset_utils._Feed(self.config, 'val', 'eval', device=self.model.engine.torch_device)
         try:
             for k, b in enumerate(feed):
@@ -252,6 +266,8 @@ class EvalHook:
             logging.info('{:5d} evlad >>> '.format(step) + '; '.join(
                 'class {}: '.format(c['class']) + ', '.join('AP@{:.2f} {:.4f}'.format(t, a) for t, a in zip(lad['iou_thresholds'], c['ap'])) +
                 ', mean {:.4f}'.format(c['ap_mean']) for c in lad['classes']) + '; mean AP {:.4f}'.format(lad['ap_mean']))
+        if 'subsets' in self.last:
+            logging.info(evsub_line(step, self.last['subsets']))
         return self.last
 
     def close(self):

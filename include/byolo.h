@@ -683,6 +683,46 @@ BYOLO_API size_t byolo_eval_ladder_bytes(int64_t capacity, int32_t n_thr);
 BYOLO_API int32_t byolo_eval_set_ladder(byolo_eval_t* ev, const byolo_eval_ladder_cfg* cfg, void* d_ladder_table);
 BYOLO_API int32_t byolo_eval_ladder_records(byolo_eval_t* ev, int32_t* h_dst, int64_t first, int64_t n_records, void* stream);
 
+/* The subsets: the matching per height range of the ground truth with ignore regions -- the protocol in which the pedestrian
+ * benchmarks (EuroCity Persons, CityPersons, Caltech) publish LAMR; INTEGRATION.md "Evaluation" has the rule in full and
+ * tests/_eval_subsets_ref.py restates it.  With a subsets table set, byolo_eval_add launches one more kernel behind the matching
+ * on the same stream (no host wait) that matches every image of the batch once per subset s = [lo[s], hi[s]) of pixel heights
+ * h = (ymax - ymin) * img_h (two float32 operations on the box as the matcher orders it):
+ *   counted box    its label is a class and lo[s] <= h < hi[s]; only counted boxes can be matched, and only they are counted
+ *   ignore region  for a detection of class c: every box whose label is outside [0, cls_cnt), every box of class c that is not
+ *                  counted and, with ignore_other_classes, every box of another class.  Regions are never used up
+ *   state          same survivors and visiting order as the main matching.  1: the counted, not yet matched box of the
+ *                  detection's class with the largest IoU (ties: lower index) has IoU >= iou_thresh; the box is marked.
+ *                  Else 2: the region with the largest inter / area(detection) (float32; 0 when either area is <= 0 or the
+ *                  value is not finite; ties: lower index) reaches ignore_thresh.  Else 3: the detection's own height is
+ *                  < lo[s] / height_slack or >= hi[s] * height_slack.  Else 0: a false positive.  States 2 and 3 are neither
+ *                  true nor false positives
+ *   record         at the record's index, 1 + n_subsets 32-bit words: word 0 holds the state of subset s at bits 2s, 2s + 1;
+ *                  word 1 + s the matched box (state 1), the region (state 2), or -1
+ *   counters       d_subsets_counts: n_subsets * cls_cnt int32, the counted boxes per (subset, class), subset-major
+ * d_subsets_table holds byolo_eval_subsets_bytes(capacity, n_subsets) bytes and d_subsets_counts
+ * byolo_eval_subsets_state_bytes(n_subsets, cls_cnt) bytes, both caller-owned and 4-byte aligned; byolo_eval_reset zeroes the
+ * counters while they are set, so hand them over zeroed or reset afterwards.  A NULL table switches the subsets off.  Nothing
+ * is written at or beyond `capacity` records.  byolo_eval_set_subsets is refused with BYOLO_ERR_STATE between the first
+ * byolo_eval_add and the next byolo_eval_reset, and with BYOLO_ERR_ARG for a wrong struct_bytes, n_subsets outside
+ * 1 .. BYOLO_EVAL_SUBSETS_MAX, a range that is NaN, negative or not lo < hi (hi may be +inf), img_h not finite and > 0,
+ * ignore_thresh outside [0, 1], height_slack not finite and >= 1, NULL counters and a misaligned pointer.  The main records, the
+ * device state, the other side tables and -- with no subsets set -- the launches are the same with and without it. */
+#define BYOLO_EVAL_SUBSETS_MAX 16
+typedef struct byolo_eval_subsets_cfg {
+    int32_t struct_bytes;          /* sizeof(byolo_eval_subsets_cfg) of the caller's header: a mismatch is BYOLO_ERR_ARG */
+    int32_t n_subsets;
+    float lo[BYOLO_EVAL_SUBSETS_MAX];
+    float hi[BYOLO_EVAL_SUBSETS_MAX];
+    float img_h, ignore_thresh, height_slack;
+    int32_t ignore_other_classes;
+} byolo_eval_subsets_cfg;
+BYOLO_API size_t byolo_eval_subsets_bytes(int64_t capacity, int32_t n_subsets);
+BYOLO_API size_t byolo_eval_subsets_state_bytes(int32_t n_subsets, int32_t cls_cnt);
+BYOLO_API int32_t byolo_eval_set_subsets(byolo_eval_t* ev, const byolo_eval_subsets_cfg* cfg, void* d_subsets_table, void* d_subsets_counts);
+BYOLO_API int32_t byolo_eval_subsets_records(byolo_eval_t* ev, int32_t* h_dst, int64_t first, int64_t n_records, void* stream);
+BYOLO_API int32_t byolo_eval_subsets_counts(byolo_eval_t* ev, int64_t* h_counts, int32_t n_counts, void* stream);
+
 /* ---- variance voting (He et al., CVPR 2019; no counterpart in the reference; csrc/box_vote.hip; INTEGRATION.md "Variance voting"
  * has the definition in full, tests/_box_vote_ref.py restates it) -------------------------------------------------------------
  * After the NMS every kept row's box is replaced by the weighted mean of the pre-NMS boxes of its class that overlap it:
