@@ -106,6 +106,19 @@ class SoftNmsCfg(ctypes.Structure):
                [(n, ctypes.c_float) for n in ("sigma", "iou_soft", "iou_hard", "min_score")]
 
 
+VAR_RECAL_ALE, VAR_RECAL_EPI, VAR_RECAL_TOTAL = 1, 2, 3              # BYOLO_VAR_RECAL_* (target)
+VAR_RECAL_SCALE, VAR_RECAL_POWER = 0, 1                             # (method)
+VAR_RECAL_FITTED, VAR_RECAL_SCALE_FALLBACK, VAR_RECAL_IDENTITY, VAR_RECAL_EMPTY = 0, 1, 2, 3      # (status of a fitted segment)
+VAR_RECAL_TABLE_BYTES, VAR_RECAL_FIT_WORDS = 8192, 10
+
+
+class VarRecalCfg(ctypes.Structure):
+    """include/byolo.h byolo_var_recal_cfg (field for field; tests/test_var_recal_cpu.py compares the two)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("struct_bytes", "kind", "target", "n_layers")] + \
+               [("n_priors", ctypes.c_int32 * EVAL_LOC_MAX_LAYERS)] + \
+               [(n, ((ctypes.c_double * 4) * EVAL_LOC_MAX_PRIORS) * EVAL_LOC_MAX_LAYERS) for n in ("a", "b")]
+
+
 _i32, _i64, _f32 = ctypes.c_int32, ctypes.c_int64, ctypes.c_float
 _vp, _cp, _sz, _u64 = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint64
 _P = ctypes.POINTER
@@ -221,6 +234,11 @@ PROTOTYPES = {
     "byolo_soft_nms_workspace_bytes": (_sz, [_i32, _i64, _i32, _i32]),
     "byolo_soft_nms": (_i32, [_vp, _vp, _i32, _i64, _i32, _i32, _i32, _i32, _i32, _P(SoftNmsCfg), _vp, _sz, _vp, _vp, _vp, _vp]),
     "byolo_set_soft_nms": (_i32, [_vp, _P(SoftNmsCfg)]),
+    "byolo_var_recal_table": (_i32, [_P(VarRecalCfg), _vp]),
+    "byolo_var_recal_apply": (_i32, [_P(VarRecalCfg), _vp, _i64, _i32, _vp, _vp, _vp]),
+    "byolo_set_var_recal": (_i32, [_vp, _P(VarRecalCfg)]),
+    "byolo_var_recal_fit_workspace_bytes": (_sz, [_i64]),
+    "byolo_var_recal_fit": (_i32, [_vp, _vp, _vp, _i32, _i64, _i32, _vp, _vp, _sz, _vp]),
 }
 
 

@@ -39,6 +39,8 @@ class Engine:
         self._trainers = weakref.WeakSet()       # byolo.train.HeadTrainer objects bound to this handle (closed before it)
         self._box_vote = None            # the settings set_box_vote() switched variance voting on with (None: off)
         self._soft_nms = None            # the settings set_soft_nms() switched the soft-NMS on with (None: off, the hard NMS)
+        self._var_recal = None           # the VarCalibration set_var_recal() switched variance recalibration on with (None: off)
+        self._var_recal_table = None     # var_recal(): (packed table bytes, device, its copy on that device) of the last call
 
     # ---- arithmetic of the convolution stack (include/byolo.h: BYOLO_PREC_*) ----------------------------
     @property
@@ -170,6 +172,8 @@ class Engine:
             t.set_box_vote(self._box_vote)
         if self._soft_nms is not None:
             t.set_soft_nms(self._soft_nms)
+        if self._var_recal is not None:
+            t.set_var_recal(self._var_recal)
         t.set_params(self.get_params())
         t.finalize()
         return t
@@ -514,6 +518,60 @@ class Engine:
                                           ctypes.byref(loc) if loc is not None else None, p(rows_in), p(kept), p(count), cap, p(rows),
                                           p(vote_n), p(ws), wsb, ctypes.c_void_p(stream)))
         return dict(rows=rows, vote_n=vote_n)
+
+    # ---- variance recalibration (include/byolo.h "variance recalibration"; byolo/recalibrate.py) ----------------
+    _VARIANT_OF_KIND = {_lib.DET_STANDARD: "yolov3", _lib.DET_ALEATORIC: "yolov3_aleatoric", _lib.DET_EPISTEMIC: "bayesian_yolov3_aleatoric"}
+
+    def set_var_recal(self, cal=None):
+        """Variance recalibration inside forward(): a byolo.recalibrate.VarCalibration, the path of a saved one or its dict switches
+        it on -- the table is applied in place on the pre-NMS rows right behind the decode, so 'boxes', 'rows', the soft-NMS and
+        variance voting see calibrated variances; 'kept' and 'count' do not change --, None / False switches it off (the default;
+        forward() is then what it was).  ValueError naming the field when the calibration was fitted for another variant or
+        geometry.  A twin made before the call follows it."""
+        from .recalibrate import VarCalibration
+        if cal is None or cal is False:
+            check(self._h, lib.byolo_set_var_recal(self._h, None))
+            self._var_recal = None
+        else:
+            cal = VarCalibration.coerce(cal)
+            dets = [a for n, a in self._graph if n == "add_detection"]
+            if not dets:
+                raise ValueError("set_var_recal: add the detection layers first")
+            cal.check(self._VARIANT_OF_KIND[int(dets[-1][1])], [len(a[2]) for a in dets])
+            cfg = cal.cfg()
+            check(self._h, lib.byolo_set_var_recal(self._h, ctypes.byref(cfg)))
+            self._var_recal = cal
+        if self._twin is not None:
+            self._twin.set_var_recal(self._var_recal)
+
+    def var_recal(self, rows, cal):
+        """The recalibration stage by itself (byolo_var_recal_apply) on rows [..., D] of this engine's class count -- pre-NMS boxes
+        or kept rows alike: returns a calibrated copy, `rows` is not touched.  The table is copied to the device when it differs from
+        the last call's (a copy torch waits for); calls with the same table copy nothing and wait for nothing."""
+        torch = _torch()
+        from .recalibrate import VarCalibration
+        cal = VarCalibration.coerce(cal)
+        assert rows.is_cuda and rows.dtype == torch.float32 and rows.is_contiguous() and rows.dim() >= 1
+        D = int(rows.shape[-1])
+        want = {"yolov3_aleatoric": 14, "bayesian_yolov3_aleatoric": 21}[cal.variant] + self.cfg.cls_cnt
+        if D != want:
+            raise ValueError("var_recal: variant: rows of %d columns, %s rows with %d classes have %d" % (D, cal.variant, self.cfg.cls_cnt, want))
+        out = torch.empty_like(rows)
+        n = rows.numel() // D
+        if n == 0:
+            return out
+        cfg = cal.cfg()
+        host = np.empty(_lib.VAR_RECAL_TABLE_BYTES // 8, dtype=np.float64)
+        check(None, lib.byolo_var_recal_table(ctypes.byref(cfg), ctypes.c_void_p(host.ctypes.data)))
+        key = host.tobytes()
+        if self._var_recal_table is None or self._var_recal_table[0] != key or self._var_recal_table[1] != rows.device:
+            self._var_recal_table = (key, rows.device, torch.from_numpy(host).to(rows.device))      # (pageable memory: the copy is complete on return)
+        tab = self._var_recal_table[2]
+        stream = torch.cuda.current_stream(rows.device).cuda_stream
+        rc = lib.byolo_var_recal_apply(ctypes.byref(cfg), ctypes.c_void_p(rows.data_ptr()), n, D, ctypes.c_void_p(out.data_ptr()),
+                                       ctypes.c_void_p(tab.data_ptr()), ctypes.c_void_p(stream))
+        check(None, rc)
+        return out
 
     # ---- soft-NMS (include/byolo.h "soft-NMS"; INTEGRATION.md "Soft-NMS") -----------------------------------------
     SOFT_METHODS = {"linear": _lib.SOFT_NMS_LINEAR, "gaussian": _lib.SOFT_NMS_GAUSSIAN}

@@ -256,7 +256,7 @@ class Evaluator:
                                           ctypes.c_void_p(self._state.data_ptr()), ctypes.byref(self._h)), handle=False)
         self.sorted = None
         self.reset()
-        self.loc_table = None
+        self.loc_table, self.loc_geometry = None, None
         self._setup_loc(lay, loc, loc_table)
         self.iou_thresholds, self.ladder_table = ladder_thresholds(iou_thresholds), None
         if self.iou_thresholds is not None:
@@ -337,7 +337,8 @@ class Evaluator:
             return
         if why is not None:
             raise ValueError('loc=True: ' + why)
-        cfg = eval_loc.loc_cfg(ids[0], ids[1], eval_loc.geometry(lay['det_layers']))
+        self.loc_geometry = eval_loc.geometry(lay['det_layers'])          # byolo/recalibrate.py fits per layer and prior of this table
+        cfg = eval_loc.loc_cfg(ids[0], ids[1], self.loc_geometry)
         assert lib.byolo_eval_loc_bytes(self.capacity) == 4 * _lib.EVAL_LOC_WORDS * self.capacity
         self.loc_table = self._side_table(loc_table, _lib.EVAL_LOC_WORDS)
         self._check(lib.byolo_eval_set_loc(self._h, ctypes.byref(cfg), ctypes.c_void_p(self.loc_table.data_ptr())))

@@ -437,6 +437,9 @@ class InferenceLoop:
             if flags[0] or flags[1]:
                 return None, flags
             rows = eng.finish_tshard(buf[:N * D].view(1, N, D), T)
+            recal = getattr(eng, '_var_recal', None)
+            if recal is not None:                          # engine_options['var_recal']: what byolo_forward does behind its own decode
+                rows = eng.var_recal(rows, recal)
             soft = getattr(eng, '_soft_nms', None)
             if soft is not None:                           # engine_options['soft_nms']: in place of the hard NMS, as in byolo_forward
                 res = eng.soft_nms(rows, self.model.obj_idx, self.model.cls_start_idx, **soft)

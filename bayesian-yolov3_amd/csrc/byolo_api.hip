@@ -155,6 +155,7 @@ extern "C" int32_t byolo_destroy(byolo_t* h) {
         if (h->d_status) (void)hipFree(h->d_status);
         if (h->pc_own) (void)hipFree(h->pc_own);
         if (h->vn_own) (void)hipFree(h->vn_own);
+        if (h->vr_tab) (void)hipFree(h->vr_tab);
         if (h->h_status) (void)hipHostFree(h->h_status);
         for (auto& ps : h->prof) {
             for (auto& e : ps.ev) if (e) (void)hipEventDestroy(e);
@@ -1026,6 +1027,7 @@ static int32_t forward_piece(byolo_t* h, const float* d_img, int32_t B, int32_t 
         h->vn_ptr = reinterpret_cast<const int32_t*>(static_cast<char*>(d_workspace) + h->plan.vote_n_off);
         h->vn_B = B; h->vn_cap = (int32_t)nms_out_cap(h);
     }
+    if (h->vr_on && h->vr_dirty) { rc = byolo_var_recal_upload(h, st); if (rc) return rc; }      // once per byolo_set_var_recal, in front of any capture
     // (see ev_convs)  Only where a forward fills the chip by itself: a small one -- 8 images at 416 x 416 are 0.5 TFLOP in launches of
     // a few dozen tiles -- gains from running beside the next (config 2: 2480 img/s one after the other, 3110 side by side).
     // opts.serialize_convs: 0 never, 1 forwards of >= 1 TFLOP (default), 2 always.
@@ -1309,6 +1311,12 @@ static int32_t enqueue_forward(byolo_t* h, const FwdArgs& a, hipStream_t st, boo
     }
     float* boxes = d_boxes ? d_boxes : reinterpret_cast<float*>(ws + h->plan.boxes_off);
     if (d_boxes || d_rows) { rc = run_decode(h, ws, boxes, B, T, st, h->tshard_T > 0 ? 1 : 0); if (rc) return rc; }
+    if ((d_boxes || d_rows) && h->vr_on && h->tshard_T == 0) {      // variance recalibration, in place on the pre-NMS rows (var_recal.hip); a T shard holds sums
+        VarRecalParams v;
+        byolo_var_recal_from_handle(h, &v);
+        v.in = boxes; v.out = boxes; v.n = (int64_t)B * h->n_boxes;
+        HIPCHK(h, launch_var_recal(v, st));
+    }
     if (h->profiling) HIPCHK(h, hipEventRecord(h->wslot().ev[3], st));
     if (d_rows) {
         NmsParams n; memset(&n, 0, sizeof n);

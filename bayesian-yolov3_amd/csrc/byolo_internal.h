@@ -222,6 +222,11 @@ struct byolo {
     bool vote_on = false; byolo_vote_cfg vote_cfg = {};
     // byolo_set_soft_nms: byolo_forward runs the soft-NMS (tail_kernels.hip soft_*) in place of the hard one
     bool soft_on = false; byolo_soft_nms_cfg soft_cfg = {};
+    // byolo_set_var_recal: byolo_forward applies vr_cfg's table in place behind the decode (var_recal.hip).  vr_tab: the handle's
+    // device copy (BYOLO_VAR_RECAL_TABLE_BYTES), filled by the first forward after a change (vr_dirty), never per forward, from
+    // vr_host, the packed table in memory that lives as long as the handle
+    bool vr_on = false, vr_dirty = false; byolo_var_recal_cfg vr_cfg = {}; double* vr_tab = nullptr;
+    double vr_host[BYOLO_VAR_RECAL_TABLE_BYTES / sizeof(double)] = {};
     const int32_t* vn_ptr = nullptr; int32_t vn_B = 0, vn_cap = 0;
     int32_t* vn_own = nullptr; size_t vn_own_cap = 0;
     int64_t first_image = 0;       // position of a call's first image in the logical batch (dropout stream)
@@ -290,5 +295,10 @@ int32_t check_run(byolo_t* h, int32_t B, int32_t T, const char* what, bool need_
 // (status cleared) if an activation left the range.  For the head trainer (train_heads.hip).
 // box_vote.hip: the VoteParams of byolo_forward's voting stage from the handle's rows and detection layers (pointers left null)
 int32_t byolo_vote_from_handle(byolo_t* h, VoteParams* p, const char* what);
+// var_recal.hip: the handle's device table brought up to date on the forward's stream `st` (waits for the device and for `st`; only
+// after byolo_set_var_recal changed it),
+// and the VarRecalParams of byolo_forward's stage (pointers to the rows left null)
+int32_t byolo_var_recal_upload(byolo_t* h, hipStream_t st);
+void byolo_var_recal_from_handle(const byolo_t* h, VarRecalParams* p);
 static inline int64_t nms_out_cap(const byolo_t* h) { return (int64_t)h->cfg.max_out * nms_classes(h->cfg.nms_mode, h->cfg.cls_cnt); }
 int32_t byolo_run_backbone(byolo_t* h, const float* d_img, int32_t B, void* d_workspace, size_t workspace_bytes, hipStream_t st);

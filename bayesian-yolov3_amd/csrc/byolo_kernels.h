@@ -313,6 +313,16 @@ struct VoteParams {
 size_t box_vote_workspace_bytes(int B, int64_t N);
 hipError_t launch_box_vote(const VoteParams& p, hipStream_t st);
 
+// ---- variance recalibration (var_recal.hip; include/byolo.h "variance recalibration") ---------------------------------------
+struct VarRecalParams {
+    const float* in; float* out;        // [n, D]; out == in: in place (only the changed columns are written)
+    int64_t n; int D;
+    int kind, target;                   // BYOLO_DET_ALEATORIC / _EPISTEMIC, BYOLO_VAR_RECAL_*
+    int n_layers, n_priors[8];
+    const double* tab;                  // device: [8][16][4] pairs (a, b)
+};
+hipError_t launch_var_recal(const VarRecalParams& p, hipStream_t st);
+
 // ---- ground-truth encoding and training loss (train_kernels.hip) ------------------------
 struct EncodeGtParams {
     const float* boxes;      // [B, max_boxes, 4]  ymin, xmin, ymax, xmax (image fractions)

@@ -30,6 +30,13 @@ NMS, `Engine.soft_nms` runs on the same pre-NMS rows of every batch, a second ev
 result dicts under 'nms' and 'soft_nms' (the ladder included when `iou_thresholds` is set), logged side by side per class and
 threshold.  `soft_nms_compare` together with `box_vote_compare` is refused: one comparison per run.
 
+`var_recal` (the path of a file `recalibrate.py` wrote): the model recalibrates its predicted variances behind the decode
+(INTEGRATION.md "Variance recalibration") and the calibrated rows are scored -- `sigma_scale` of the target kind should then read 1.
+With `var_recal_compare: True` the model runs with it OFF, `Engine.var_recal` produces the calibrated kept rows beside the raw ones,
+two evaluators score both and metrics.json carries the two result dicts under 'raw' and 'var_recal'.  Refused together with
+`box_vote_compare` or `soft_nms_compare` (one comparison per run) and with `box_vote` (the model would vote with the raw variances).
+To see what recalibrated variances do to the voted boxes, run `var_recal` with `box_vote_compare` and `iou_thresholds: 'coco'`.
+
 `box_vote_sweep` (a list of at most 8 settings dicts; needs `box_vote_compare: True`): the model still runs ONCE per batch with
 voting off; every entry gets its own `Engine.box_vote` call on that batch's rows and its own evaluator, metrics.json gains
 'box_vote_sweep': [{'settings': ..., **result}, ...] and a table of mean AP per entry is logged -- the tool for choosing `sigma_t`
@@ -115,6 +122,24 @@ def check_config(config, model='bayesian'):
                 raise ValueError(str(e))
             if not cfg['soft_nms_compare']:                          # the model runs the soft-NMS itself; the comparison runs it beside the hard one
                 cfg['engine_options'] = dict(cfg.get('engine_options', {}), soft_nms=soft)
+    # var_recal / var_recal_compare: both keys stay absent when absent
+    if cfg.get('var_recal') is not None or cfg.get('var_recal_compare') is not None:
+        recal = cfg.setdefault('var_recal', None)
+        cfg.setdefault('var_recal_compare', False)
+        if recal is not None and not isinstance(recal, str):
+            raise ValueError('var_recal is the path of a calibration file (recalibrate.py writes one)')
+        if cfg['var_recal_compare'] not in (True, False):
+            raise ValueError('var_recal_compare is True or False')
+        if cfg['var_recal_compare'] and not recal:
+            raise ValueError('var_recal_compare: True needs var_recal')
+        if recal and model == 'standard':
+            raise ValueError('var_recal: the rows of the standard model carry no variances')
+        if cfg['var_recal_compare'] and (cfg['box_vote_compare'] or cfg.get('soft_nms_compare')):
+            raise ValueError('var_recal_compare together with box_vote_compare or soft_nms_compare: one comparison per run')
+        if cfg['var_recal_compare'] and cfg['box_vote']:
+            raise ValueError('var_recal_compare together with box_vote: the model would vote with the raw variances')
+        if recal and not cfg['var_recal_compare']:                   # the model recalibrates behind its decode; the comparison beside the raw rows
+            cfg['engine_options'] = dict(cfg.get('engine_options', {}), var_recal=recal)
     from byolo.evaluate import height_subsets, ladder_thresholds
     ladder_thresholds(cfg.get('iou_thresholds'))                     # ValueError on a bad ladder; both keys stay absent when absent
     height_subsets(cfg.get('eval_subsets'))                          # likewise; the rule's parameters stay absent without subsets
@@ -188,13 +213,14 @@ def build_model(cfg):
 
 
 def score(model, feed, evaluator, seed=0, max_batches=None, points=None, vote=None, vote_evaluator=None, sweep=(), soft=None,
-          soft_evaluator=None):
+          soft_evaluator=None, recal=None, recal_evaluator=None):
     """Model.run -> Evaluator.add over the batches of `feed` (the 'eval' split of lib_yolo.dataset_utils._Feed); returns the
     number of images.  points: a list that receives (time, images so far) after every batch.  vote (settings) and
     vote_evaluator: every batch's NMS rows are also voted (Engine.box_vote) and the voted rows scored by vote_evaluator.
     sweep: [(settings, evaluator)], each voted and scored the same way on the same rows of the one forward.  soft (settings) and
     soft_evaluator: Engine.soft_nms runs on every batch's pre-NMS rows beside the model's hard NMS (and, where the model votes, is
-    voted with the same settings) and its rows are scored by soft_evaluator."""
+    voted with the same settings) and its rows are scored by soft_evaluator.  recal (a VarCalibration) and recal_evaluator:
+    Engine.var_recal calibrates every batch's kept rows beside the raw ones and recal_evaluator scores them."""
     images = 0
     for step, b in enumerate(feed):
         if max_batches is not None and step >= max_batches:
@@ -205,6 +231,8 @@ def score(model, feed, evaluator, seed=0, max_batches=None, points=None, vote=No
             voted = res.get('engine', model.engine).box_vote(res['boxes'], res, model.obj_idx, model.cls_start_idx,
                                                              geom=model.det_layers, **({} if settings is True else dict(settings)))
             vev.add(voted['rows'], res['count'][:, 0], b['boxes'], b['labels'], b['counts'])
+        if recal_evaluator is not None:
+            recal_evaluator.add(res.get('engine', model.engine).var_recal(res['rows'], recal), res['count'][:, 0], b['boxes'], b['labels'], b['counts'])
         if soft_evaluator is not None:
             eng = res.get('engine', model.engine)
             sres = eng.soft_nms(res['boxes'], model.obj_idx, model.cls_start_idx, **({} if soft is True else dict(soft)))
@@ -298,13 +326,21 @@ def evaluate(config, model='bayesian'):
     ev_vote = new_ev() if cfg['box_vote_compare'] else None
     sweep = [(settings, new_ev()) for settings in (cfg.get('box_vote_sweep') or [])]
     ev_soft = new_ev() if cfg.get('soft_nms_compare') else None
+    ev_recal, recal = None, None
+    if cfg.get('var_recal_compare'):
+        from byolo.recalibrate import VarCalibration
+        recal = VarCalibration.load(cfg['var_recal'])
+        recal.check(MODELS[cfg['model']], [len(dl.priors) for dl in m.det_layers])
+        ev_recal = new_ev()
     feed = dataset_utils._Feed(cfg, 'data', 'eval', device=m.engine.torch_device)
     try:
         t0 = time.time()
         points = []
         images = score(m, feed, ev, seed=int(cfg['seed']), max_batches=cfg['eval_batches'], points=points, vote=cfg['box_vote'],
-                       vote_evaluator=ev_vote, sweep=sweep, soft=cfg.get('soft_nms'), soft_evaluator=ev_soft)
+                       vote_evaluator=ev_vote, sweep=sweep, soft=cfg.get('soft_nms'), soft_evaluator=ev_soft, recal=recal,
+                       recal_evaluator=ev_recal)
         metrics = ev.finish()
+        recal_metrics = ev_recal.finish() if ev_recal is not None else None
         soft_metrics = ev_soft.finish() if ev_soft is not None else None
         voted_metrics = ev_vote.finish() if ev_vote is not None else None
         sweep_metrics = [e.finish() for _, e in sweep]
@@ -318,6 +354,12 @@ def evaluate(config, model='bayesian'):
             e.close()
         if ev_soft is not None:
             ev_soft.close()
+        if ev_recal is not None:
+            ev_recal.close()
+    if recal_metrics is not None and 'localisation' in recal_metrics:
+        from byolo import eval_loc
+        for line in eval_loc.log_lines(recal_metrics['localisation']):
+            logging.info('var_recal: ' + line)
     if soft_metrics is not None:
         for c, v in zip(metrics['classes'], soft_metrics['classes']):
             logging.info('class {:3d}: AP at IoU {:.2f}: NMS rows {:.4f}, soft-NMS rows {:.4f}; LAMR {:.4f}, {:.4f}'.format(
@@ -355,6 +397,9 @@ def evaluate(config, model='bayesian'):
     if soft_metrics is not None:                          # likewise: the hard NMS's result beside the soft-NMS's
         metrics = dict({k: v for k, v in metrics.items() if k not in soft_metrics}, nms={k: metrics[k] for k in soft_metrics},
                        soft_nms=soft_metrics)
+    if recal_metrics is not None:                         # likewise: the raw rows' result beside the recalibrated rows'
+        metrics = dict({k: v for k, v in metrics.items() if k not in recal_metrics}, raw={k: metrics[k] for k in recal_metrics},
+                       var_recal=recal_metrics)
     if sweep:
         metrics['box_vote_sweep'] = [dict(r, settings=settings) for (settings, _), r in zip(sweep, sweep_metrics)]
     with open(os.path.join(out_path, 'metrics.json'), 'w') as f:

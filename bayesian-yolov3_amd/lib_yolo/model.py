@@ -81,6 +81,8 @@ class ModelBuilder:
         self.__box_vote = opts.pop('box_vote', None)
         # 'soft_nms': True | {settings}: the soft-NMS in place of the hard one (Engine.set_soft_nms)
         self.__soft_nms = opts.pop('soft_nms', None)
+        # 'var_recal': a path | dict | byolo.recalibrate.VarCalibration: the variances recalibrated behind the decode (Engine.set_var_recal)
+        self.__var_recal = opts.pop('var_recal', None)
         self.engine = Engine(img_size=shape[1:], cls_cnt=cls_cnt, **opts)
         self.T = 1
 
@@ -113,6 +115,8 @@ class ModelBuilder:
             self.engine.set_soft_nms(self.__soft_nms)
         if self.__box_vote:
             self.engine.set_box_vote(self.__box_vote)
+        if self.__var_recal is not None:
+            self.engine.set_var_recal(self.__var_recal)
         return Model(self.__layers, self.__det_layers, self.__cls_cnt, obj_idx, cls_start_idx, builder=self)
 
     def __update_layers(self, index, name, kind):

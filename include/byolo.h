@@ -802,6 +802,63 @@ BYOLO_API int32_t byolo_soft_nms(byolo_t* h, const float* d_boxes, int32_t B, in
                                  void* d_ws, size_t ws_bytes, float* d_rows, int32_t* d_kept, int32_t* d_count, void* stream);
 BYOLO_API int32_t byolo_set_soft_nms(byolo_t* h, const byolo_soft_nms_cfg* cfg);
 
+/* ---- variance recalibration (sigma-scaling, Laves et al. 2020; no counterpart in the reference; csrc/var_recal.hip; INTEGRATION.md
+ * "Variance recalibration" has the definitions in full, tests/_var_recal_ref.py restates them) -----------------------------------
+ * A calibration is a table of float64 pairs (a, b) per detection layer l, prior p and coordinate c of (x, y, w, h); the calibrated
+ * variance of a row is v' = a v^b, v the row's TARGET variance of that coordinate: BYOLO_VAR_RECAL_ALE the aleatoric column,
+ * _EPI the epistemic column, _TOTAL their float64 sum -- ONE factor f = v' / v then multiplies both columns.
+ * Apply (one thread per row of D floats; kind = BYOLO_DET_ALEATORIC rows of 14 + C or BYOLO_DET_EPISTEMIC rows of 21 + C columns):
+ *   row       layer / prior from the last two columns; an id that is not finite, not integral or outside the table leaves the
+ *             whole row untouched
+ *   factor    b == 1 exactly: f = a.  Otherwise f = a exp((b - 1) log v), float64, and the coordinate is untouched unless v is
+ *             finite and > 0
+ *   column    float32(float64(col) f), rounded once; a NaN keeps its bits
+ *   derived   aleatoric rows: column 8 = ((c4 c5) c6) c7; Bayesian rows: column 13 = (((0 + a0) + a1) + a2) + a3, both float32
+ *             as the decode forms them, and column 12 = float32(float64(col12) P), P = ((fx fy) fw) fh over the epistemic
+ *             factors (1 for an untouched coordinate; the column is left alone under _ALE and when it is NaN)
+ * Every other column keeps its bits: the identity table (a = b = 1) reproduces its input.
+ * byolo_var_recal_apply: the stand-alone stage, handle-less (errors: byolo_last_error(NULL)); d_out [n, D] must not overlap d_in;
+ * d_table: BYOLO_VAR_RECAL_TABLE_BYTES bytes of device memory, 8-byte aligned, holding what byolo_var_recal_table(cfg, h_table)
+ * wrote to the host buffer h_table of that size -- the caller copies it to the device ONCE per table, complete or ordered in front
+ * of `stream`, and may use it for any number of calls: the call itself copies nothing and never waits.  Refused with BYOLO_ERR_ARG, the field named: a wrong struct_bytes, an unknown kind / target, a
+ * target the rows do not have, D < 14 (aleatoric) or < 21 (Bayesian), n_layers / n_priors beyond the limits of byolo_eval_loc_cfg,
+ * an a that is not finite and > 0, a b that is not finite.
+ * byolo_set_var_recal(h, cfg): byolo_forward applies the table in place on the pre-NMS rows right behind the decode, so d_boxes,
+ * d_rows, the soft-NMS and box voting see calibrated variances; the NMS reads no variance column, so d_kept / d_count do not
+ * change (cfg NULL: off, the default; with it off every output is what it was without this entry point).  The handle keeps a
+ * device copy of the table: no allocation and no host wait per forward.  kind and the geometry must be the handle's
+ * (BYOLO_ERR_ARG names the field; BYOLO_ERR_STATE before the detection layers exist).  A T-shard forward hands out sums and
+ * applies nothing: call byolo_var_recal_apply behind byolo_finish_tshard.
+ * Fit (byolo_var_recal_fit): d_r / d_v [n] float64, the residuals and target variances of the eligible entries, grouped into
+ * n_seg consecutive segments d_seg[s] .. d_seg[s + 1] (int64, n_seg + 1 offsets); one workgroup per segment, the whole Newton
+ * iteration of BYOLO_VAR_RECAL_POWER inside the one launch.  Every sum is the FIXED SUM: partial[t] = the sequential sum of the
+ * terms j = t (mod 256) in ascending j, the result the sequential sum of partial[0 .. 255]; float64, no atomics, the same bytes
+ * in every run.  d_out [n_seg][BYOLO_VAR_RECAL_FIT_WORDS] float64: n, a, b, mean r^2 / v, NLL before, NLL after, iterations,
+ * status (BYOLO_VAR_RECAL_FITTED, _SCALE_FALLBACK: power with n < 3, a singular Hessian or a step that is not finite -- the scale
+ * answer with b = 1, _IDENTITY: sum r^2 / v is 0 or not finite, _EMPTY), converged, max |log v - mean log v|.
+ * d_ws >= byolo_var_recal_fit_workspace_bytes(n), 8-byte aligned.  INTEGRATION.md has the Newton rule. */
+#define BYOLO_VAR_RECAL_TABLE_BYTES 8192
+#define BYOLO_VAR_RECAL_FIT_WORDS 10
+enum { BYOLO_VAR_RECAL_ALE = 1, BYOLO_VAR_RECAL_EPI = 2, BYOLO_VAR_RECAL_TOTAL = 3 };
+enum { BYOLO_VAR_RECAL_SCALE = 0, BYOLO_VAR_RECAL_POWER = 1 };
+enum { BYOLO_VAR_RECAL_FITTED = 0, BYOLO_VAR_RECAL_SCALE_FALLBACK = 1, BYOLO_VAR_RECAL_IDENTITY = 2, BYOLO_VAR_RECAL_EMPTY = 3 };
+typedef struct byolo_var_recal_cfg {
+    int32_t struct_bytes;          /* sizeof(byolo_var_recal_cfg) of the caller's header: a mismatch is BYOLO_ERR_ARG */
+    int32_t kind;                  /* BYOLO_DET_ALEATORIC or BYOLO_DET_EPISTEMIC: the layout of the rows */
+    int32_t target;                /* BYOLO_VAR_RECAL_ALE / _EPI / _TOTAL */
+    int32_t n_layers;
+    int32_t n_priors[BYOLO_EVAL_LOC_MAX_LAYERS];
+    double a[BYOLO_EVAL_LOC_MAX_LAYERS][BYOLO_EVAL_LOC_MAX_PRIORS][4];
+    double b[BYOLO_EVAL_LOC_MAX_LAYERS][BYOLO_EVAL_LOC_MAX_PRIORS][4];
+} byolo_var_recal_cfg;
+BYOLO_API int32_t byolo_var_recal_table(const byolo_var_recal_cfg* cfg, double* h_table);
+BYOLO_API int32_t byolo_var_recal_apply(const byolo_var_recal_cfg* cfg, const float* d_in, int64_t n, int32_t D, float* d_out,
+                                        const void* d_table, void* stream);
+BYOLO_API int32_t byolo_set_var_recal(byolo_t* h, const byolo_var_recal_cfg* cfg);
+BYOLO_API size_t byolo_var_recal_fit_workspace_bytes(int64_t n);
+BYOLO_API int32_t byolo_var_recal_fit(const double* d_r, const double* d_v, const int64_t* d_seg, int32_t n_seg, int64_t n,
+                                      int32_t method, double* d_out, void* d_ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
