@@ -119,6 +119,19 @@ class VarRecalCfg(ctypes.Structure):
                [(n, ((ctypes.c_double * 4) * EVAL_LOC_MAX_PRIORS) * EVAL_LOC_MAX_LAYERS) for n in ("a", "b")]
 
 
+SCORE_RECAL_MAX_K, SCORE_RECAL_MAX_GROUPS, SCORE_RECAL_TABLE_BYTES, SCORE_RECAL_FIT_WORDS = 8, 80, 5120, 36      # BYOLO_SCORE_RECAL_*
+SCORE_RECAL_BY_ALL, SCORE_RECAL_BY_CLASS = 0, 1
+SCORE_RECAL_F_BIAS, SCORE_RECAL_F_LOGIT, SCORE_RECAL_F_LOG_HEIGHT, SCORE_RECAL_F_COL_ID, SCORE_RECAL_F_COL_LOG = 0, 1, 2, 3, 4
+SCORE_RECAL_FIT, SCORE_RECAL_IDENTITY, SCORE_RECAL_EMPTY = 0, 1, 2                                              # (status of a fitted segment)
+
+
+class ScoreRecalCfg(ctypes.Structure):
+    """include/byolo.h byolo_score_recal_cfg (field for field; tests/test_score_recal_cpu.py compares the two)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("struct_bytes", "kind", "cls_cnt", "by", "K")] + \
+               [(n, ctypes.c_int32 * SCORE_RECAL_MAX_K) for n in ("feat_kind", "feat_col")] + [("reserved", ctypes.c_int32)] + \
+               [("w", (ctypes.c_double * SCORE_RECAL_MAX_K) * SCORE_RECAL_MAX_GROUPS)]
+
+
 _i32, _i64, _f32 = ctypes.c_int32, ctypes.c_int64, ctypes.c_float
 _vp, _cp, _sz, _u64 = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint64
 _P = ctypes.POINTER
@@ -239,6 +252,13 @@ PROTOTYPES = {
     "byolo_set_var_recal": (_i32, [_vp, _P(VarRecalCfg)]),
     "byolo_var_recal_fit_workspace_bytes": (_sz, [_i64]),
     "byolo_var_recal_fit": (_i32, [_vp, _vp, _vp, _i32, _i64, _i32, _vp, _vp, _sz, _vp]),
+    "byolo_score_recal_table": (_i32, [_P(ScoreRecalCfg), _vp]),
+    "byolo_score_recal_apply": (_i32, [_P(ScoreRecalCfg), _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "byolo_set_score_recal": (_i32, [_vp, _P(ScoreRecalCfg)]),
+    "byolo_score_recal_scores": (_i32, [_vp, _vp, _i32, _i32, _vp]),
+    "byolo_score_recal_features": (_i32, [_P(ScoreRecalCfg), _vp, _i64, _i32, _i32, _i32, _i32, _P(ctypes.c_int32), _vp, _vp]),
+    "byolo_score_recal_fit_workspace_bytes": (_sz, [_i64, _i32]),
+    "byolo_score_recal_fit": (_i32, [_vp, _vp, _vp, _i32, _i64, _i32, ctypes.c_double, _i64, _vp, _vp, _sz, _vp]),
 }
 
 

@@ -41,6 +41,8 @@ class Engine:
         self._soft_nms = None            # the settings set_soft_nms() switched the soft-NMS on with (None: off, the hard NMS)
         self._var_recal = None           # the VarCalibration set_var_recal() switched variance recalibration on with (None: off)
         self._var_recal_table = None     # var_recal(): (packed table bytes, device, its copy on that device) of the last call
+        self._score_recal = None         # the ScoreCalibration set_score_recal() switched score recalibration on with (None: off)
+        self._score_recal_table = None   # score_recal(): as _var_recal_table
 
     # ---- arithmetic of the convolution stack (include/byolo.h: BYOLO_PREC_*) ----------------------------
     @property
@@ -174,6 +176,8 @@ class Engine:
             t.set_soft_nms(self._soft_nms)
         if self._var_recal is not None:
             t.set_var_recal(self._var_recal)
+        if self._score_recal is not None:
+            t.set_score_recal(self._score_recal)
         t.set_params(self.get_params())
         t.finalize()
         return t
@@ -444,6 +448,10 @@ class Engine:
             vn = torch.empty((B, self.out_cap), dtype=torch.int32, device=dev)
             check(self._h, lib.byolo_box_vote_counts(self._h, ctypes.c_void_p(vn.data_ptr()), B, self.out_cap, ctypes.c_void_p(stream)))
             res["vote_n"] = vn
+        if want_nms and self._score_recal is not None:    # 'rows' carry the calibrated score in obj (byolo_set_score_recal)
+            sc = torch.empty((B, self.out_cap), dtype=torch.float32, device=dev)
+            check(self._h, lib.byolo_score_recal_scores(self._h, ctypes.c_void_p(sc.data_ptr()), B, self.out_cap, ctypes.c_void_p(stream)))
+            res["score"] = sc
         return res
 
     # ---- variance voting (include/byolo.h "variance voting") ---------------------------------
@@ -572,6 +580,61 @@ class Engine:
                                        ctypes.c_void_p(tab.data_ptr()), ctypes.c_void_p(stream))
         check(None, rc)
         return out
+
+    # ---- score recalibration (include/byolo.h "score recalibration"; byolo/score_recal.py) ------------------------
+    def set_score_recal(self, cal=None):
+        """Score recalibration inside forward(): a byolo.score_recal.ScoreCalibration, the path of a saved one or its dict switches
+        it on -- behind the NMS or soft-NMS and in front of box voting the kept rows' obj column is rewritten so that obj * cls[class]
+        is the calibrated score, and the result gains 'score' [B, cap]; 'kept', 'count' and every other column do not change, and the
+        rows keep their pick order --, None / False switches it off (the default; forward() is then what it was).  ValueError naming
+        the field when the calibration was fitted for another variant or class count; one warning line when it was fitted under
+        other soft_nms / var_recal settings than this engine runs.  A twin made before the call follows it."""
+        from .score_recal import ScoreCalibration
+        if cal is None or cal is False:
+            check(self._h, lib.byolo_set_score_recal(self._h, None))
+            self._score_recal = None
+        else:
+            cal = ScoreCalibration.coerce(cal)
+            dets = [a for n, a in self._graph if n == "add_detection"]
+            if not dets:
+                raise ValueError("set_score_recal: add the detection layers first")
+            cal.check(self._VARIANT_OF_KIND[int(dets[-1][1])], self.cfg.cls_cnt)
+            cal.warn_settings(self._soft_nms, self._var_recal)
+            cfg = cal.cfg()
+            check(self._h, lib.byolo_set_score_recal(self._h, ctypes.byref(cfg)))
+            self._score_recal = cal
+        if self._twin is not None:
+            self._twin.set_score_recal(self._score_recal)
+
+    def score_recal(self, rows, count, cal):
+        """The stage by itself (byolo_score_recal_apply) on kept rows [B, cap, D] and count [B, 2] as forward() returns them: returns
+        {'rows': calibrated copy, 'score': [B, cap] float32}; `rows` is not touched.  The table is copied to the device when it
+        differs from the last call's (a copy torch waits for); calls with the same table copy nothing and wait for nothing."""
+        torch = _torch()
+        from .score_recal import ScoreCalibration
+        cal = ScoreCalibration.coerce(cal)
+        assert rows.is_cuda and rows.dtype == torch.float32 and rows.is_contiguous() and rows.dim() == 3
+        B, cap, D = (int(v) for v in rows.shape)
+        assert count.is_cuda and count.dtype == torch.int32 and count.is_contiguous() and tuple(count.shape) == (B, 2)
+        cal.check(cal.variant, self.cfg.cls_cnt)
+        want = {"yolov3": 5, "yolov3_aleatoric": 14, "bayesian_yolov3_aleatoric": 21}[cal.variant] + self.cfg.cls_cnt
+        if D != want:
+            raise ValueError("score_recal: variant: rows of %d columns, %s rows with %d classes have %d" % (D, cal.variant, self.cfg.cls_cnt, want))
+        out = torch.empty_like(rows)
+        score = torch.empty((B, cap), dtype=torch.float32, device=rows.device)
+        if B * cap == 0:
+            return dict(rows=out, score=score)
+        cfg = cal.cfg()
+        host = np.empty(_lib.SCORE_RECAL_TABLE_BYTES // 8, dtype=np.float64)
+        check(None, lib.byolo_score_recal_table(ctypes.byref(cfg), ctypes.c_void_p(host.ctypes.data)))
+        key = host.tobytes()
+        if self._score_recal_table is None or self._score_recal_table[0] != key or self._score_recal_table[1] != rows.device:
+            self._score_recal_table = (key, rows.device, torch.from_numpy(host).to(rows.device))      # (pageable memory: the copy is complete on return)
+        tab = self._score_recal_table[2]
+        stream = torch.cuda.current_stream(rows.device).cuda_stream
+        p = lambda t: ctypes.c_void_p(t.data_ptr())
+        check(None, lib.byolo_score_recal_apply(ctypes.byref(cfg), p(rows), p(count), B, cap, D, p(out), p(score), p(tab), ctypes.c_void_p(stream)))
+        return dict(rows=out, score=score)
 
     # ---- soft-NMS (include/byolo.h "soft-NMS"; INTEGRATION.md "Soft-NMS") -----------------------------------------
     SOFT_METHODS = {"linear": _lib.SOFT_NMS_LINEAR, "gaussian": _lib.SOFT_NMS_GAUSSIAN}

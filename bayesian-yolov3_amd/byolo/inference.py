@@ -445,6 +445,9 @@ class InferenceLoop:
                 res = eng.soft_nms(rows, self.model.obj_idx, self.model.cls_start_idx, **soft)
             else:
                 res = eng.sort_nms(rows, self.model.obj_idx, self.model.cls_start_idx)
+            score = getattr(eng, '_score_recal', None)
+            if score is not None:                          # engine_options['score_recal']: what byolo_forward does behind its own NMS
+                res = dict(res, **eng.score_recal(res['rows'], res['count'], score))
             vote = getattr(eng, '_box_vote', None)
             if vote is not None:                           # engine_options['box_vote']: what byolo_forward does behind its own NMS
                 res.update(eng.box_vote(rows, res, self.model.obj_idx, self.model.cls_start_idx, geom=self.model.det_layers, **vote))

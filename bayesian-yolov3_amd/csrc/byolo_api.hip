@@ -156,6 +156,8 @@ extern "C" int32_t byolo_destroy(byolo_t* h) {
         if (h->pc_own) (void)hipFree(h->pc_own);
         if (h->vn_own) (void)hipFree(h->vn_own);
         if (h->vr_tab) (void)hipFree(h->vr_tab);
+        if (h->sr_tab) (void)hipFree(h->sr_tab);
+        if (h->sr_own) (void)hipFree(h->sr_own);
         if (h->h_status) (void)hipHostFree(h->h_status);
         for (auto& ps : h->prof) {
             for (auto& e : ps.ev) if (e) (void)hipEventDestroy(e);
@@ -964,6 +966,13 @@ static int32_t forward_impl(byolo_t* h, const float* d_img, int32_t B, int32_t T
                 HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->vn_own), (size_t)B * out_cap * sizeof(int32_t)));
                 h->vn_own_cap = (size_t)B * out_cap;
             }
+            const bool scoring = h->sr_on && d_rows;
+            if (scoring && h->sr_own_cap < (size_t)B * out_cap) {
+                HIPCHK(h, hipSetDevice(h->device));
+                if (h->sr_own) { HIPCHK(h, hipDeviceSynchronize()); HIPCHK(h, hipFree(h->sr_own)); h->sr_own = nullptr; h->sr_own_cap = 0; }
+                HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->sr_own), (size_t)B * out_cap * sizeof(float)));
+                h->sr_own_cap = (size_t)B * out_cap;
+            }
             int32_t rc = BYOLO_OK;
             for (int64_t lo = 0; lo < B && rc == BYOLO_OK; lo += cap) {
                 const int32_t n = (int32_t)std::min<int64_t>(cap, B - lo);
@@ -982,7 +991,13 @@ static int32_t forward_impl(byolo_t* h, const float* d_img, int32_t B, int32_t T
                                                         hipMemcpyDeviceToDevice, reinterpret_cast<hipStream_t>(stream));
                     if (e != hipSuccess) rc = fail(h, BYOLO_ERR_HIP, "byolo_forward: vote counts of a piece: %s", hipGetErrorString(e));
                 }
+                if (rc == BYOLO_OK && scoring) {
+                    const hipError_t e = hipMemcpyAsync(h->sr_own + (size_t)lo * out_cap, h->sr_ptr, (size_t)n * out_cap * sizeof(float),
+                                                        hipMemcpyDeviceToDevice, reinterpret_cast<hipStream_t>(stream));
+                    if (e != hipSuccess) rc = fail(h, BYOLO_ERR_HIP, "byolo_forward: calibrated scores of a piece: %s", hipGetErrorString(e));
+                }
             }
+            if (rc == BYOLO_OK && scoring) { h->sr_ptr = h->sr_own; h->sr_B = B; }
             if (rc == BYOLO_OK && per_class) { h->pc_counts = h->pc_own; h->pc_B = B; }
             if (rc == BYOLO_OK && voting) { h->vn_ptr = h->vn_own; h->vn_B = B; }
             h->first_image = first;
@@ -1028,6 +1043,11 @@ static int32_t forward_piece(byolo_t* h, const float* d_img, int32_t B, int32_t 
         h->vn_B = B; h->vn_cap = (int32_t)nms_out_cap(h);
     }
     if (h->vr_on && h->vr_dirty) { rc = byolo_var_recal_upload(h, st); if (rc) return rc; }      // once per byolo_set_var_recal, in front of any capture
+    if (d_rows && h->sr_on) {
+        if (h->sr_dirty) { rc = byolo_score_recal_upload(h, st); if (rc) return rc; }           // likewise once per byolo_set_score_recal
+        h->sr_ptr = reinterpret_cast<const float*>(static_cast<char*>(d_workspace) + h->plan.score_off);
+        h->sr_B = B; h->sr_cap = (int32_t)nms_out_cap(h);
+    }
     // (see ev_convs)  Only where a forward fills the chip by itself: a small one -- 8 images at 416 x 416 are 0.5 TFLOP in launches of
     // a few dozen tiles -- gains from running beside the next (config 2: 2480 img/s one after the other, 3110 side by side).
     // opts.serialize_convs: 0 never, 1 forwards of >= 1 TFLOP (default), 2 always.
@@ -1330,6 +1350,12 @@ static int32_t enqueue_forward(byolo_t* h, const FwdArgs& a, hipStream_t st, boo
             sp.n = n; sp.n.ws = ws + h->plan.soft_off; sp.n.ws_bytes = soft_nms_workspace_bytes(B, h->n_boxes, n.C);
             HIPCHK(h, launch_soft_nms(sp, st));
         } else HIPCHK(h, launch_sort_nms(n, st));
+        if (h->sr_on) {                                     // score recalibration, in place on the kept rows (score_recal.hip): reads d_count on the device
+            ScoreRecalParams s;
+            byolo_score_recal_from_handle(h, &s);
+            s.in = d_rows; s.out = d_rows; s.count = d_count; s.score = reinterpret_cast<float*>(ws + h->plan.score_off); s.B = B; s.cap = (int)nms_out_cap(h);
+            HIPCHK(h, launch_score_recal(s, st));
+        }
         if (h->vote_on) {                                   // variance voting, in place on the kept rows (box_vote.hip)
             VoteParams v;
             rc = byolo_vote_from_handle(h, &v, "byolo_forward"); if (rc) return rc;

@@ -122,6 +122,7 @@ struct Plan {
     size_t arena = 0, boxes_off = 0, nms_off = 0, stats_off = 0, total = 0;
     size_t soft_off = 0;                   // soft-NMS (byolo_set_soft_nms): the stage's workspace; no bytes while it is off
     size_t vote_n_off = 0, vote_off = 0;   // box voting (byolo_set_box_vote): vote_n [B, cap] and the stage's workspace; no bytes while it is off
+    size_t score_off = 0;                  // score recalibration (byolo_set_score_recal): score [B, cap]; no bytes while it is off
     size_t img_split_off = 0;      // split precision: the image as hi/lo pairs, for a matrix-pipe convolution that reads it (img_c % 32 == 0)
     size_t slab_off = 0, slab_bytes = 0, cnt_off = 0, cnt_bytes = 0;   // split-K slabs (shared by all steps), per-step ticket counters
     std::vector<ConvSplit> split;  // per step
@@ -227,6 +228,13 @@ struct byolo {
     // vr_host, the packed table in memory that lives as long as the handle
     bool vr_on = false, vr_dirty = false; byolo_var_recal_cfg vr_cfg = {}; double* vr_tab = nullptr;
     double vr_host[BYOLO_VAR_RECAL_TABLE_BYTES / sizeof(double)] = {};
+    // byolo_set_score_recal: byolo_forward applies sr_cfg's table in place on the kept rows behind the NMS (score_recal.hip).  sr_tab /
+    // sr_host / sr_dirty: as vr_*.  sr_ptr: where the last such forward left score [sr_B, sr_cap] -- inside that call's workspace,
+    // or in sr_own (a forward that ran in pieces), as vn_ptr / vn_own
+    bool sr_on = false, sr_dirty = false; byolo_score_recal_cfg sr_cfg = {}; double* sr_tab = nullptr;
+    double sr_host[BYOLO_SCORE_RECAL_TABLE_BYTES / sizeof(double)] = {};
+    const float* sr_ptr = nullptr; int32_t sr_B = 0, sr_cap = 0;
+    float* sr_own = nullptr; size_t sr_own_cap = 0;
     const int32_t* vn_ptr = nullptr; int32_t vn_B = 0, vn_cap = 0;
     int32_t* vn_own = nullptr; size_t vn_own_cap = 0;
     int64_t first_image = 0;       // position of a call's first image in the logical batch (dropout stream)
@@ -300,5 +308,8 @@ int32_t byolo_vote_from_handle(byolo_t* h, VoteParams* p, const char* what);
 // and the VarRecalParams of byolo_forward's stage (pointers to the rows left null)
 int32_t byolo_var_recal_upload(byolo_t* h, hipStream_t st);
 void byolo_var_recal_from_handle(const byolo_t* h, VarRecalParams* p);
+// score_recal.hip: the same two for byolo_set_score_recal (pointers to the rows, the counts and the scores left null)
+int32_t byolo_score_recal_upload(byolo_t* h, hipStream_t st);
+void byolo_score_recal_from_handle(const byolo_t* h, ScoreRecalParams* p);
 static inline int64_t nms_out_cap(const byolo_t* h) { return (int64_t)h->cfg.max_out * nms_classes(h->cfg.nms_mode, h->cfg.cls_cnt); }
 int32_t byolo_run_backbone(byolo_t* h, const float* d_img, int32_t B, void* d_workspace, size_t workspace_bytes, hipStream_t st);

@@ -323,6 +323,19 @@ struct VarRecalParams {
 };
 hipError_t launch_var_recal(const VarRecalParams& p, hipStream_t st);
 
+// ---- score recalibration (score_recal.hip; include/byolo.h "score recalibration") -------------------------------------------
+struct ScoreRecalParams {
+    const float* in; float* out;        // kept rows [B, cap, D]; out == in: in place (only obj is written)
+    const int32_t* count;               // [B, 2]: the first word of each pair counts the kept rows
+    float* score;                       // [B, cap]
+    int B, cap, D;
+    int obj_idx, cls_start, C;
+    int by_class, K;
+    int feat_kind[8], feat_col[8];
+    const double* tab;                  // device: [80][8] weights
+};
+hipError_t launch_score_recal(const ScoreRecalParams& p, hipStream_t st);
+
 // ---- ground-truth encoding and training loss (train_kernels.hip) ------------------------
 struct EncodeGtParams {
     const float* boxes;      // [B, max_boxes, 4]  ymin, xmin, ymax, xmax (image fractions)

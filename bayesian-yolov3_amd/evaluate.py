@@ -37,6 +37,12 @@ two evaluators score both and metrics.json carries the two result dicts under 'r
 `box_vote_compare` or `soft_nms_compare` (one comparison per run) and with `box_vote` (the model would vote with the raw variances).
 To see what recalibrated variances do to the voted boxes, run `var_recal` with `box_vote_compare` and `iou_thresholds: 'coco'`.
 
+`score_recal` (the path of a file `recalibrate.py --what score` wrote): the model recalibrates the score of its kept rows behind the
+NMS (INTEGRATION.md "Score recalibration") and those rows are scored.  With `score_recal_compare: True` the model runs with it OFF,
+`Engine.score_recal` produces the calibrated rows beside the raw ones, two evaluators score both -- the ladder and the subsets
+included when set -- and metrics.json carries the two result dicts under 'raw' and 'score_recal'.  Refused together with any other
+`*_compare` (one comparison per run) and with `box_vote`.
+
 `box_vote_sweep` (a list of at most 8 settings dicts; needs `box_vote_compare: True`): the model still runs ONCE per batch with
 voting off; every entry gets its own `Engine.box_vote` call on that batch's rows and its own evaluator, metrics.json gains
 'box_vote_sweep': [{'settings': ..., **result}, ...] and a table of mean AP per entry is logged -- the tool for choosing `sigma_t`
@@ -140,8 +146,24 @@ def check_config(config, model='bayesian'):
             raise ValueError('var_recal_compare together with box_vote: the model would vote with the raw variances')
         if recal and not cfg['var_recal_compare']:                   # the model recalibrates behind its decode; the comparison beside the raw rows
             cfg['engine_options'] = dict(cfg.get('engine_options', {}), var_recal=recal)
+    # score_recal / score_recal_compare: both keys stay absent when absent
+    if cfg.get('score_recal') is not None or cfg.get('score_recal_compare') is not None:
+        srecal = cfg.setdefault('score_recal', None)
+        cfg.setdefault('score_recal_compare', False)
+        if srecal is not None and not isinstance(srecal, str):
+            raise ValueError('score_recal is the path of a calibration file (recalibrate.py --what score writes one)')
+        if cfg['score_recal_compare'] not in (True, False):
+            raise ValueError('score_recal_compare is True or False')
+        if cfg['score_recal_compare'] and not srecal:
+            raise ValueError('score_recal_compare: True needs score_recal')
+        if cfg['score_recal_compare'] and (cfg['box_vote_compare'] or cfg.get('soft_nms_compare') or cfg.get('var_recal_compare')):
+            raise ValueError('score_recal_compare together with another *_compare: one comparison per run')
+        if cfg['score_recal_compare'] and cfg['box_vote']:
+            raise ValueError('score_recal_compare together with box_vote: the stage runs in front of the vote, the comparison could only run behind it')
+        if srecal and not cfg['score_recal_compare']:                # the model recalibrates behind its NMS; the comparison beside the raw rows
+            cfg['engine_options'] = dict(cfg.get('engine_options', {}), score_recal=srecal)
     from byolo.evaluate import height_subsets, ladder_thresholds
-    ladder_thresholds(cfg.get('iou_thresholds'))                     # ValueError on a bad ladder; both keys stay absent when absent
+    ladder_thresholds(cfg.get('iou_thresholds'))                    # ValueError on a bad ladder; both keys stay absent when absent
     height_subsets(cfg.get('eval_subsets'))                          # likewise; the rule's parameters stay absent without subsets
     given = [k for k in ('eval_ignore_thresh', 'eval_height_slack', 'eval_ignore_other_classes') if k in cfg]
     if cfg.get('eval_subsets') is None:
@@ -213,14 +235,15 @@ def build_model(cfg):
 
 
 def score(model, feed, evaluator, seed=0, max_batches=None, points=None, vote=None, vote_evaluator=None, sweep=(), soft=None,
-          soft_evaluator=None, recal=None, recal_evaluator=None):
+          soft_evaluator=None, recal=None, recal_evaluator=None, score_cal=None, score_evaluator=None):
     """Model.run -> Evaluator.add over the batches of `feed` (the 'eval' split of lib_yolo.dataset_utils._Feed); returns the
     number of images.  points: a list that receives (time, images so far) after every batch.  vote (settings) and
     vote_evaluator: every batch's NMS rows are also voted (Engine.box_vote) and the voted rows scored by vote_evaluator.
     sweep: [(settings, evaluator)], each voted and scored the same way on the same rows of the one forward.  soft (settings) and
     soft_evaluator: Engine.soft_nms runs on every batch's pre-NMS rows beside the model's hard NMS (and, where the model votes, is
     voted with the same settings) and its rows are scored by soft_evaluator.  recal (a VarCalibration) and recal_evaluator:
-    Engine.var_recal calibrates every batch's kept rows beside the raw ones and recal_evaluator scores them."""
+    Engine.var_recal calibrates every batch's kept rows beside the raw ones and recal_evaluator scores them.  score_cal (a
+    ScoreCalibration) and score_evaluator: likewise with Engine.score_recal."""
     images = 0
     for step, b in enumerate(feed):
         if max_batches is not None and step >= max_batches:
@@ -233,6 +256,9 @@ def score(model, feed, evaluator, seed=0, max_batches=None, points=None, vote=No
             vev.add(voted['rows'], res['count'][:, 0], b['boxes'], b['labels'], b['counts'])
         if recal_evaluator is not None:
             recal_evaluator.add(res.get('engine', model.engine).var_recal(res['rows'], recal), res['count'][:, 0], b['boxes'], b['labels'], b['counts'])
+        if score_evaluator is not None:
+            cal_rows = res.get('engine', model.engine).score_recal(res['rows'], res['count'], score_cal)['rows']
+            score_evaluator.add(cal_rows, res['count'][:, 0], b['boxes'], b['labels'], b['counts'])
         if soft_evaluator is not None:
             eng = res.get('engine', model.engine)
             sres = eng.soft_nms(res['boxes'], model.obj_idx, model.cls_start_idx, **({} if soft is True else dict(soft)))
@@ -332,14 +358,22 @@ def evaluate(config, model='bayesian'):
         recal = VarCalibration.load(cfg['var_recal'])
         recal.check(MODELS[cfg['model']], [len(dl.priors) for dl in m.det_layers])
         ev_recal = new_ev()
-    feed = dataset_utils._Feed(cfg, 'data', 'eval', device=m.engine.torch_device)
+    ev_score, score_cal = None, None
+    if cfg.get('score_recal_compare'):
+        from byolo.score_recal import ScoreCalibration
+        score_cal = ScoreCalibration.load(cfg['score_recal'])
+        score_cal.check(MODELS[cfg['model']], m.cls_cnt)
+        score_cal.warn_settings(getattr(m.engine, '_soft_nms', None), getattr(m.engine, '_var_recal', None))
+        ev_score = new_ev()
+    feed =dataset_utils._Feed(cfg, 'data', 'eval', device=m.engine.torch_device)
     try:
         t0 = time.time()
         points = []
         images = score(m, feed, ev, seed=int(cfg['seed']), max_batches=cfg['eval_batches'], points=points, vote=cfg['box_vote'],
                        vote_evaluator=ev_vote, sweep=sweep, soft=cfg.get('soft_nms'), soft_evaluator=ev_soft, recal=recal,
-                       recal_evaluator=ev_recal)
+                       recal_evaluator=ev_recal, score_cal=score_cal, score_evaluator=ev_score)
         metrics = ev.finish()
+        score_metrics = ev_score.finish() if ev_score is not None else None
         recal_metrics = ev_recal.finish() if ev_recal is not None else None
         soft_metrics = ev_soft.finish() if ev_soft is not None else None
         voted_metrics = ev_vote.finish() if ev_vote is not None else None
@@ -356,6 +390,12 @@ def evaluate(config, model='bayesian'):
             ev_soft.close()
         if ev_recal is not None:
             ev_recal.close()
+        if ev_score is not None:
+            ev_score.close()
+    if score_metrics is not None:
+        for c, v in zip(metrics['classes'], score_metrics['classes']):
+            logging.info('class {:3d}: raw rows AP {:.4f}, LAMR {:.4f}, ECE {:.4f}; score_recal rows AP {:.4f}, LAMR {:.4f}, ECE {:.4f}'.format(
+                c['class'], c['ap'], c['lamr'], c['ece'], v['ap'], v['lamr'], v['ece']))
     if recal_metrics is not None and 'localisation' in recal_metrics:
         from byolo import eval_loc
         for line in eval_loc.log_lines(recal_metrics['localisation']):
@@ -400,6 +440,9 @@ def evaluate(config, model='bayesian'):
     if recal_metrics is not None:                         # likewise: the raw rows' result beside the recalibrated rows'
         metrics = dict({k: v for k, v in metrics.items() if k not in recal_metrics}, raw={k: metrics[k] for k in recal_metrics},
                        var_recal=recal_metrics)
+    if score_metrics is not None:                         # likewise: the raw rows' result beside the score-recalibrated rows'
+        metrics = dict({k: v for k, v in metrics.items() if k not in score_metrics}, raw={k: metrics[k] for k in score_metrics},
+                       score_recal=score_metrics)
     if sweep:
         metrics['box_vote_sweep'] = [dict(r, settings=settings) for (settings, _), r in zip(sweep, sweep_metrics)]
     with open(os.path.join(out_path, 'metrics.json'), 'w') as f:

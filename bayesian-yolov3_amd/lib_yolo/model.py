@@ -83,6 +83,8 @@ class ModelBuilder:
         self.__soft_nms = opts.pop('soft_nms', None)
         # 'var_recal': a path | dict | byolo.recalibrate.VarCalibration: the variances recalibrated behind the decode (Engine.set_var_recal)
         self.__var_recal = opts.pop('var_recal', None)
+        # 'score_recal': a path | dict | byolo.score_recal.ScoreCalibration: the kept rows' score recalibrated behind the NMS (Engine.set_score_recal)
+        self.__score_recal = opts.pop('score_recal', None)
         self.engine = Engine(img_size=shape[1:], cls_cnt=cls_cnt, **opts)
         self.T = 1
 
@@ -117,6 +119,8 @@ class ModelBuilder:
             self.engine.set_box_vote(self.__box_vote)
         if self.__var_recal is not None:
             self.engine.set_var_recal(self.__var_recal)
+        if self.__score_recal is not None:
+            self.engine.set_score_recal(self.__score_recal)
         return Model(self.__layers, self.__det_layers, self.__cls_cnt, obj_idx, cls_start_idx, builder=self)
 
     def __update_layers(self, index, name, kind):

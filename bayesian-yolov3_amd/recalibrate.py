@@ -15,6 +15,16 @@ The config is that of evaluate.py; the keys of this entry point:
                  nobody has tuned on a real checkpoint
   recal_holdout  k: every k-th batch goes to a second evaluator that is NOT fitted on; the log shows `sigma_scale`, NLL and ENCE of
                  those batches before and after -- the out-of-sample figure (None: every batch is fitted on)
+
+`--what score` (default `var`: everything above) fits a SCORE recalibration instead (INTEGRATION.md "Score recalibration";
+byolo/score_recal.py, csrc/score_recal.hip) on every kept detection of any of the three models and writes
+`<out_path>_<step>/score_recal.json`, the file the config key / engine option `score_recal` takes.  Its keys:
+  score_recal_features  None (the model's default) or a list of 'logit', 'log_height', {'col': name, 'f': 'id' | 'log'}
+  score_recal_by        'all' (default) | 'class'
+  score_recal_l2        the ridge on the standardised weights (1.0)
+  score_recal_min_n     groups with fewer records, or with one label only, inherit class -> all -> identity (200)
+  recal_holdout         as above; the log shows ECE, Brier, AP and LAMR per class of the held-out batches before and after
+The defaults are starting values that nobody has tuned on a real checkpoint.
 """
 import argparse
 import json
@@ -124,14 +134,121 @@ def recalibrate(config, model='bayesian'):
     return {'path': path, 'calibration': cal, 'images': images, 'holdout': holdout}
 
 
+def check_score_config(config, model='bayesian'):
+    """evaluate.check_config plus the score_recal_* keys of `--what score`; raises ValueError on what cannot be fitted."""
+    from byolo import score_recal as sr
+    for k in ('score_recal', 'score_recal_compare', 'var_recal_compare', 'box_vote', 'box_vote_compare', 'soft_nms_compare'):
+        if config.get(k):
+            raise ValueError('recalibrate: {} belongs to evaluate.py; the fit runs on the rows of the model as it is configured'.format(k))
+    cfg = _evaluate.check_config(config, model)                # (soft_nms and var_recal stay: the file records what it was fitted under)
+    cfg.setdefault('score_recal_features', None)
+    cfg.setdefault('score_recal_by', 'all')
+    cfg.setdefault('score_recal_l2', sr.DEFAULT_L2)
+    cfg.setdefault('score_recal_min_n', sr.DEFAULT_MIN_N)
+    cfg.setdefault('recal_holdout', None)
+    try:
+        sr.ScoreCalibration(MODELS[model], int(cfg['cls_cnt']), cfg['score_recal_features'], cfg['score_recal_by'], l2=cfg['score_recal_l2'],
+                            min_n=cfg['score_recal_min_n'])
+    except ValueError as e:
+        raise ValueError(str(e).replace('score_recal: ', 'score_recal_'))
+    k = cfg['recal_holdout']
+    if k is not None and (isinstance(k, bool) or not isinstance(k, int) or k < 2):
+        raise ValueError('recal_holdout is None or an integer >= 2 (every k-th batch is held out), not {!r}'.format(k))
+    return cfg
+
+
+def score_holdout_lines(before, after):
+    """The out-of-sample figures per class, before -> after: the line that answers "do the uncertainties help"."""
+    return ['holdout score class {:3d}: n_det {:6d}, ECE {:.4f} -> {:.4f}, Brier {:.4f} -> {:.4f}, AP {:.4f} -> {:.4f}, LAMR {:.4f} -> {:.4f}'.format(
+        b['class'], b['n_det'], b['ece'], a['ece'], b['brier'], a['brier'], b['ap'], a['ap'], b['lamr'], a['lamr'])
+        for b, a in zip(before['classes'], after['classes'])]
+
+
+def _brier(evaluator, cls_cnt):
+    """Mean (score - tp)^2 per class over an evaluator's records (float64, ascending table order)."""
+    rec = evaluator.records()
+    out = []
+    for c in range(cls_cnt):
+        m = rec['cls'] == c
+        d = rec['score'][m].astype(np.float64) - rec['tp'][m].astype(np.float64)
+        out.append(float(np.cumsum(d * d)[-1] / len(d)) if len(d) else float('nan'))
+    return out
+
+
+def recalibrate_score(config, model='bayesian'):
+    """`--what score`: fits a score recalibration (byolo/score_recal.py) and writes <out_path>_<step>/score_recal.json; returns
+    {'path', 'calibration' (the ScoreCalibration), 'images', 'holdout' ({'before', 'after'}: the result dicts of the held-out
+    batches with 'brier' added per class, or None)}."""
+    from byolo import inference as _inf, score_recal as sr
+    from byolo.evaluate import Evaluator
+    from lib_yolo import dataset_utils
+    cfg = check_score_config(config, model)
+    logging.info(json.dumps(cfg, indent=4, default=lambda x: str(x)))
+    logging.info('----- START -----')
+    start = time.time()
+    m, checkpoint = _evaluate.build_model(cfg)
+    out_path = '{}_{}'.format(cfg['out_path'], _inf.step_of(checkpoint))
+    os.makedirs(out_path)
+    kw = dict(iou_thresh=cfg['iou_thresh'], min_score=cfg['min_score'], capacity=cfg['eval_capacity'], device=m.engine.torch_device, loc=False)
+    k = cfg['recal_holdout']
+    ev_fit = Evaluator(sr.eval_layout(m), **kw)                # its records also carry ymin / ymax, which 'log_height' reads
+    ev_before, ev_after = (Evaluator(m, **kw), Evaluator(m, **kw)) if k else (None, None)
+    held = []
+    feed = dataset_utils._Feed(cfg, 'data', 'eval', device=m.engine.torch_device)
+    try:
+        images = 0
+        for step, b in enumerate(feed):
+            if cfg['eval_batches'] is not None and step >= cfg['eval_batches']:
+                break
+            res = m.run(b['img'], seed=int(cfg['seed']) + step, want_boxes=False)
+            args = (res['rows'], res['count'], b['boxes'], b['labels'], b['counts'])
+            if k and step % k == k - 1:
+                ev_before.add(args[0], args[1][:, 0], *args[2:])
+                held.append(args[:2] + tuple(x.clone() if hasattr(x, 'clone') else np.array(x) for x in args[2:]))
+            else:
+                ev_fit.add(args[0], args[1][:, 0], *args[2:])
+            images += int(b['img'].shape[0])
+        cal = sr.fit(ev_fit, cfg['score_recal_features'], cfg['score_recal_by'], float(cfg['score_recal_l2']), int(cfg['score_recal_min_n']),
+                     fitted_under=sr.fitted_under(m.engine))
+        holdout = None
+        if k:
+            for rows, count, gb, gl, gc in held:
+                ev_after.add(m.engine.score_recal(rows, count, cal)['rows'], count[:, 0], gb, gl, gc)
+            holdout = {'before': ev_before.finish(), 'after': ev_after.finish()}
+            for name, e in (('before', ev_before), ('after', ev_after)):
+                for c, br in zip(holdout[name]['classes'], _brier(e, m.cls_cnt)):
+                    c['brier'] = br
+    finally:
+        feed.close()
+        for e in (ev_fit, ev_before, ev_after):
+            if e is not None:
+                e.close()
+    for line in cal.log_lines():
+        logging.info(line)
+    if holdout is not None:
+        for line in score_holdout_lines(holdout['before'], holdout['after']):
+            logging.info(line)
+    path = os.path.join(out_path, 'score_recal.json')
+    cal.save(path)
+    logging.info('wrote {} ({} images, {} of them held out)'.format(path, images, sum(int(h[0].shape[0]) for h in held)))
+    elapsed = int(time.time() - start)
+    logging.info('----- FINISHED in {:02d}:{:02d}:{:02d} -----'.format(elapsed // 3600, (elapsed // 60) % 60, elapsed % 60))
+    m.engine.close()
+    return {'path': path, 'calibration': cal, 'images': images, 'holdout': holdout}
+
+
 def main(argv=None):
     from lib_yolo import yolov3
     ap = argparse.ArgumentParser(description=__doc__.split('\n\n')[0])
-    ap.add_argument('--model', choices=sorted(k for k in MODELS if k != 'standard'), default='bayesian')
+    ap.add_argument('--what', choices=['var', 'score'], default='var',
+                    help="var: the variance recalibration (var_recal.json); score: the score recalibration (score_recal.json, config keys score_recal_*)")
+    ap.add_argument('--model', choices=sorted(MODELS), default='bayesian')
     args = ap.parse_args(argv)
+    if args.what == 'var' and args.model == 'standard':
+        ap.error('--what var: the rows of the standard model carry no variances')
     config = {
         'checkpoint_path': './checkpoints',  # edit
-        'run_id': {'aleatoric': 'aleatoric', 'bayesian': 'epi_ale'}[args.model],  # edit
+        'run_id': {'standard': 'yolov3', 'aleatoric': 'aleatoric', 'bayesian': 'epi_ale'}[args.model],  # edit
         'step': 'last',  # edit: int or 'last'
         'full_img_size': [1024, 1920, 3],  # edit if not ECP dataset
         'cls_cnt': 2,  # edit if not ECP dataset
@@ -154,7 +271,11 @@ def main(argv=None):
     }
     config['data']['file_pattern'] = os.path.join(os.path.expandvars(config['data']['path']), config['data']['file_pattern'])
     config['out_path'] = os.path.join('./recalibration', config['run_id'])  # edit
-    recalibrate(config, args.model)
+    if args.what == 'score':
+        # the defaults of byolo/score_recal.py (features per model, by 'all', l2 1.0, min_n 200) are starting values, untuned
+        recalibrate_score({k: v for k, v in config.items() if k not in ('recal_by', 'recal_method', 'recal_min_n')}, args.model)
+    else:
+        recalibrate(config, args.model)
 
 
 if __name__ == '__main__':

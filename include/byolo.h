@@ -859,6 +859,74 @@ BYOLO_API size_t byolo_var_recal_fit_workspace_bytes(int64_t n);
 BYOLO_API int32_t byolo_var_recal_fit(const double* d_r, const double* d_v, const int64_t* d_seg, int32_t n_seg, int64_t n,
                                       int32_t method, double* d_out, void* d_ws, size_t ws_bytes, void* stream);
 
+/* ---- score recalibration (logistic map: Platt 1999, Guo et al. 2017; box-dependent covariates: Kueppers et al. 2020; no counterpart
+ * in the reference; csrc/score_recal.hip; INTEGRATION.md "Score recalibration" has the definitions in full,
+ * tests/_score_recal_ref.py restates them) ------------------------------------------------------------------------------------------
+ * A calibration is a table w[g][k] of float64 weights over K features (2 <= K <= BYOLO_SCORE_RECAL_MAX_K) per group g: ONE group
+ * (by = BYOLO_SCORE_RECAL_BY_ALL) or one per class (_BY_CLASS, cls_cnt <= BYOLO_SCORE_RECAL_MAX_GROUPS).  The calibrated score of a
+ * kept row is s' = 1 / (1 + exp(-(w[g] . x))), float64, the dot product in ascending k.
+ *   class, s   the first index of the largest class score (a NaN wins); s = obj * cls[class], one float32 multiply -- the
+ *              evaluation's rule.  kind says where obj and the classes are (standard 4 / 5, aleatoric 9 / 11, Bayesian 14 / 17).
+ *   features   feat_kind[0] is _F_BIAS (1), feat_kind[1] is _F_LOGIT: log(t / (1 - t)), t = min(max(s, 1e-7), 1 - 1e-7).
+ *              _F_LOG_HEIGHT: log(h), h = col 2 - col 0 in float32, widened; 1e-6 where h is not finite or not > 1e-6.
+ *              _F_COL_ID: the row's column feat_col[k]; 0 where it is not finite.  _F_COL_LOG: log(u) of that column; u = 1e-12
+ *              where it is not finite or not > 1e-12.
+ *   writes     score = float32(s'), and obj = float32(float64(score) / float64(cls[class])) so that obj * cls[class] downstream is
+ *              the calibrated score within one float32 rounding.  The row is left alone and score = s where s is NaN, where
+ *              cls[class] is not finite and > 0, and where the group's weights are the IDENTITY (0, 1, 0, ...): no exp, no log.
+ * Every other column keeps its bits.  score [B, cap] is 0 in the padding (k >= count).
+ * byolo_score_recal_apply: the stand-alone stage, handle-less (errors: byolo_last_error(NULL)) on kept rows d_rows_in [B, cap, D]
+ * and d_count [B, 2] (the first word of each pair counts the kept rows, as byolo_forward writes it); d_rows_out must not overlap
+ * d_rows_in; d_table: BYOLO_SCORE_RECAL_TABLE_BYTES bytes of device memory, 8-byte aligned, holding what byolo_score_recal_table
+ * wrote to a host buffer of that size, copied to the device by the caller ONCE per table.  Refused with BYOLO_ERR_ARG, the field
+ * named: a wrong struct_bytes, an unknown kind / by, cls_cnt outside the groups, K outside 2 .. 8, feat_kind[0] / [1] not bias /
+ * logit, a feature column outside the row, D != the kind's row length, a weight that is not finite.
+ * byolo_set_score_recal(h, cfg): byolo_forward applies the table in place on d_rows behind the NMS or soft-NMS and in front of box
+ * voting, reading d_count on the device (cfg NULL: off, the default; with it off every output is what it was without this entry
+ * point).  byolo_score_recal_scores then copies score [B, cap] of the last such forward, on `stream`.  A T-shard forward runs
+ * no NMS: call byolo_score_recal_apply behind the caller's own.
+ * byolo_score_recal_features: d_x [n, K] float64 of cfg's features from n float32 rows d_src of `stride` floats whose score is
+ * the column score_col (records of an evaluation rather than kept rows); cols [K] on the host: the column of d_src of every
+ * _F_COL_* feature; ymin_col / ymax_col: the two of _F_LOG_HEIGHT.
+ * Fit (byolo_score_recal_fit): d_x [n, K] and d_y [n] (float64, 0 / 1), grouped into n_seg consecutive segments d_seg[s] ..
+ * d_seg[s + 1]; one workgroup per segment standardises the features (population mean and standard deviation; a feature whose
+ * standard deviation is 0 or not finite is dropped: weight 0), runs Newton on the ridge-penalised mean NLL (l2 >= 0, not on the
+ * bias; Cholesky; the step halved at most 30 times while the loss does not fall; at most 50 iterations; converged at a step below
+ * 1e-10) and folds the weights back, inside the one launch.  Every sum is the FIXED SUM of byolo_var_recal_fit.  d_out
+ * [n_seg][BYOLO_SCORE_RECAL_FIT_WORDS] float64: n, positives, status (_FIT; _IDENTITY: n < min_n, no positive or no negative;
+ * _EMPTY), iterations, converged, NLL before, NLL after, Brier before, Brier after, the last step, the dropped features as a bit
+ * mask, one spare word, then w[8], mean[8], sd[8].  d_ws >= byolo_score_recal_fit_workspace_bytes(n, K), 8-byte aligned. */
+#define BYOLO_SCORE_RECAL_MAX_K 8
+#define BYOLO_SCORE_RECAL_MAX_GROUPS 80
+#define BYOLO_SCORE_RECAL_TABLE_BYTES 5120
+#define BYOLO_SCORE_RECAL_FIT_WORDS 36
+enum { BYOLO_SCORE_RECAL_BY_ALL = 0, BYOLO_SCORE_RECAL_BY_CLASS = 1 };
+enum { BYOLO_SCORE_RECAL_F_BIAS = 0, BYOLO_SCORE_RECAL_F_LOGIT = 1, BYOLO_SCORE_RECAL_F_LOG_HEIGHT = 2, BYOLO_SCORE_RECAL_F_COL_ID = 3,
+       BYOLO_SCORE_RECAL_F_COL_LOG = 4 };
+enum { BYOLO_SCORE_RECAL_FIT = 0, BYOLO_SCORE_RECAL_IDENTITY = 1, BYOLO_SCORE_RECAL_EMPTY = 2 };
+typedef struct byolo_score_recal_cfg {
+    int32_t struct_bytes;          /* sizeof(byolo_score_recal_cfg) of the caller's header: a mismatch is BYOLO_ERR_ARG */
+    int32_t kind;                  /* BYOLO_DET_STANDARD / _ALEATORIC / _EPISTEMIC: the layout of the rows */
+    int32_t cls_cnt;
+    int32_t by;                    /* BYOLO_SCORE_RECAL_BY_ALL / _BY_CLASS */
+    int32_t K;
+    int32_t feat_kind[BYOLO_SCORE_RECAL_MAX_K];   /* BYOLO_SCORE_RECAL_F_* */
+    int32_t feat_col[BYOLO_SCORE_RECAL_MAX_K];    /* the row's column of a _F_COL_* feature */
+    int32_t reserved;
+    double w[BYOLO_SCORE_RECAL_MAX_GROUPS][BYOLO_SCORE_RECAL_MAX_K];
+} byolo_score_recal_cfg;
+BYOLO_API int32_t byolo_score_recal_table(const byolo_score_recal_cfg* cfg, double* h_table);
+BYOLO_API int32_t byolo_score_recal_apply(const byolo_score_recal_cfg* cfg, const float* d_rows_in, const int32_t* d_count, int32_t B,
+                                          int32_t cap, int32_t D, float* d_rows_out, float* d_score, const void* d_table, void* stream);
+BYOLO_API int32_t byolo_set_score_recal(byolo_t* h, const byolo_score_recal_cfg* cfg);
+BYOLO_API int32_t byolo_score_recal_scores(byolo_t* h, float* d_score, int32_t B, int32_t cap, void* stream);
+BYOLO_API int32_t byolo_score_recal_features(const byolo_score_recal_cfg* cfg, const float* d_src, int64_t n, int32_t stride,
+                                             int32_t score_col, int32_t ymin_col, int32_t ymax_col, const int32_t* cols, double* d_x,
+                                             void* stream);
+BYOLO_API size_t byolo_score_recal_fit_workspace_bytes(int64_t n, int32_t K);
+BYOLO_API int32_t byolo_score_recal_fit(const double* d_x, const double* d_y, const int64_t* d_seg, int32_t n_seg, int64_t n,
+                                        int32_t K, double l2, int64_t min_n, double* d_out, void* d_ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
