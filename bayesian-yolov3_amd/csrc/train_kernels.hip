@@ -57,7 +57,9 @@ __device__ __forceinline__ float logit_tf(float x) { return -logf((1.f / x) - 1.
 // kept in registers while the thread walks the image's boxes in order, like the reference's sequential tf.while_loop:
 //   encode_gt_max_kernel   tf.reduce_max(iou) of every box over ALL prior boxes of all layers -> best[image][box] (wave maximum,
 //                          then one atomic maximum per wave and box on the IoU's bit pattern: IoUs are >= 0, so unsigned order =
-//                          float order; NaN never wins, like a maximum over numbers)
+//                          float order; NaN never wins, like a maximum over numbers.  oracle/train_ref.py's `np.max` PROPAGATES a
+//                          NaN IoU instead -- both are readings of an unspecified tf.reduce_max; the two differ there and no test
+//                          pins either: the suites feed finite boxes with prior_area + box_area != 0)
 //   encode_gt_assign_kernel the loop body (tfdata.py:109-149) with its loop variables in registers, one store at the end
 constexpr int ENC_THREADS = 256;
 

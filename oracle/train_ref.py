@@ -96,6 +96,8 @@ def encode_boxes(bboxes, labels, layers, ign_thresh, dtype=np.float32):
         dy = pd["lh"] * (y[i] - pd["cy"])
         obj_mask = (dx >= 0) & (dx <= 1) & (dy >= 0) & (dy <= 1)
         iou = calc_iou(bboxes[i], pd)
+        # np.max propagates a NaN IoU (0 / 0: prior_area + box_area == 0), csrc/train_kernels.hip's maximum never lets NaN win: the two
+        # differ there, tf.reduce_max leaves it unspecified, and no test pins either
         best = iou >= np.max(iou)
         obj_mask = best & obj_mask
         ign_mask = iou >= dtype(ign_thresh)
@@ -131,9 +133,11 @@ def split_detection(raw, cls_cnt, aleatoric):
             "cls": r[..., 10:10 + cls_cnt], "log_cls_stddev": r[..., 10 + cls_cnt:10 + 2 * cls_cnt]}
 
 
-def loss(raw, gt, cls_cnt, aleatoric, aleatoric_loss, dtype=np.float64, want_grad=False):
+def loss(raw, gt, cls_cnt, aleatoric, aleatoric_loss, dtype=np.float64, want_grad=False, want_abs=False):
     """lib_yolo/layers.py:126-188 for one detection layer.  raw [b, h, w, F]; gt: loc [b, h, w, 3, 4], obj, ign [b, h, w, 3],
-    cls [b, h, w, 3] int.  Returns {'loc', 'obj', 'cls'} (and 'grad' [b, h, w, F] = d(loc + obj + cls) / d raw)."""
+    cls [b, h, w, 3] int.  Returns {'loc', 'obj', 'cls'} (and 'grad' [b, h, w, F] = d(loc + obj + cls) / d raw; and 'abs': the same
+    three sums over the ABSOLUTE values of the per-element terms, the scale of a float32 implementation's rounding error where
+    log-variance terms of both signs cancel in 'loc')."""
     raw = np.asarray(raw, dtype)
     det = split_detection(raw, cls_cnt, aleatoric)
     g_loc = np.asarray(gt["loc"], dtype); g_obj = np.asarray(gt["obj"], dtype); g_ign = np.asarray(gt["ign"], dtype)
@@ -160,6 +164,9 @@ def loss(raw, gt, cls_cnt, aleatoric, aleatoric_loss, dtype=np.float64, want_gra
     cls_loss = (lse - picked)[..., 0]
     cls_all = np.sum(cls_loss * g_obj) / bs
     out = {"loc": loc_all, "obj": obj_all, "cls": cls_all}
+    if want_abs:
+        out["abs"] = {"loc": np.sum(np.abs(loc_loss)) / (dtype(2) * bs), "obj": np.sum(np.abs(obj_loss * g_ign)) / bs,
+                      "cls": np.sum(np.abs(cls_loss * g_obj)) / bs}
     if want_grad:
         b, h, w, F = raw.shape
         blk = F // 3
