@@ -40,9 +40,8 @@ class Engine:
         self._box_vote = None            # the settings set_box_vote() switched variance voting on with (None: off)
         self._soft_nms = None            # the settings set_soft_nms() switched the soft-NMS on with (None: off, the hard NMS)
         self._var_recal = None           # the VarCalibration set_var_recal() switched variance recalibration on with (None: off)
-        self._var_recal_table = None     # var_recal(): (packed table bytes, device, its copy on that device) of the last call
         self._score_recal = None         # the ScoreCalibration set_score_recal() switched score recalibration on with (None: off)
-        self._score_recal_table = None   # score_recal(): as _var_recal_table
+        self._recal_tables = {}          # var_recal() / score_recal(): (packed table bytes, device, its copy on that device) of the stage's last call
 
     # ---- arithmetic of the convolution stack (include/byolo.h: BYOLO_PREC_*) ----------------------------
     @property
@@ -530,6 +529,36 @@ class Engine:
     # ---- variance recalibration (include/byolo.h "variance recalibration"; byolo/recalibrate.py) ----------------
     _VARIANT_OF_KIND = {_lib.DET_STANDARD: "yolov3", _lib.DET_ALEATORIC: "yolov3_aleatoric", _lib.DET_EPISTEMIC: "bayesian_yolov3_aleatoric"}
 
+    def _set_recal(self, name, cls, cal, check_model):
+        """set_var_recal / set_score_recal (`name` without the set_): None / False switches the stage off; anything else is coerced to
+        a `cls`, checked against the detection layers by check_model(cal, dets) and switched on.  A twin follows."""
+        lib_set = getattr(lib, "byolo_set_" + name)
+        if cal is None or cal is False:
+            check(self._h, lib_set(self._h, None))
+            cal = None
+        else:
+            cal = cls.coerce(cal)
+            dets = [a for n, a in self._graph if n == "add_detection"]
+            if not dets:
+                raise ValueError("set_%s: add the detection layers first" % name)
+            check_model(cal, dets)
+            cfg = cal.cfg()
+            check(self._h, lib_set(self._h, ctypes.byref(cfg)))
+        setattr(self, "_" + name, cal)
+        if self._twin is not None:
+            getattr(self._twin, "set_" + name)(cal)
+
+    def _recal_table(self, name, cfg, n_bytes, device):
+        """The device copy of cfg's packed table (byolo_<name>_table) for var_recal() / score_recal(): copied when the bytes or the
+        device differ from the stage's last call."""
+        host = np.empty(n_bytes // 8, dtype=np.float64)
+        check(None, getattr(lib, "byolo_%s_table" % name)(ctypes.byref(cfg), ctypes.c_void_p(host.ctypes.data)))
+        key = host.tobytes()
+        last = self._recal_tables.get(name)
+        if last is None or last[0] != key or last[1] != device:
+            last = self._recal_tables[name] = (key, device, _torch().from_numpy(host).to(device))      # (pageable memory: the copy is complete on return)
+        return last[2]
+
     def set_var_recal(self, cal=None):
         """Variance recalibration inside forward(): a byolo.recalibrate.VarCalibration, the path of a saved one or its dict switches
         it on -- the table is applied in place on the pre-NMS rows right behind the decode, so 'boxes', 'rows', the soft-NMS and
@@ -537,20 +566,7 @@ class Engine:
         forward() is then what it was).  ValueError naming the field when the calibration was fitted for another variant or
         geometry.  A twin made before the call follows it."""
         from .recalibrate import VarCalibration
-        if cal is None or cal is False:
-            check(self._h, lib.byolo_set_var_recal(self._h, None))
-            self._var_recal = None
-        else:
-            cal = VarCalibration.coerce(cal)
-            dets = [a for n, a in self._graph if n == "add_detection"]
-            if not dets:
-                raise ValueError("set_var_recal: add the detection layers first")
-            cal.check(self._VARIANT_OF_KIND[int(dets[-1][1])], [len(a[2]) for a in dets])
-            cfg = cal.cfg()
-            check(self._h, lib.byolo_set_var_recal(self._h, ctypes.byref(cfg)))
-            self._var_recal = cal
-        if self._twin is not None:
-            self._twin.set_var_recal(self._var_recal)
+        self._set_recal("var_recal", VarCalibration, cal, lambda c, dets: c.check(self._VARIANT_OF_KIND[int(dets[-1][1])], [len(a[2]) for a in dets]))
 
     def var_recal(self, rows, cal):
         """The recalibration stage by itself (byolo_var_recal_apply) on rows [..., D] of this engine's class count -- pre-NMS boxes
@@ -569,12 +585,7 @@ class Engine:
         if n == 0:
             return out
         cfg = cal.cfg()
-        host = np.empty(_lib.VAR_RECAL_TABLE_BYTES // 8, dtype=np.float64)
-        check(None, lib.byolo_var_recal_table(ctypes.byref(cfg), ctypes.c_void_p(host.ctypes.data)))
-        key = host.tobytes()
-        if self._var_recal_table is None or self._var_recal_table[0] != key or self._var_recal_table[1] != rows.device:
-            self._var_recal_table = (key, rows.device, torch.from_numpy(host).to(rows.device))      # (pageable memory: the copy is complete on return)
-        tab = self._var_recal_table[2]
+        tab = self._recal_table("var_recal", cfg, _lib.VAR_RECAL_TABLE_BYTES, rows.device)
         stream = torch.cuda.current_stream(rows.device).cuda_stream
         rc = lib.byolo_var_recal_apply(ctypes.byref(cfg), ctypes.c_void_p(rows.data_ptr()), n, D, ctypes.c_void_p(out.data_ptr()),
                                        ctypes.c_void_p(tab.data_ptr()), ctypes.c_void_p(stream))
@@ -590,21 +601,11 @@ class Engine:
         the field when the calibration was fitted for another variant or class count; one warning line when it was fitted under
         other soft_nms / var_recal settings than this engine runs.  A twin made before the call follows it."""
         from .score_recal import ScoreCalibration
-        if cal is None or cal is False:
-            check(self._h, lib.byolo_set_score_recal(self._h, None))
-            self._score_recal = None
-        else:
-            cal = ScoreCalibration.coerce(cal)
-            dets = [a for n, a in self._graph if n == "add_detection"]
-            if not dets:
-                raise ValueError("set_score_recal: add the detection layers first")
-            cal.check(self._VARIANT_OF_KIND[int(dets[-1][1])], self.cfg.cls_cnt)
-            cal.warn_settings(self._soft_nms, self._var_recal)
-            cfg = cal.cfg()
-            check(self._h, lib.byolo_set_score_recal(self._h, ctypes.byref(cfg)))
-            self._score_recal = cal
-        if self._twin is not None:
-            self._twin.set_score_recal(self._score_recal)
+
+        def check_model(c, dets):
+            c.check(self._VARIANT_OF_KIND[int(dets[-1][1])], self.cfg.cls_cnt)
+            c.warn_settings(self._soft_nms, self._var_recal)
+        self._set_recal("score_recal", ScoreCalibration, cal, check_model)
 
     def score_recal(self, rows, count, cal):
         """The stage by itself (byolo_score_recal_apply) on kept rows [B, cap, D] and count [B, 2] as forward() returns them: returns
@@ -625,12 +626,7 @@ class Engine:
         if B * cap == 0:
             return dict(rows=out, score=score)
         cfg = cal.cfg()
-        host = np.empty(_lib.SCORE_RECAL_TABLE_BYTES // 8, dtype=np.float64)
-        check(None, lib.byolo_score_recal_table(ctypes.byref(cfg), ctypes.c_void_p(host.ctypes.data)))
-        key = host.tobytes()
-        if self._score_recal_table is None or self._score_recal_table[0] != key or self._score_recal_table[1] != rows.device:
-            self._score_recal_table = (key, rows.device, torch.from_numpy(host).to(rows.device))      # (pageable memory: the copy is complete on return)
-        tab = self._score_recal_table[2]
+        tab = self._recal_table("score_recal", cfg, _lib.SCORE_RECAL_TABLE_BYTES, rows.device)
         stream = torch.cuda.current_stream(rows.device).cuda_stream
         p = lambda t: ctypes.c_void_p(t.data_ptr())
         check(None, lib.byolo_score_recal_apply(ctypes.byref(cfg), p(rows), p(count), B, cap, D, p(out), p(score), p(tab), ctypes.c_void_p(stream)))

@@ -8,13 +8,13 @@ INTEGRATION.md "Variance recalibration" has the definitions; tests/_var_recal_re
 
 "calibrate" elsewhere in this package means BN calibration (Engine.calibrate_bn); this module says "recalibrate"."""
 import ctypes
-import json
 import math
 
 import numpy as np
 
 from . import _lib, eval_loc
-from ._lib import ByoloError, lib
+from ._calibration import Calibration, check_min_n, segmented_fit
+from ._lib import lib
 
 VARIANTS = {'yolov3_aleatoric': _lib.DET_ALEATORIC, 'bayesian_yolov3_aleatoric': _lib.DET_EPISTEMIC}
 TARGETS = {'ale': _lib.VAR_RECAL_ALE, 'epi': _lib.VAR_RECAL_EPI, 'total': _lib.VAR_RECAL_TOTAL}
@@ -41,13 +41,14 @@ def _check_settings(variant, target, by, method, min_n=None):
         raise ValueError('var_recal: by is one of %s, not %r' % (list(BYS), by))
     if method not in METHODS:
         raise ValueError('var_recal: method is one of %s, not %r' % (sorted(METHODS), method))
-    if min_n is not None and (isinstance(min_n, bool) or not isinstance(min_n, (int, np.integer)) or min_n < 1):
-        raise ValueError('var_recal: min_n is an integer >= 1, not %r' % (min_n,))
+    if min_n is not None:
+        check_min_n('var_recal', min_n)
 
 
-class VarCalibration:
+class VarCalibration(Calibration):
     """The table cal.a[l][p][c], cal.b[l][p][c] (float64; c over x, y, w, h) of one model geometry, with what it was fitted for:
     variant, n_priors (one entry per detection layer), target ('ale' | 'epi' | 'total'), by, method and the per-group report."""
+    FORMAT, PREFIX, REQUIRED = FORMAT, 'var_recal', ('variant', 'n_priors', 'target', 'by', 'method', 'a', 'b')
 
     def __init__(self, variant, n_priors, target=None, by='prior', method='scale', a=None, b=None, report=None, min_n=None):
         target = default_target(variant) if target is None else target
@@ -107,44 +108,16 @@ class VarCalibration:
                     c.a[l][k][i], c.b[l][k][i] = self.a[l][k][i], self.b[l][k][i]
         return c
 
-    # ---- JSON: Python writes a float as its repr, which reads back to the same bits -------------------------------------------------
-    def to_json(self):
-        clean = lambda v: None if isinstance(v, float) and not math.isfinite(v) else v
-        return json.dumps({'format': FORMAT, 'version': 1, 'variant': self.variant, 'n_layers': len(self.n_priors), 'n_priors': self.n_priors,
-                           'target': self.target, 'by': self.by, 'method': self.method, 'min_n': self.min_n, 'a': self.a, 'b': self.b,
-                           'report': [{k: clean(v) for k, v in e.items()} for e in self.report]}, indent=1, allow_nan=False)
+    # ---- the file (Calibration) -------------------------------------------------------------------------------------------------
+    def _fields(self):
+        return {'variant': self.variant, 'n_layers': len(self.n_priors), 'n_priors': self.n_priors, 'target': self.target, 'by': self.by,
+                'method': self.method, 'min_n': self.min_n, 'a': self.a, 'b': self.b}
 
     @classmethod
-    def from_json(cls, text):
-        d = json.loads(text)
-        if not isinstance(d, dict) or d.get('format') != FORMAT:
-            raise ValueError('var_recal: format: not a %s file' % FORMAT)
-        for k in ('variant', 'n_priors', 'target', 'by', 'method', 'a', 'b'):
-            if k not in d:
-                raise ValueError('var_recal: the file has no %r' % k)
+    def _from_dict(cls, d):
         if 'n_layers' in d and d['n_layers'] != len(d['n_priors']):
             raise ValueError('var_recal: n_layers %r does not match n_priors %r' % (d['n_layers'], d['n_priors']))
         return cls(d['variant'], d['n_priors'], d['target'], d['by'], d['method'], d['a'], d['b'], d.get('report'), d.get('min_n'))
-
-    def save(self, path):
-        with open(path, 'w') as f:
-            f.write(self.to_json() + '\n')
-
-    @classmethod
-    def load(cls, path):
-        with open(path) as f:
-            return cls.from_json(f.read())
-
-    @classmethod
-    def coerce(cls, cal):
-        """A VarCalibration from one, from a path, or from the dict of to_json()."""
-        if isinstance(cal, cls):
-            return cal
-        if isinstance(cal, dict):
-            return cls.from_json(json.dumps(cal))
-        if isinstance(cal, (str, bytes)) or hasattr(cal, '__fspath__'):
-            return cls.load(cal)
-        raise ValueError('var_recal: a VarCalibration, a path or a dict, not %r' % (type(cal).__name__,))
 
     def log_lines(self):
         """One line per group and coordinate of the report."""
@@ -166,29 +139,13 @@ def fit_arrays(r, v, group, n_groups, method='scale', min_n=DEFAULT_MIN_N):
     import torch
     if method not in METHODS:
         raise ValueError('var_recal: method is one of %s, not %r' % (sorted(METHODS), method))
-    if isinstance(min_n, bool) or not isinstance(min_n, (int, np.integer)) or min_n < 1:
-        raise ValueError('var_recal: min_n is an integer >= 1, not %r' % (min_n,))
-    n_groups = int(n_groups)
+    check_min_n('var_recal', min_n)
     assert r.is_cuda and v.is_cuda and group.is_cuda and r.dtype == torch.float64 and v.dtype == torch.float64
-    assert r.dim() == 1 and r.shape == v.shape == group.shape and n_groups >= 1
-    n = int(r.numel())
-    dev = r.device
-    g = group.to(torch.int64)
-    order = torch.sort(g, stable=True)[1]
-    rs, vs = r[order].contiguous(), v[order].contiguous()
-    seg = torch.zeros(n_groups + 1, dtype=torch.int64, device=dev)
-    if n:
-        seg[1:] = torch.cumsum(torch.bincount(g, minlength=n_groups)[:n_groups], 0)
-    out = torch.empty((n_groups, _lib.VAR_RECAL_FIT_WORDS), dtype=torch.float64, device=dev)
+    assert r.dim() == 1 and r.shape == v.shape == group.shape and int(n_groups) >= 1
+    n, n_groups = int(r.numel()), int(n_groups)
     wsb = int(lib.byolo_var_recal_fit_workspace_bytes(n))
-    ws = torch.empty(max(wsb // 8, 1), dtype=torch.float64, device=dev)
-    p = lambda t: ctypes.c_void_p(t.data_ptr())
-    rc = lib.byolo_var_recal_fit(p(rs), p(vs), p(seg), n_groups, n, METHODS[method], p(out), p(ws), wsb,
-                                 ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc < 0:
-        msg = lib.byolo_last_error(None)
-        raise ByoloError(rc, msg.decode('utf-8', 'replace') if msg else '?')
-    o = out.cpu().numpy()                                          # the host wait
+    o = segmented_fit([r, v], group, n_groups, _lib.VAR_RECAL_FIT_WORDS, wsb, lambda cols, seg, out, ws, stream: lib.byolo_var_recal_fit(
+        cols[0], cols[1], seg, n_groups, n, METHODS[method], out, ws, wsb, stream))
     return dict(n=o[:, 0].astype(np.int64), a=o[:, 1].copy(), b=o[:, 2].copy(), mean_z2_before=o[:, 3].copy(), nll_before=o[:, 4].copy(),
                 nll_after=o[:, 5].copy(), iterations=o[:, 6].astype(np.int64), status=o[:, 7].astype(np.int64), converged=o[:, 8] != 0,
                 enough=o[:, 0] >= min_n)

@@ -18,7 +18,8 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import ByoloError, lib
+from ._calibration import Calibration, check_min_n, raise_last, segmented_fit
+from ._lib import lib
 
 VARIANTS = {'yolov3': _lib.DET_STANDARD, 'yolov3_aleatoric': _lib.DET_ALEATORIC, 'bayesian_yolov3_aleatoric': _lib.DET_EPISTEMIC}
 BYS = {'all': _lib.SCORE_RECAL_BY_ALL, 'class': _lib.SCORE_RECAL_BY_CLASS}
@@ -77,14 +78,15 @@ def _check_settings(cls_cnt, by, l2=None, min_n=None):
         raise ValueError("score_recal: by = 'class' with cls_cnt %d: at most %d groups" % (cls_cnt, _lib.SCORE_RECAL_MAX_GROUPS))
     if l2 is not None and not (isinstance(l2, (int, float, np.floating, np.integer)) and not isinstance(l2, bool) and l2 >= 0 and math.isfinite(l2)):
         raise ValueError('score_recal: l2 is a finite number >= 0, not %r' % (l2,))
-    if min_n is not None and (isinstance(min_n, bool) or not isinstance(min_n, (int, np.integer)) or min_n < 1):
-        raise ValueError('score_recal: min_n is an integer >= 1, not %r' % (min_n,))
+    if min_n is not None:
+        check_min_n('score_recal', min_n)
 
 
-class ScoreCalibration:
+class ScoreCalibration(Calibration):
     """The table cal.w[g][k] (float64; g over the classes under by = 'class', one group under 'all'; k over cal.features, the bias
     and the logit first) with what it was fitted for: variant, cls_cnt, by, l2, min_n, the per-group report and the soft_nms /
     var_recal settings of the model whose detections it was fitted on (fitted_under)."""
+    FORMAT, PREFIX, REQUIRED = FORMAT, 'score_recal', ('variant', 'cls_cnt', 'features', 'by', 'w')
 
     def __init__(self, variant, cls_cnt, features=None, by='all', w=None, l2=None, min_n=None, report=None, fitted_under=None):
         self.features, self._desc = _features(variant, cls_cnt, features)
@@ -137,42 +139,14 @@ class ScoreCalibration:
                 c.w[g][k] = v
         return c
 
-    # ---- JSON: Python writes a float as its repr, which reads back to the same bits -------------------------------------------------
-    def to_json(self):
-        clean = lambda v: None if isinstance(v, float) and not math.isfinite(v) else [clean(x) for x in v] if isinstance(v, list) else v
-        return json.dumps({'format': FORMAT, 'version': 1, 'variant': self.variant, 'cls_cnt': self.cls_cnt, 'features': self.features, 'by': self.by,
-                           'l2': self.l2, 'min_n': self.min_n, 'w': self.w, 'fitted_under': self.fitted_under,
-                           'report': [{k: clean(v) for k, v in e.items()} for e in self.report]}, indent=1, allow_nan=False)
+    # ---- the file (Calibration) -------------------------------------------------------------------------------------------------
+    def _fields(self):
+        return {'variant': self.variant, 'cls_cnt': self.cls_cnt, 'features': self.features, 'by': self.by, 'l2': self.l2, 'min_n': self.min_n,
+                'w': self.w, 'fitted_under': self.fitted_under}
 
     @classmethod
-    def from_json(cls, text):
-        d = json.loads(text)
-        if not isinstance(d, dict) or d.get('format') != FORMAT:
-            raise ValueError('score_recal: format: not a %s file' % FORMAT)
-        for k in ('variant', 'cls_cnt', 'features', 'by', 'w'):
-            if k not in d:
-                raise ValueError('score_recal: the file has no %r' % k)
+    def _from_dict(cls, d):
         return cls(d['variant'], d['cls_cnt'], d['features'], d['by'], d['w'], d.get('l2'), d.get('min_n'), d.get('report'), d.get('fitted_under'))
-
-    def save(self, path):
-        with open(path, 'w') as f:
-            f.write(self.to_json() + '\n')
-
-    @classmethod
-    def load(cls, path):
-        with open(path) as f:
-            return cls.from_json(f.read())
-
-    @classmethod
-    def coerce(cls, cal):
-        """A ScoreCalibration from one, from a path, or from the dict of to_json()."""
-        if isinstance(cal, cls):
-            return cal
-        if isinstance(cal, dict):
-            return cls.from_json(json.dumps(cal))
-        if isinstance(cal, (str, bytes)) or hasattr(cal, '__fspath__'):
-            return cls.load(cal)
-        raise ValueError('score_recal: a ScoreCalibration, a path or a dict, not %r' % (type(cal).__name__,))
 
     def log_lines(self):
         """One line per group of the report."""
@@ -212,12 +186,6 @@ def fitted_under(engine):
 
 
 # ---- the fit -----------------------------------------------------------------------------------------------------------------------
-def _err(rc):
-    if rc < 0:
-        msg = lib.byolo_last_error(None)
-        raise ByoloError(rc, msg.decode('utf-8', 'replace') if msg else '?')
-
-
 def eval_layout(model_or_layout):
     """The Evaluator layout of a model (or of a layout dict) whose records also carry ymin and ymax, which 'log_height' reads."""
     from .evaluate import uncertainty_columns, variant_of
@@ -239,8 +207,8 @@ def features_of(cal, src, score_col, cols, ymin_col=0, ymax_col=2):
     x = torch.empty((n, cal.K), dtype=torch.float64, device=src.device)
     cfg = cal.cfg()
     arr = (ctypes.c_int32 * _lib.SCORE_RECAL_MAX_K)(*([int(c) for c in cols] + [0] * (_lib.SCORE_RECAL_MAX_K - len(cols))))
-    _err(lib.byolo_score_recal_features(ctypes.byref(cfg), ctypes.c_void_p(src.data_ptr()), n, stride, int(score_col), int(ymin_col), int(ymax_col), arr,
-                                        ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(torch.cuda.current_stream(src.device).cuda_stream)))
+    raise_last(lib.byolo_score_recal_features(ctypes.byref(cfg), ctypes.c_void_p(src.data_ptr()), n, stride, int(score_col), int(ymin_col), int(ymax_col), arr,
+                                              ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(torch.cuda.current_stream(src.device).cuda_stream)))
     return x
 
 
@@ -254,21 +222,9 @@ def fit_arrays(x, y, group, n_groups, l2=DEFAULT_L2, min_n=DEFAULT_MIN_N):
     n_groups = int(n_groups)
     assert x.is_cuda and x.dtype == torch.float64 and x.dim() == 2 and y.shape == group.shape == x.shape[:1] and n_groups >= 1
     n, K = int(x.shape[0]), int(x.shape[1])
-    dev = x.device
-    g = group.to(torch.int64)
-    order = torch.sort(g, stable=True)[1]
-    xs, ys = x[order].contiguous(), y.to(torch.float64)[order].contiguous()
-    seg = torch.zeros(n_groups + 1, dtype=torch.int64, device=dev)
-    if n:
-        seg[1:] = torch.cumsum(torch.bincount(g, minlength=n_groups)[:n_groups], 0)
-    W = _lib.SCORE_RECAL_FIT_WORDS
-    out = torch.empty((n_groups, W), dtype=torch.float64, device=dev)
     wsb = int(lib.byolo_score_recal_fit_workspace_bytes(n, K))
-    ws = torch.empty(max(wsb // 8, 1), dtype=torch.float64, device=dev)
-    p = lambda t: ctypes.c_void_p(t.data_ptr())
-    _err(lib.byolo_score_recal_fit(p(xs), p(ys), p(seg), n_groups, n, K, float(l2), int(min_n), p(out), p(ws), wsb,
-                                   ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-    o = out.cpu().numpy()                                          # the host wait
+    o = segmented_fit([x, y.to(torch.float64)], group, n_groups, _lib.SCORE_RECAL_FIT_WORDS, wsb, lambda cols, seg, out, ws, stream: lib.byolo_score_recal_fit(
+        cols[0], cols[1], seg, n_groups, n, K, float(l2), int(min_n), out, ws, wsb, stream))
     mask = o[:, 10].astype(np.int64)
     return dict(n=o[:, 0].astype(np.int64), n_tp=o[:, 1].astype(np.int64), status=o[:, 2].astype(np.int64), iterations=o[:, 3].astype(np.int64),
                 converged=o[:, 4] != 0, nll_before=o[:, 5].copy(), nll_after=o[:, 6].copy(), brier_before=o[:, 7].copy(), brier_after=o[:, 8].copy(),

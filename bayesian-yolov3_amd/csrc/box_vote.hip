@@ -310,7 +310,7 @@ extern "C" int32_t byolo_set_box_vote(byolo_t* h, const byolo_vote_cfg* cfg) {
     h->vote_on = cfg != nullptr;
     h->vn_ptr = nullptr;
     // the stage's workspace is part of the plan, and a captured forward holds the launches of the old setting
-    h->plan.B = -1; h->plan.T = -1; ++h->plan_epoch; h->wsm_B = -1;
+    invalidate_plan(h);
     return BYOLO_OK;
 }
 

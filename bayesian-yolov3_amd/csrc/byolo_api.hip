@@ -114,7 +114,7 @@ extern "C" int32_t byolo_set_plan_opts(byolo_t* h, const byolo_plan_opts* o) {
     const bool repack = (o->wshift_per_layer != 0) != (c.wshift_per_layer != 0) || (o->dedup != 0) != (c.dedup != 0) || (o->lowmain != 0) != (c.lowmain != 0) || (o->kx3 != 0) != (c.kx3 != 0) || (o->p1 != 0) != (c.p1 != 0);
     h->opts = *o;
     h->dedup = o->dedup != 0;
-    h->plan.B = -1; h->plan.T = -1; ++h->plan_epoch; h->wsm_B = -1;
+    invalidate_plan(h);
     if (h->d_blob || !h->graphs.empty()) { HIPCHK(h, hipSetDevice(h->device)); drop_graphs(h); }
     if (repack && h->lowered) { h->lowered = false; h->finalized = false; }
     return BYOLO_OK;
@@ -155,8 +155,8 @@ extern "C" int32_t byolo_destroy(byolo_t* h) {
         if (h->d_status) (void)hipFree(h->d_status);
         if (h->pc_own) (void)hipFree(h->pc_own);
         if (h->vn_own) (void)hipFree(h->vn_own);
-        if (h->vr_tab) (void)hipFree(h->vr_tab);
-        if (h->sr_tab) (void)hipFree(h->sr_tab);
+        if (h->vr.dev) (void)hipFree(h->vr.dev);
+        if (h->sr.dev) (void)hipFree(h->sr.dev);
         if (h->sr_own) (void)hipFree(h->sr_own);
         if (h->h_status) (void)hipHostFree(h->h_status);
         for (auto& ps : h->prof) {
@@ -966,7 +966,7 @@ static int32_t forward_impl(byolo_t* h, const float* d_img, int32_t B, int32_t T
                 HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->vn_own), (size_t)B * out_cap * sizeof(int32_t)));
                 h->vn_own_cap = (size_t)B * out_cap;
             }
-            const bool scoring = h->sr_on && d_rows;
+            const bool scoring = h->sr.on && d_rows;
             if (scoring && h->sr_own_cap < (size_t)B * out_cap) {
                 HIPCHK(h, hipSetDevice(h->device));
                 if (h->sr_own) { HIPCHK(h, hipDeviceSynchronize()); HIPCHK(h, hipFree(h->sr_own)); h->sr_own = nullptr; h->sr_own_cap = 0; }
@@ -1042,9 +1042,9 @@ static int32_t forward_piece(byolo_t* h, const float* d_img, int32_t B, int32_t 
         h->vn_ptr = reinterpret_cast<const int32_t*>(static_cast<char*>(d_workspace) + h->plan.vote_n_off);
         h->vn_B = B; h->vn_cap = (int32_t)nms_out_cap(h);
     }
-    if (h->vr_on && h->vr_dirty) { rc = byolo_var_recal_upload(h, st); if (rc) return rc; }      // once per byolo_set_var_recal, in front of any capture
-    if (d_rows && h->sr_on) {
-        if (h->sr_dirty) { rc = byolo_score_recal_upload(h, st); if (rc) return rc; }           // likewise once per byolo_set_score_recal
+    if (h->vr.on && h->vr.dirty) { rc = byolo_recal_upload(h, &h->vr, byolo_var_recal_pack, st); if (rc) return rc; }      // once per byolo_set_var_recal, in front of any capture
+    if (d_rows && h->sr.on) {
+        if (h->sr.dirty) { rc = byolo_recal_upload(h, &h->sr, byolo_score_recal_pack, st); if (rc) return rc; }           // likewise once per byolo_set_score_recal
         h->sr_ptr = reinterpret_cast<const float*>(static_cast<char*>(d_workspace) + h->plan.score_off);
         h->sr_B = B; h->sr_cap = (int32_t)nms_out_cap(h);
     }
@@ -1331,7 +1331,7 @@ static int32_t enqueue_forward(byolo_t* h, const FwdArgs& a, hipStream_t st, boo
     }
     float* boxes = d_boxes ? d_boxes : reinterpret_cast<float*>(ws + h->plan.boxes_off);
     if (d_boxes || d_rows) { rc = run_decode(h, ws, boxes, B, T, st, h->tshard_T > 0 ? 1 : 0); if (rc) return rc; }
-    if ((d_boxes || d_rows) && h->vr_on && h->tshard_T == 0) {      // variance recalibration, in place on the pre-NMS rows (var_recal.hip); a T shard holds sums
+    if ((d_boxes || d_rows) && h->vr.on && h->tshard_T == 0) {      // variance recalibration, in place on the pre-NMS rows (var_recal.hip); a T shard holds sums
         VarRecalParams v;
         byolo_var_recal_from_handle(h, &v);
         v.in = boxes; v.out = boxes; v.n = (int64_t)B * h->n_boxes;
@@ -1350,7 +1350,7 @@ static int32_t enqueue_forward(byolo_t* h, const FwdArgs& a, hipStream_t st, boo
             sp.n = n; sp.n.ws = ws + h->plan.soft_off; sp.n.ws_bytes = soft_nms_workspace_bytes(B, h->n_boxes, n.C);
             HIPCHK(h, launch_soft_nms(sp, st));
         } else HIPCHK(h, launch_sort_nms(n, st));
-        if (h->sr_on) {                                     // score recalibration, in place on the kept rows (score_recal.hip): reads d_count on the device
+        if (h->sr.on) {                                     // score recalibration, in place on the kept rows (score_recal.hip): reads d_count on the device
             ScoreRecalParams s;
             byolo_score_recal_from_handle(h, &s);
             s.in = d_rows; s.out = d_rows; s.count = d_count; s.score = reinterpret_cast<float*>(ws + h->plan.score_off); s.B = B; s.cap = (int)nms_out_cap(h);
@@ -1550,7 +1550,7 @@ extern "C" int32_t byolo_set_soft_nms(byolo_t* h, const byolo_soft_nms_cfg* cfg)
     h->soft_on = cfg != nullptr;
     h->pc_counts = nullptr;
     // the stage's workspace is part of the plan, and a captured forward holds the launches of the old setting
-    h->plan.B = -1; h->plan.T = -1; ++h->plan_epoch; h->wsm_B = -1;
+    invalidate_plan(h);
     return BYOLO_OK;
 }
 

@@ -155,6 +155,15 @@ static inline size_t nms_workspace_bytes_ex(int B, int64_t N, int nms_mode, int 
     return nms_workspace_bytes(B, N, nms_mode == BYOLO_NMS_PER_CLASS ? cls_cnt : 2);
 }
 
+// The table of a recalibration stage of a handle, applied by byolo_forward while `on`.  dev: the device copy (`bytes` of it), filled
+// by the first forward after a change (dirty; byolo_recal_upload), never per forward, from host, which lives as long as the handle.
+struct RecalTable {
+    size_t bytes;
+    bool on = false, dirty = false;
+    double* dev = nullptr;
+    double host[(BYOLO_VAR_RECAL_TABLE_BYTES > BYOLO_SCORE_RECAL_TABLE_BYTES ? BYOLO_VAR_RECAL_TABLE_BYTES : BYOLO_SCORE_RECAL_TABLE_BYTES) / sizeof(double)] = {};
+};
+
 }  // namespace byi
 using namespace byi;
 
@@ -223,16 +232,12 @@ struct byolo {
     bool vote_on = false; byolo_vote_cfg vote_cfg = {};
     // byolo_set_soft_nms: byolo_forward runs the soft-NMS (tail_kernels.hip soft_*) in place of the hard one
     bool soft_on = false; byolo_soft_nms_cfg soft_cfg = {};
-    // byolo_set_var_recal: byolo_forward applies vr_cfg's table in place behind the decode (var_recal.hip).  vr_tab: the handle's
-    // device copy (BYOLO_VAR_RECAL_TABLE_BYTES), filled by the first forward after a change (vr_dirty), never per forward, from
-    // vr_host, the packed table in memory that lives as long as the handle
-    bool vr_on = false, vr_dirty = false; byolo_var_recal_cfg vr_cfg = {}; double* vr_tab = nullptr;
-    double vr_host[BYOLO_VAR_RECAL_TABLE_BYTES / sizeof(double)] = {};
-    // byolo_set_score_recal: byolo_forward applies sr_cfg's table in place on the kept rows behind the NMS (score_recal.hip).  sr_tab /
-    // sr_host / sr_dirty: as vr_*.  sr_ptr: where the last such forward left score [sr_B, sr_cap] -- inside that call's workspace,
-    // or in sr_own (a forward that ran in pieces), as vn_ptr / vn_own
-    bool sr_on = false, sr_dirty = false; byolo_score_recal_cfg sr_cfg = {}; double* sr_tab = nullptr;
-    double sr_host[BYOLO_SCORE_RECAL_TABLE_BYTES / sizeof(double)] = {};
+    // byolo_set_var_recal: byolo_forward applies vr_cfg's table (vr) in place behind the decode (var_recal.hip)
+    byolo_var_recal_cfg vr_cfg = {}; RecalTable vr{BYOLO_VAR_RECAL_TABLE_BYTES};
+    // byolo_set_score_recal: byolo_forward applies sr_cfg's table (sr) in place on the kept rows behind the NMS (score_recal.hip).
+    // sr_ptr: where the last such forward left score [sr_B, sr_cap] -- inside that call's workspace, or in sr_own (a forward that
+    // ran in pieces), as vn_ptr / vn_own
+    byolo_score_recal_cfg sr_cfg = {}; RecalTable sr{BYOLO_SCORE_RECAL_TABLE_BYTES};
     const float* sr_ptr = nullptr; int32_t sr_B = 0, sr_cap = 0;
     float* sr_own = nullptr; size_t sr_own_cap = 0;
     const int32_t* vn_ptr = nullptr; int32_t vn_B = 0, vn_cap = 0;
@@ -270,6 +275,13 @@ int32_t byolo_fail(byolo_t* h, int32_t code, const char* fmt, ...);
     return fail(h, BYOLO_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 static inline float* dptr(const byolo_t* h, size_t off) { return h->d_blob + off; }
+// A setting changed that the plan, a captured forward's launches and the size byolo_workspace_bytes remembers depend on
+static inline void invalidate_plan(byolo_t* h) { h->plan.B = -1; h->plan.T = -1; ++h->plan_epoch; h->wsm_B = -1; }
+// Do the byte ranges [a, a + a_bytes) and [b, b + b_bytes) share a byte?
+static inline bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+    const char* a0 = static_cast<const char*>(a); const char* b0 = static_cast<const char*>(b);
+    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
 
 // No C++ exception leaves the C-ABI: a host allocation that fails (a graph of absurd sizes) is BYOLO_ERR_NOMEM, like a workspace
 // that is too small -- the caller is a ctypes / cgo / JNI binding that cannot unwind.
@@ -280,7 +292,6 @@ static int32_t guarded(byolo_t* h, const char* what, F&& f) {
     catch (const std::exception& e) { return fail(h, BYOLO_ERR_ARG, "%s: %s", what, e.what()); }
     catch (...) { return fail(h, BYOLO_ERR_ARG, "%s: an exception that is not a std::exception", what); }      // nothing crosses the C-ABI (include/byolo.h)
 }
-
 
 #define lower byolo_lower
 int32_t byolo_lower(byolo_t* h);                                   // byolo_api.hip: freeze the graph, lower it to steps (host only)
@@ -303,13 +314,16 @@ int32_t check_run(byolo_t* h, int32_t B, int32_t T, const char* what, bool need_
 // (status cleared) if an activation left the range.  For the head trainer (train_heads.hip).
 // box_vote.hip: the VoteParams of byolo_forward's voting stage from the handle's rows and detection layers (pointers left null)
 int32_t byolo_vote_from_handle(byolo_t* h, VoteParams* p, const char* what);
-// var_recal.hip: the handle's device table brought up to date on the forward's stream `st` (waits for the device and for `st`; only
-// after byolo_set_var_recal changed it),
-// and the VarRecalParams of byolo_forward's stage (pointers to the rows left null)
-int32_t byolo_var_recal_upload(byolo_t* h, hipStream_t st);
+// var_recal.hip, for both recalibration stages: a stage's device table brought up to date on the forward's stream `st` -- `pack`
+// writes the handle's table into t->host first -- (waits for the device and for `st`; only after byolo_set_*_recal changed it);
+// the arguments the two segmented fits share (null pointers, n_seg / n, ws_bytes against `need`, which ws_call spells, d_ws aligned);
+// var_recal.hip's pack and the VarRecalParams of byolo_forward's stage (pointers to the rows left null)
+int32_t byolo_recal_upload(byolo_t* h, RecalTable* t, void (*pack)(const byolo_t* h, double* tab), hipStream_t st);
+int32_t byolo_recal_check_fit(const char* what, bool have_ptrs, int32_t n_seg, int64_t n, const void* d_ws, size_t ws_bytes, size_t need, const char* ws_call);
+void byolo_var_recal_pack(const byolo_t* h, double* tab);
 void byolo_var_recal_from_handle(const byolo_t* h, VarRecalParams* p);
 // score_recal.hip: the same two for byolo_set_score_recal (pointers to the rows, the counts and the scores left null)
-int32_t byolo_score_recal_upload(byolo_t* h, hipStream_t st);
+void byolo_score_recal_pack(const byolo_t* h, double* tab);
 void byolo_score_recal_from_handle(const byolo_t* h, ScoreRecalParams* p);
 static inline int64_t nms_out_cap(const byolo_t* h) { return (int64_t)h->cfg.max_out * nms_classes(h->cfg.nms_mode, h->cfg.cls_cnt); }
 int32_t byolo_run_backbone(byolo_t* h, const float* d_img, int32_t B, void* d_workspace, size_t workspace_bytes, hipStream_t st);

@@ -234,7 +234,7 @@ void make_plan(byolo_t* h, int B, int T, bool inject) {
         p.vote_off = o; o += align_up(box_vote_workspace_bytes(B, h->n_boxes), 256);
     }
     p.score_off = o;
-    if (h->sr_on) o += align_up((size_t)B * nms_out_cap(h) * sizeof(float), 256);
+    if (h->sr.on) o += align_up((size_t)B * nms_out_cap(h) * sizeof(float), 256);
     p.stats_off = o; o += align_up((size_t)1024 * 2 * h->maxC * sizeof(double) + 2 * h->maxC * sizeof(float), 256);
     p.img_split_off = o; if (h->img_split) o += align_up((size_t)B * h->cfg.img_h * h->cfg.img_w * h->cfg.img_c * sizeof(float), 256);
     // launch geometry per step: tile configuration and the split-K of the last partial round (shape-only)

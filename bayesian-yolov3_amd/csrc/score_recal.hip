@@ -8,13 +8,14 @@
 //                        its 256 rows with consecutive lanes.  A group at the identity (0, 1, 0, ...) leaves its rows alone.
 //   sr_features_kernel   the features of records (or rows) as float64 [n, K], the device functions of the apply
 //   sr_fit_kernel        the fit: one workgroup of 256 lanes per segment -- standardise, Newton on the ridge-penalised mean NLL, fold
-//                        back -- inside the one launch.  Every sum is the fixed sum of vr_fit_kernel: lane t sums the terms j = t
+//                        back -- inside the one launch.  Every sum is the fixed sum of recal_common.h: lane t sums the terms j = t
 //                        (mod 256) in ascending j, one lane per quantity then adds the 256 partial sums in ascending t (LDS).  No
 //                        atomics, no dependence on which workgroup runs first: two runs give the same bytes.
 //
 // Compiled without contraction (build.py _EXACT_F32): every float64 operation below is one operation of the restatement.
 #include <cfloat>
 #include "byolo_internal.h"
+#include "recal_common.h"
 
 namespace byk {
 
@@ -51,12 +52,7 @@ __device__ __forceinline__ double sr_feature(int kind, int col, float s, const f
 __global__ __launch_bounds__(256) void score_recal_kernel(ScoreRecalParams p) {
     const int64_t n = (int64_t)p.B * p.cap;
     const int64_t row0 = (int64_t)blockIdx.x * 256;
-    if (p.out != p.in) {                                     // every column and the padding come along (uniform over the workgroup)
-        const int64_t rows = n - row0 < 256 ? n - row0 : 256;
-        const int64_t e0 = row0 * p.D, cnt = rows * p.D;
-        for (int64_t e = threadIdx.x; e < cnt; e += 256) p.out[e0 + e] = p.in[e0 + e];
-        __syncthreads();
-    }
+    recal_copy_rows(p, row0, n);                              // out of place: every column and the padding come along
     const int64_t i = row0 + threadIdx.x;
     if (i >= n) return;
     const int b = (int)(i / p.cap), k = (int)(i - (int64_t)b * p.cap);
@@ -113,7 +109,7 @@ __global__ __launch_bounds__(256) void sr_features_kernel(SrFeatParams p) {
     if (i >= p.n) return;
     const float* r = p.src + i * p.stride;
     const float s = r[p.score_col];
-    for (int q = 0; q < p.K; ++q) p.x[i * p.K + q] = s != s ? __longlong_as_double(0x7ff8000000000000ll) : sr_feature(p.kind[q], p.col[q], s, r, p.ymin_col, p.ymax_col);
+    for (int q = 0; q < p.K; ++q) p.x[i * p.K + q] = s != s ? recal_nan() : sr_feature(p.kind[q], p.col[q], s, r, p.ymin_col, p.ymax_col);
 }
 
 // ---- the fit ---------------------------------------------------------------------------------------------------------------------
@@ -123,18 +119,6 @@ struct SrFitParams {
     double* out;             // [n_seg][BYOLO_SCORE_RECAL_FIT_WORDS]
 };
 
-// The fixed sum of five quantities at once (var_recal.hip vr_totals): lane q < 5 adds the 256 partials of quantity q in ascending t.
-__device__ __forceinline__ void sr_totals(double (*s_part)[256], double* s_tot, double p0, double p1, double p2, double p3, double p4) {
-    const int tid = threadIdx.x;
-    s_part[0][tid] = p0; s_part[1][tid] = p1; s_part[2][tid] = p2; s_part[3][tid] = p3; s_part[4][tid] = p4;
-    __syncthreads();
-    if (tid < 5) {
-        double acc = 0.0;
-        for (int t = 0; t < 256; ++t) acc += s_part[tid][t];
-        s_tot[tid] = acc;
-    }
-    __syncthreads();
-}
 __device__ __forceinline__ double sr_softplus(double a) {
     const double m = fmax(a, 0.0);
     const double e = exp(-fabs(a));
@@ -155,12 +139,12 @@ __device__ __forceinline__ double sr_loss(const SrFitParams& p, int64_t lo, int6
         const double ya = p.y[j] * a;
         acc += sr_softplus(a) - ya;
     }
-    sr_totals(s_part, s_tot, acc, 0.0, 0.0, 0.0, 0.0);
+    recal_totals(s_part, s_tot, 5, acc, 0.0, 0.0, 0.0, 0.0);
     double pen = 0.0;
     for (int k = 1; k < p.K; ++k) { const double t = s_u[k] * s_u[k]; pen = pen + t; }
     const double c = p.l2 / (2.0 * dn);
     const double L = s_tot[0] / dn + c * pen;
-    __syncthreads();                                         // s_tot is read; the next sr_totals may write it
+    __syncthreads();                                         // s_tot is read; the next recal_totals may write it
     return L;
 }
 // mean NLL and mean Brier score of sigmoid(w . row) over the segment, rows of K doubles at `rows` (raw features) -- or, w == nullptr,
@@ -179,7 +163,7 @@ __device__ __forceinline__ void sr_nll_brier(const SrFitParams& p, int64_t lo, i
         const double r = pr - y;
         ab += r * r;
     }
-    sr_totals(s_part, s_tot, an, ab, 0.0, 0.0, 0.0);
+    recal_totals(s_part, s_tot, 5, an, ab, 0.0, 0.0, 0.0);
     nll = s_tot[0] / dn; brier = s_tot[1] / dn;
     __syncthreads();
 }
@@ -192,12 +176,11 @@ __global__ __launch_bounds__(256) void sr_fit_kernel(SrFitParams p) {
     __shared__ double s_state[4];                            // what the lanes do next, the loss at u, the last step, the step length
     __shared__ int s_drop[8];
     const int tid = threadIdx.x, K = p.K;
-    int64_t lo = p.seg[blockIdx.x], hi = p.seg[blockIdx.x + 1];
-    lo = lo < 0 ? 0 : (lo > p.n_total ? p.n_total : lo);     // nothing is read outside [0, n) whatever the offsets say
-    hi = hi < lo ? lo : (hi > p.n_total ? p.n_total : hi);
+    int64_t lo, hi;
+    recal_segment(p.seg, blockIdx.x, p.n_total, lo, hi);
     const int64_t n = hi - lo;
     double* out = p.out + (size_t)blockIdx.x * BYOLO_SCORE_RECAL_FIT_WORDS;
-    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    const double nan = recal_nan();
     if (tid < 8) { s_u[tid] = 0.0; s_w[tid] = tid == 1 ? 1.0 : 0.0; s_mean[tid] = 0.0; s_sd[tid] = 1.0; s_drop[tid] = 0; }
     if (tid < 4) s_state[tid] = 0.0;
     __syncthreads();
@@ -213,19 +196,19 @@ __global__ __launch_bounds__(256) void sr_fit_kernel(SrFitParams p) {
     // the positives (an integer: exact in any order, summed in the fixed one all the same)
     double ytp = 0.0;
     for (int64_t j = lo + tid; j < hi; j += 256) { ytp += p.y[j]; p.z[j * K] = 1.0; }
-    sr_totals(s_part, s_tot, ytp, 0.0, 0.0, 0.0, 0.0);
+    recal_totals(s_part, s_tot, 5, ytp, 0.0, 0.0, 0.0, 0.0);
     const double n_tp = s_tot[0];
     __syncthreads();
     // standardise: per feature the mean, then the population standard deviation; z = (x - mean) / sd, 0 for a dropped feature
     for (int k = 1; k < K; ++k) {
         double sx = 0.0;
         for (int64_t j = lo + tid; j < hi; j += 256) sx += p.x[j * K + k];
-        sr_totals(s_part, s_tot, sx, 0.0, 0.0, 0.0, 0.0);
+        recal_totals(s_part, s_tot, 5, sx, 0.0, 0.0, 0.0, 0.0);
         const double mean = s_tot[0] / dn;
         __syncthreads();
         double sv = 0.0;
         for (int64_t j = lo + tid; j < hi; j += 256) { const double d = p.x[j * K + k] - mean; sv += d * d; }
-        sr_totals(s_part, s_tot, sv, 0.0, 0.0, 0.0, 0.0);
+        recal_totals(s_part, s_tot, 5, sv, 0.0, 0.0, 0.0, 0.0);
         const double var = s_tot[0] / dn;
         const double sd = sqrt(var);
         __syncthreads();
@@ -272,7 +255,7 @@ __global__ __launch_bounds__(256) void sr_fit_kernel(SrFitParams p) {
                 }
             }
 #pragma unroll
-            for (int c = 0; c < 9; ++c) sr_totals(s_part, s_tot + 5 * c, acc[5 * c], acc[5 * c + 1], acc[5 * c + 2], acc[5 * c + 3], acc[5 * c + 4]);
+            for (int c = 0; c < 9; ++c) recal_totals(s_part, s_tot + 5 * c, 5, acc[5 * c], acc[5 * c + 1], acc[5 * c + 2], acc[5 * c + 3], acc[5 * c + 4]);
             if (tid == 0) {                                  // the Newton step, one operation per line
                 const double ln = p.l2 / dn;
                 int q = 8;
@@ -434,11 +417,9 @@ extern "C" int32_t byolo_score_recal_apply(const byolo_score_recal_cfg* cfg, con
     if (D != p.D) return fail(nullptr, BYOLO_ERR_ARG, "%s: D %d: rows of kind %d with %d classes have %d columns", what, D, cfg->kind, cfg->cls_cnt, p.D);
     if (B < 0 || cap < 0 || (int64_t)B * cap >= (1ll << 31) * 256) return fail(nullptr, BYOLO_ERR_ARG, "%s: B %d, cap %d outside the launch", what, B, cap);
     if (reinterpret_cast<uintptr_t>(d_table) & 7) return fail(nullptr, BYOLO_ERR_ARG, "%s: d_table is not 8-byte aligned", what);
-    const char* i0 = reinterpret_cast<const char*>(d_rows_in); const char* o0 = reinterpret_cast<const char*>(d_rows_out);
-    const char* s0 = reinterpret_cast<const char*>(d_score);
     const size_t bytes = (size_t)B * cap * D * sizeof(float), sbytes = (size_t)B * cap * sizeof(float);
-    if (i0 < o0 + bytes && o0 < i0 + bytes) return fail(nullptr, BYOLO_ERR_ARG, "%s: d_rows_out overlaps d_rows_in (the stand-alone stage never works in place)", what);
-    if ((i0 < s0 + sbytes && s0 < i0 + bytes) || (o0 < s0 + sbytes && s0 < o0 + bytes)) return fail(nullptr, BYOLO_ERR_ARG, "%s: d_score overlaps the rows", what);
+    if (ranges_overlap(d_rows_in, bytes, d_rows_out, bytes)) return fail(nullptr, BYOLO_ERR_ARG, "%s: d_rows_out overlaps d_rows_in (the stand-alone stage never works in place)", what);
+    if (ranges_overlap(d_rows_in, bytes, d_score, sbytes) || ranges_overlap(d_rows_out, bytes, d_score, sbytes)) return fail(nullptr, BYOLO_ERR_ARG, "%s: d_score overlaps the rows", what);
     if ((int64_t)B * cap == 0) return BYOLO_OK;
     p.in = d_rows_in; p.out = d_rows_out; p.count = d_count; p.score = d_score; p.B = B; p.cap = cap; p.tab = static_cast<const double*>(d_table);
     HIPCHK(nullptr, launch_score_recal(p, reinterpret_cast<hipStream_t>(stream)));
@@ -447,20 +428,9 @@ extern "C" int32_t byolo_score_recal_apply(const byolo_score_recal_cfg* cfg, con
 
 void byolo_score_recal_from_handle(const byolo_t* h, ScoreRecalParams* p) {
     sr_params(h->sr_cfg, p);
-    p->D = h->row_len; p->obj_idx = h->obj_idx; p->cls_start = h->cls_start; p->tab = h->sr_tab;
+    p->D = h->row_len; p->obj_idx = h->obj_idx; p->cls_start = h->cls_start; p->tab = h->sr.dev;
 }
-
-// (var_recal.hip byolo_var_recal_upload says why the copy runs on the forward's own stream and is waited for)
-int32_t byolo_score_recal_upload(byolo_t* h, hipStream_t st) {
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipDeviceSynchronize());                       // a forward in flight, or a graph replaying, may still read the table
-    if (!h->sr_tab) HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->sr_tab), BYOLO_SCORE_RECAL_TABLE_BYTES));
-    sr_pack(&h->sr_cfg, h->sr_host);
-    HIPCHK(h, hipMemcpyAsync(h->sr_tab, h->sr_host, sizeof h->sr_host, hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    h->sr_dirty = false;
-    return BYOLO_OK;
-}
+void byolo_score_recal_pack(const byolo_t* h, double* tab) { sr_pack(&h->sr_cfg, tab); }
 
 extern "C" int32_t byolo_set_score_recal(byolo_t* h, const byolo_score_recal_cfg* cfg) {
     const char* what = "byolo_set_score_recal";
@@ -476,12 +446,12 @@ extern "C" int32_t byolo_set_score_recal(byolo_t* h, const byolo_score_recal_cfg
         sr_params(*cfg, &p);
         if (p.D != h->row_len || p.obj_idx != h->obj_idx || p.cls_start != h->cls_start) return fail(h, BYOLO_ERR_ARG, "%s: kind %d: the handle's rows have another layout", what, cfg->kind);
         h->sr_cfg = *cfg;
-        h->sr_dirty = true;
+        h->sr.dirty = true;
     }
-    h->sr_on = cfg != nullptr;
+    h->sr.on = cfg != nullptr;
     h->sr_ptr = nullptr;
     // a captured forward holds the launches of the old setting, and the plan has score [B, cap] only while this is on (as byolo_set_box_vote)
-    h->plan.B = -1; h->plan.T = -1; ++h->plan_epoch; h->wsm_B = -1;
+    invalidate_plan(h);
     return BYOLO_OK;
 }
 
@@ -520,13 +490,12 @@ extern "C" size_t byolo_score_recal_fit_workspace_bytes(int64_t n, int32_t K) { 
 extern "C" int32_t byolo_score_recal_fit(const double* d_x, const double* d_y, const int64_t* d_seg, int32_t n_seg, int64_t n, int32_t K,
                                          double l2, int64_t min_n, double* d_out, void* d_ws, size_t ws_bytes, void* stream) {
     const char* what = "byolo_score_recal_fit";
-    if (!d_seg || !d_out || (n > 0 && (!d_x || !d_y || !d_ws))) return fail(nullptr, BYOLO_ERR_ARG, "%s: null argument", what);
-    if (n_seg < 1 || n < 0) return fail(nullptr, BYOLO_ERR_ARG, "%s: n_seg %d, n %lld", what, n_seg, (long long)n);
+    int32_t rc = byolo_recal_check_fit(what, d_seg && d_out && (n <= 0 || (d_x && d_y && d_ws)), n_seg, n, d_ws, ws_bytes, byolo_score_recal_fit_workspace_bytes(n, K),
+                                       "byolo_score_recal_fit_workspace_bytes(n, K)");
+    if (rc) return rc;
     if (K < 2 || K > BYOLO_SCORE_RECAL_MAX_K) return fail(nullptr, BYOLO_ERR_ARG, "%s: K %d outside 2 .. %d", what, K, BYOLO_SCORE_RECAL_MAX_K);
     if (!(l2 >= 0.0 && l2 <= DBL_MAX)) return fail(nullptr, BYOLO_ERR_ARG, "%s: l2 %g must be >= 0 and finite", what, l2);
     if (min_n < 1) return fail(nullptr, BYOLO_ERR_ARG, "%s: min_n %lld must be >= 1", what, (long long)min_n);
-    if (ws_bytes < byolo_score_recal_fit_workspace_bytes(n, K)) return fail(nullptr, BYOLO_ERR_NOMEM, "%s: workspace %zu < byolo_score_recal_fit_workspace_bytes(n, K) = %zu", what, ws_bytes, byolo_score_recal_fit_workspace_bytes(n, K));
-    if (reinterpret_cast<uintptr_t>(d_ws) & 7) return fail(nullptr, BYOLO_ERR_ARG, "%s: d_ws is not 8-byte aligned", what);
     byk::SrFitParams p;
     p.x = d_x; p.y = d_y; p.seg = d_seg; p.n_total = n; p.K = K; p.l2 = l2; p.min_n = min_n; p.z = static_cast<double*>(d_ws); p.out = d_out;
     hipLaunchKernelGGL(byk::sr_fit_kernel, dim3((unsigned)n_seg), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p);

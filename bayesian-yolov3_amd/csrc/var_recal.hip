@@ -9,12 +9,13 @@
 //                      float64 multiply per column -- no exp, no log: bit-exact against numpy.
 //   vr_fit_kernel      the fit: one workgroup of 256 lanes per segment (a group and coordinate), the whole Newton iteration of the
 //                      power method inside the one launch.  Lane t sums the terms j = t (mod 256) in ascending j; lanes 0 .. 4
-//                      then each add the 256 partial sums of one quantity in ascending t (LDS).  No atomics, no dependence on
-//                      which workgroup runs first: two runs give the same bytes.
+//                      then each add the 256 partial sums of one quantity in ascending t (LDS; recal_common.h).  No atomics, no
+//                      dependence on which workgroup runs first: two runs give the same bytes.
 //
 // Compiled without contraction (build.py _EXACT_F32): every float64 operation below is one operation of the restatement.
 #include <cfloat>
 #include "byolo_internal.h"
+#include "recal_common.h"
 
 namespace byk {
 
@@ -48,12 +49,7 @@ __device__ __forceinline__ bool vr_same(float x, float y) { return __float_as_ui
 
 __global__ __launch_bounds__(256) void var_recal_kernel(VarRecalParams p) {
     const int64_t row0 = (int64_t)blockIdx.x * 256;
-    if (p.out != p.in) {                                     // every column comes along (uniform over the workgroup)
-        const int64_t rows = p.n - row0 < 256 ? p.n - row0 : 256;
-        const int64_t e0 = row0 * p.D, cnt = rows * p.D;
-        for (int64_t e = threadIdx.x; e < cnt; e += 256) p.out[e0 + e] = p.in[e0 + e];
-        __syncthreads();
-    }
+    recal_copy_rows(p, row0, p.n);                            // out of place: every column comes along
     const int64_t i = row0 + threadIdx.x;
     if (i >= p.n) return;
     const float* r = p.in + i * p.D;
@@ -111,19 +107,6 @@ struct VrFitParams {
     double* out;             // [n_seg][BYOLO_VAR_RECAL_FIT_WORDS]
 };
 
-// The fixed sum of up to five quantities at once: lane t hands in its partial sums, lane q < nq adds the 256 partials of quantity q
-// in ascending t.  Every lane returns with the totals in s_tot.
-__device__ __forceinline__ void vr_totals(double (*s_part)[256], double* s_tot, int nq, double p0, double p1, double p2, double p3, double p4) {
-    const int tid = threadIdx.x;
-    s_part[0][tid] = p0; s_part[1][tid] = p1; s_part[2][tid] = p2; s_part[3][tid] = p3; s_part[4][tid] = p4;
-    __syncthreads();
-    if (tid < nq) {
-        double acc = 0.0;
-        for (int t = 0; t < 256; ++t) acc += s_part[tid][t];
-        s_tot[tid] = acc;
-    }
-    __syncthreads();
-}
 // 0.5 (log(2 pi v) + r^2 / v), one operation per line (byolo/eval_loc.py nll_terms with z^2 = r^2 / v)
 __device__ __forceinline__ double vr_nll(double r2, double v) {
     const double a = VR_TWO_PI * v;
@@ -138,12 +121,11 @@ __global__ __launch_bounds__(256) void vr_fit_kernel(VrFitParams p) {
     __shared__ double s_tot[5];
     __shared__ double s_state[4];                            // alpha, b, what the lanes do next, iterations
     const int tid = threadIdx.x;
-    int64_t lo = p.seg[blockIdx.x], hi = p.seg[blockIdx.x + 1];
-    lo = lo < 0 ? 0 : (lo > p.n_total ? p.n_total : lo);     // nothing is read outside [0, n) whatever the offsets say
-    hi = hi < lo ? lo : (hi > p.n_total ? p.n_total : hi);
+    int64_t lo, hi;
+    recal_segment(p.seg, blockIdx.x, p.n_total, lo, hi);
     const int64_t n = hi - lo;
     double* out = p.out + (size_t)blockIdx.x * BYOLO_VAR_RECAL_FIT_WORDS;
-    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    const double nan = recal_nan();
     if (n == 0) {
         if (tid == 0) { out[0] = 0.0; out[1] = 1.0; out[2] = 1.0; out[3] = nan; out[4] = nan; out[5] = nan; out[6] = 0.0; out[7] = (double)BYOLO_VAR_RECAL_EMPTY; out[8] = 1.0; out[9] = 0.0; }
         return;
@@ -159,10 +141,10 @@ __global__ __launch_bounds__(256) void vr_fit_kernel(VrFitParams p) {
         p.lv[j] = lv;
         q_sum += q; l_sum += lv; nll_sum += vr_nll(r2, v);
     }
-    vr_totals(s_part, s_tot, 3, q_sum, l_sum, nll_sum, 0.0, 0.0);
+    recal_totals(s_part, s_tot, 3, q_sum, l_sum, nll_sum, 0.0, 0.0);
     const double S = s_tot[0];
     const double a_scale = S / dn, ubar = s_tot[1] / dn, nll_before = s_tot[2] / dn;
-    __syncthreads();                                         // s_tot is read; the next vr_totals may write it
+    __syncthreads();                                         // s_tot is read; the next recal_totals may write it
     int status = BYOLO_VAR_RECAL_FITTED;
     double a = a_scale, b = 1.0, U = 0.0, iterations = 0.0, converged = 1.0;
     if (!(S > 0.0) || !(S <= DBL_MAX)) { status = BYOLO_VAR_RECAL_IDENTITY; a = 1.0; }
@@ -197,7 +179,7 @@ __global__ __launch_bounds__(256) void vr_fit_kernel(VrFitParams p) {
                     const double wuu = wu * u;
                     g0 += d; g1 += ud; h00 += w; h01 += wu; h11 += wuu;
                 }
-                vr_totals(s_part, s_tot, 5, g0, g1, h00, h01, h11);
+                recal_totals(s_part, s_tot, 5, g0, g1, h00, h01, h11);
                 if (tid == 0) {                              // the Newton step, one operation per line
                     const double G0 = s_tot[0], G1 = s_tot[1], H00 = s_tot[2], H01 = s_tot[3], H11 = s_tot[4];
                     const double hh = H00 * H11;
@@ -253,7 +235,7 @@ __global__ __launch_bounds__(256) void vr_fit_kernel(VrFitParams p) {
         else { const double bl = b * p.lv[j]; const double x = exp(bl); vp = a * x; }
         after += vr_nll(r2, vp);
     }
-    vr_totals(s_part, s_tot, 1, after, 0.0, 0.0, 0.0, 0.0);
+    recal_totals(s_part, s_tot, 1, after, 0.0, 0.0, 0.0, 0.0);
     if (tid == 0) {
         out[0] = dn; out[1] = a; out[2] = b; out[3] = a_scale; out[4] = nll_before; out[5] = s_tot[0] / dn;
         out[6] = iterations; out[7] = (double)status; out[8] = converged; out[9] = U;
@@ -317,9 +299,8 @@ extern "C" int32_t byolo_var_recal_apply(const byolo_var_recal_cfg* cfg, const f
     if (D < need) return fail(nullptr, BYOLO_ERR_ARG, "%s: D %d: rows of kind %d have at least %d columns", what, D, cfg->kind, need);
     if (n < 0 || n >= (1ll << 31) * 256) return fail(nullptr, BYOLO_ERR_ARG, "%s: n %lld outside the launch", what, (long long)n);
     if (reinterpret_cast<uintptr_t>(d_table) & 7) return fail(nullptr, BYOLO_ERR_ARG, "%s: d_table is not 8-byte aligned", what);
-    const char* i0 = reinterpret_cast<const char*>(d_in); const char* o0 = reinterpret_cast<const char*>(d_out);
     const size_t bytes = (size_t)n * D * sizeof(float);
-    if (i0 < o0 + bytes && o0 < i0 + bytes) return fail(nullptr, BYOLO_ERR_ARG, "%s: d_out overlaps d_in (the stand-alone stage never works in place)", what);
+    if (ranges_overlap(d_in, bytes, d_out, bytes)) return fail(nullptr, BYOLO_ERR_ARG, "%s: d_out overlaps d_in (the stand-alone stage never works in place)", what);
     if (n == 0) return BYOLO_OK;
     VarRecalParams p;
     vr_params(*cfg, &p);
@@ -330,21 +311,23 @@ extern "C" int32_t byolo_var_recal_apply(const byolo_var_recal_cfg* cfg, const f
 
 void byolo_var_recal_from_handle(const byolo_t* h, VarRecalParams* p) {
     vr_params(h->vr_cfg, p);
-    p->D = h->row_len; p->tab = h->vr_tab;
+    p->D = h->row_len; p->tab = h->vr.dev;
 }
+void byolo_var_recal_pack(const byolo_t* h, double* tab) { vr_pack(&h->vr_cfg, tab); }
 
+// The device table of either recalibration stage (score_recal.hip's as well) brought up to date, `pack` filling t->host first.
 // The copy runs on the forward's own stream from memory the handle owns, and the stream is waited for: whatever stream the launch
 // that reads the table is enqueued on afterwards -- a caller alternates forwards over several non-blocking streams, which nothing
 // orders against the default stream -- the table is there.  (A synchronous copy on the default stream may return once the source is
 // staged, before the bytes have landed.)
-int32_t byolo_var_recal_upload(byolo_t* h, hipStream_t st) {
+int32_t byolo_recal_upload(byolo_t* h, RecalTable* t, void (*pack)(const byolo_t* h, double* tab), hipStream_t st) {
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipDeviceSynchronize());                       // a forward in flight, or a graph replaying, may still read the table
-    if (!h->vr_tab) HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->vr_tab), BYOLO_VAR_RECAL_TABLE_BYTES));
-    vr_pack(&h->vr_cfg, h->vr_host);
-    HIPCHK(h, hipMemcpyAsync(h->vr_tab, h->vr_host, sizeof h->vr_host, hipMemcpyHostToDevice, st));
+    if (!t->dev) HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&t->dev), t->bytes));
+    pack(h, t->host);
+    HIPCHK(h, hipMemcpyAsync(t->dev, t->host, t->bytes, hipMemcpyHostToDevice, st));
     HIPCHK(h, hipStreamSynchronize(st));
-    h->vr_dirty = false;
+    t->dirty = false;
     return BYOLO_OK;
 }
 
@@ -366,12 +349,20 @@ extern "C" int32_t byolo_set_var_recal(byolo_t* h, const byolo_var_recal_cfg* cf
             ++k;
         }
         h->vr_cfg = *cfg;
-        h->vr_dirty = true;
+        h->vr.dirty = true;
     }
-    h->vr_on = cfg != nullptr;
+    h->vr.on = cfg != nullptr;
     // a captured forward holds the launches of the old setting (as byolo_set_box_vote); the device table is brought up to date by the
     // next forward, behind a wait for the device, so a replay that is still running reads the table it was launched with
-    h->plan.B = -1; h->plan.T = -1; ++h->plan_epoch; h->wsm_B = -1;
+    invalidate_plan(h);
+    return BYOLO_OK;
+}
+
+int32_t byolo_recal_check_fit(const char* what, bool have_ptrs, int32_t n_seg, int64_t n, const void* d_ws, size_t ws_bytes, size_t need, const char* ws_call) {
+    if (!have_ptrs) return fail(nullptr, BYOLO_ERR_ARG, "%s: null argument", what);
+    if (n_seg < 1 || n < 0) return fail(nullptr, BYOLO_ERR_ARG, "%s: n_seg %d, n %lld", what, n_seg, (long long)n);
+    if (ws_bytes < need) return fail(nullptr, BYOLO_ERR_NOMEM, "%s: workspace %zu < %s = %zu", what, ws_bytes, ws_call, need);
+    if (reinterpret_cast<uintptr_t>(d_ws) & 7) return fail(nullptr, BYOLO_ERR_ARG, "%s: d_ws is not 8-byte aligned", what);
     return BYOLO_OK;
 }
 
@@ -380,11 +371,10 @@ extern "C" size_t byolo_var_recal_fit_workspace_bytes(int64_t n) { return n < 1 
 extern "C" int32_t byolo_var_recal_fit(const double* d_r, const double* d_v, const int64_t* d_seg, int32_t n_seg, int64_t n,
                                        int32_t method, double* d_out, void* d_ws, size_t ws_bytes, void* stream) {
     const char* what = "byolo_var_recal_fit";
-    if (!d_seg || !d_out || (n > 0 && (!d_r || !d_v || !d_ws))) return fail(nullptr, BYOLO_ERR_ARG, "%s: null argument", what);
-    if (n_seg < 1 || n < 0) return fail(nullptr, BYOLO_ERR_ARG, "%s: n_seg %d, n %lld", what, n_seg, (long long)n);
+    int32_t rc = byolo_recal_check_fit(what, d_seg && d_out && (n <= 0 || (d_r && d_v && d_ws)), n_seg, n, d_ws, ws_bytes, byolo_var_recal_fit_workspace_bytes(n),
+                                       "byolo_var_recal_fit_workspace_bytes(n)");
+    if (rc) return rc;
     if (method != BYOLO_VAR_RECAL_SCALE && method != BYOLO_VAR_RECAL_POWER) return fail(nullptr, BYOLO_ERR_ARG, "%s: unknown method %d (BYOLO_VAR_RECAL_SCALE / _POWER)", what, method);
-    if (ws_bytes < byolo_var_recal_fit_workspace_bytes(n)) return fail(nullptr, BYOLO_ERR_NOMEM, "%s: workspace %zu < byolo_var_recal_fit_workspace_bytes(n) = %zu", what, ws_bytes, byolo_var_recal_fit_workspace_bytes(n));
-    if (reinterpret_cast<uintptr_t>(d_ws) & 7) return fail(nullptr, BYOLO_ERR_ARG, "%s: d_ws is not 8-byte aligned", what);
     byk::VrFitParams p;
     p.r = d_r; p.v = d_v; p.seg = d_seg; p.n_total = n; p.method = method; p.lv = static_cast<double*>(d_ws); p.out = d_out;
     hipLaunchKernelGGL(byk::vr_fit_kernel, dim3((unsigned)n_seg), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p);

@@ -38,6 +38,12 @@ import evaluate as _evaluate
 from evaluate import MODELS
 
 
+def _check_holdout(cfg):
+    k = cfg.setdefault('recal_holdout', None)
+    if k is not None and (isinstance(k, bool) or not isinstance(k, int) or k < 2):
+        raise ValueError('recal_holdout is None or an integer >= 2 (every k-th batch is held out), not {!r}'.format(k))
+
+
 def check_config(config, model='bayesian'):
     """evaluate.check_config plus the keys of this entry point; raises ValueError on what cannot be fitted."""
     from byolo import recalibrate as rc
@@ -51,15 +57,12 @@ def check_config(config, model='bayesian'):
     cfg.setdefault('recal_by', 'prior')
     cfg.setdefault('recal_method', 'scale')
     cfg.setdefault('recal_min_n', rc.DEFAULT_MIN_N)
-    cfg.setdefault('recal_holdout', None)
     target = rc.default_target(MODELS[model]) if cfg['recal_target'] is None else cfg['recal_target']
     try:
         rc._check_settings(MODELS[model], target, cfg['recal_by'], cfg['recal_method'], cfg['recal_min_n'])
     except ValueError as e:
         raise ValueError(str(e).replace('var_recal: ', 'recal_'))
-    k = cfg['recal_holdout']
-    if k is not None and (isinstance(k, bool) or not isinstance(k, int) or k < 2):
-        raise ValueError('recal_holdout is None or an integer >= 2 (every k-th batch is held out), not {!r}'.format(k))
+    _check_holdout(cfg)
     if cfg['localisation'] is False:
         raise ValueError('recalibrate needs the localisation residuals: localisation must not be False')
     cfg['localisation'] = True
@@ -77,24 +80,23 @@ def holdout_lines(before, after, kind):
     return lines
 
 
-def recalibrate(config, model='bayesian'):
-    """Fits the calibration and writes <out_path>_<step>/var_recal.json; returns {'path', 'calibration' (the VarCalibration),
-    'images', 'holdout' ({'before', 'after'}: the localisation dicts of the held-out batches, or None)}."""
-    from byolo import inference as _inf, recalibrate as rc
-    from byolo.evaluate import Evaluator
+def _run(cfg, file_name, new_evaluator, fit, recal_rows, summarise, holdout_log):
+    """The run both fits share: the model over the labelled shards, every k-th batch (recal_holdout) to an evaluator that is not
+    fitted on, the fit, the held-out batches once more through the fitted stage, the log and <out_path>_<step>/<file_name>.  What a
+    stage brings: new_evaluator(m, for_fit), fit(m, evaluator) -> the calibration, recal_rows(m, rows, count, cal) -> the kept rows
+    recalibrated, summarise(m, ev_before, ev_after) -> the 'holdout' of the result, holdout_log(cal, holdout) -> its log lines."""
+    from byolo import inference as _inf
     from lib_yolo import dataset_utils
-    cfg = check_config(config, model)
     logging.info(json.dumps(cfg, indent=4, default=lambda x: str(x)))
     logging.info('----- START -----')
     start = time.time()
     m, checkpoint = _evaluate.build_model(cfg)
     out_path = '{}_{}'.format(cfg['out_path'], _inf.step_of(checkpoint))
     os.makedirs(out_path)                                 # like the other entry points: refuses to overwrite an existing run
-    new_ev = lambda: Evaluator(m, iou_thresh=cfg['iou_thresh'], min_score=cfg['min_score'], capacity=cfg['eval_capacity'], loc=True)
     k = cfg['recal_holdout']
-    ev_fit = new_ev()
-    ev_before, ev_after = (new_ev(), new_ev()) if k else (None, None)
-    held = []                                             # the held-out batches' kept rows and ground truth, on the device
+    ev_fit = new_evaluator(m, True)
+    ev_before, ev_after = (new_evaluator(m, False), new_evaluator(m, False)) if k else (None, None)
+    held = []                                             # the held-out batches' kept rows, counts and ground truth, on the device
     feed = dataset_utils._Feed(cfg, 'data', 'eval', device=m.engine.torch_device)
     try:
         images = 0
@@ -102,19 +104,18 @@ def recalibrate(config, model='bayesian'):
             if cfg['eval_batches'] is not None and step >= cfg['eval_batches']:
                 break
             res = m.run(b['img'], seed=int(cfg['seed']) + step, want_boxes=False)
-            args = (res['rows'], res['count'][:, 0], b['boxes'], b['labels'], b['counts'])
-            if k and step % k == k - 1:
-                ev_before.add(*args)
+            args = (res['rows'], res['count'], b['boxes'], b['labels'], b['counts'])
+            hold = k and step % k == k - 1
+            (ev_before if hold else ev_fit).add(args[0], args[1][:, 0], *args[2:])
+            if hold:
                 held.append(args[:2] + tuple(x.clone() if hasattr(x, 'clone') else np.array(x) for x in args[2:]))      # (the feed owns its arrays)
-            else:
-                ev_fit.add(*args)
             images += int(b['img'].shape[0])
-        cal = rc.fit(ev_fit, target=cfg['recal_target'], by=cfg['recal_by'], method=cfg['recal_method'], min_n=int(cfg['recal_min_n']))
+        cal = fit(m, ev_fit)
         holdout = None
         if k:
             for rows, count, gb, gl, gc in held:
-                ev_after.add(m.engine.var_recal(rows, cal), count, gb, gl, gc)
-            holdout = {'before': ev_before.finish()['localisation'], 'after': ev_after.finish()['localisation']}
+                ev_after.add(recal_rows(m, rows, count, cal), count[:, 0], gb, gl, gc)
+            holdout = summarise(m, ev_before, ev_after)
     finally:
         feed.close()
         for e in (ev_fit, ev_before, ev_after):
@@ -123,15 +124,30 @@ def recalibrate(config, model='bayesian'):
     for line in cal.log_lines():
         logging.info(line)
     if holdout is not None:
-        for line in holdout_lines(holdout['before'], holdout['after'], cal.target):
+        for line in holdout_log(cal, holdout):
             logging.info(line)
-    path = os.path.join(out_path, 'var_recal.json')
+    path = os.path.join(out_path, file_name)
     cal.save(path)
     logging.info('wrote {} ({} images, {} of them held out)'.format(path, images, sum(int(h[0].shape[0]) for h in held)))
     elapsed = int(time.time() - start)
     logging.info('----- FINISHED in {:02d}:{:02d}:{:02d} -----'.format(elapsed // 3600, (elapsed // 60) % 60, elapsed % 60))
     m.engine.close()
     return {'path': path, 'calibration': cal, 'images': images, 'holdout': holdout}
+
+
+def recalibrate(config, model='bayesian'):
+    """Fits the calibration and writes <out_path>_<step>/var_recal.json; returns {'path', 'calibration' (the VarCalibration),
+    'images', 'holdout' ({'before', 'after'}: the localisation dicts of the held-out batches, or None)}."""
+    from byolo import recalibrate as rc
+    from byolo.evaluate import Evaluator
+    cfg = check_config(config, model)
+    return _run(
+        cfg, 'var_recal.json',
+        lambda m, for_fit: Evaluator(m, iou_thresh=cfg['iou_thresh'], min_score=cfg['min_score'], capacity=cfg['eval_capacity'], loc=True),
+        lambda m, ev: rc.fit(ev, target=cfg['recal_target'], by=cfg['recal_by'], method=cfg['recal_method'], min_n=int(cfg['recal_min_n'])),
+        lambda m, rows, count, cal: m.engine.var_recal(rows, cal),
+        lambda m, before, after: {'before': before.finish()['localisation'], 'after': after.finish()['localisation']},
+        lambda cal, holdout: holdout_lines(holdout['before'], holdout['after'], cal.target))
 
 
 def check_score_config(config, model='bayesian'):
@@ -145,15 +161,12 @@ def check_score_config(config, model='bayesian'):
     cfg.setdefault('score_recal_by', 'all')
     cfg.setdefault('score_recal_l2', sr.DEFAULT_L2)
     cfg.setdefault('score_recal_min_n', sr.DEFAULT_MIN_N)
-    cfg.setdefault('recal_holdout', None)
     try:
         sr.ScoreCalibration(MODELS[model], int(cfg['cls_cnt']), cfg['score_recal_features'], cfg['score_recal_by'], l2=cfg['score_recal_l2'],
                             min_n=cfg['score_recal_min_n'])
     except ValueError as e:
         raise ValueError(str(e).replace('score_recal: ', 'score_recal_'))
-    k = cfg['recal_holdout']
-    if k is not None and (isinstance(k, bool) or not isinstance(k, int) or k < 2):
-        raise ValueError('recal_holdout is None or an integer >= 2 (every k-th batch is held out), not {!r}'.format(k))
+    _check_holdout(cfg)
     return cfg
 
 
@@ -179,62 +192,27 @@ def recalibrate_score(config, model='bayesian'):
     """`--what score`: fits a score recalibration (byolo/score_recal.py) and writes <out_path>_<step>/score_recal.json; returns
     {'path', 'calibration' (the ScoreCalibration), 'images', 'holdout' ({'before', 'after'}: the result dicts of the held-out
     batches with 'brier' added per class, or None)}."""
-    from byolo import inference as _inf, score_recal as sr
+    from byolo import score_recal as sr
     from byolo.evaluate import Evaluator
-    from lib_yolo import dataset_utils
     cfg = check_score_config(config, model)
-    logging.info(json.dumps(cfg, indent=4, default=lambda x: str(x)))
-    logging.info('----- START -----')
-    start = time.time()
-    m, checkpoint = _evaluate.build_model(cfg)
-    out_path = '{}_{}'.format(cfg['out_path'], _inf.step_of(checkpoint))
-    os.makedirs(out_path)
-    kw = dict(iou_thresh=cfg['iou_thresh'], min_score=cfg['min_score'], capacity=cfg['eval_capacity'], device=m.engine.torch_device, loc=False)
-    k = cfg['recal_holdout']
-    ev_fit = Evaluator(sr.eval_layout(m), **kw)                # its records also carry ymin / ymax, which 'log_height' reads
-    ev_before, ev_after = (Evaluator(m, **kw), Evaluator(m, **kw)) if k else (None, None)
-    held = []
-    feed = dataset_utils._Feed(cfg, 'data', 'eval', device=m.engine.torch_device)
-    try:
-        images = 0
-        for step, b in enumerate(feed):
-            if cfg['eval_batches'] is not None and step >= cfg['eval_batches']:
-                break
-            res = m.run(b['img'], seed=int(cfg['seed']) + step, want_boxes=False)
-            args = (res['rows'], res['count'], b['boxes'], b['labels'], b['counts'])
-            if k and step % k == k - 1:
-                ev_before.add(args[0], args[1][:, 0], *args[2:])
-                held.append(args[:2] + tuple(x.clone() if hasattr(x, 'clone') else np.array(x) for x in args[2:]))
-            else:
-                ev_fit.add(args[0], args[1][:, 0], *args[2:])
-            images += int(b['img'].shape[0])
-        cal = sr.fit(ev_fit, cfg['score_recal_features'], cfg['score_recal_by'], float(cfg['score_recal_l2']), int(cfg['score_recal_min_n']),
-                     fitted_under=sr.fitted_under(m.engine))
-        holdout = None
-        if k:
-            for rows, count, gb, gl, gc in held:
-                ev_after.add(m.engine.score_recal(rows, count, cal)['rows'], count[:, 0], gb, gl, gc)
-            holdout = {'before': ev_before.finish(), 'after': ev_after.finish()}
-            for name, e in (('before', ev_before), ('after', ev_after)):
-                for c, br in zip(holdout[name]['classes'], _brier(e, m.cls_cnt)):
-                    c['brier'] = br
-    finally:
-        feed.close()
-        for e in (ev_fit, ev_before, ev_after):
-            if e is not None:
-                e.close()
-    for line in cal.log_lines():
-        logging.info(line)
-    if holdout is not None:
-        for line in score_holdout_lines(holdout['before'], holdout['after']):
-            logging.info(line)
-    path = os.path.join(out_path, 'score_recal.json')
-    cal.save(path)
-    logging.info('wrote {} ({} images, {} of them held out)'.format(path, images, sum(int(h[0].shape[0]) for h in held)))
-    elapsed = int(time.time() - start)
-    logging.info('----- FINISHED in {:02d}:{:02d}:{:02d} -----'.format(elapsed // 3600, (elapsed // 60) % 60, elapsed % 60))
-    m.engine.close()
-    return {'path': path, 'calibration': cal, 'images': images, 'holdout': holdout}
+
+    def new_evaluator(m, for_fit):                             # the records fitted on also carry ymin / ymax, which 'log_height' reads
+        return Evaluator(sr.eval_layout(m) if for_fit else m, iou_thresh=cfg['iou_thresh'], min_score=cfg['min_score'], capacity=cfg['eval_capacity'],
+                         device=m.engine.torch_device, loc=False)
+
+    def summarise(m, before, after):
+        holdout = {'before': before.finish(), 'after': after.finish()}
+        for name, e in (('before', before), ('after', after)):
+            for c, br in zip(holdout[name]['classes'], _brier(e, m.cls_cnt)):
+                c['brier'] = br
+        return holdout
+
+    return _run(
+        cfg, 'score_recal.json', new_evaluator,
+        lambda m, ev: sr.fit(ev, cfg['score_recal_features'], cfg['score_recal_by'], float(cfg['score_recal_l2']), int(cfg['score_recal_min_n']),
+                             fitted_under=sr.fitted_under(m.engine)),
+        lambda m, rows, count, cal: m.engine.score_recal(rows, count, cal)['rows'], summarise,
+        lambda cal, holdout: score_holdout_lines(holdout['before'], holdout['after']))
 
 
 def main(argv=None):
