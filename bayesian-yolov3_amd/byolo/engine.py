@@ -309,13 +309,15 @@ class Engine:
     def out_cap(self):
         return self.nms_cap(self.cfg.nms_mode, self.cfg.max_out, self.cfg.cls_cnt)
 
+    def _side_out(self, call, B, cols, dtype, device, stream):
+        """[B, cols] that the handle's last call left for the getter `call`, copied out behind it on `stream`."""
+        t = _torch().empty((B, cols), dtype=dtype, device=device)
+        check(self._h, call(self._h, ctypes.c_void_p(t.data_ptr()), int(B), int(cols), ctypes.c_void_p(stream)))
+        return t
+
     def _class_counts(self, B, device, stream):
-        """[B, cls_cnt] int32: kept per class of the handle's last per-class NMS, enqueued behind it on `stream`."""
-        torch = _torch()
-        cc = torch.empty((B, self.cfg.cls_cnt), dtype=torch.int32, device=device)
-        check(self._h, lib.byolo_nms_class_counts(self._h, ctypes.c_void_p(cc.data_ptr()), int(B), int(self.cfg.cls_cnt),
-                                                  ctypes.c_void_p(stream)))
-        return cc
+        """[B, cls_cnt] int32: kept per class of the handle's last per-class NMS."""
+        return self._side_out(lib.byolo_nms_class_counts, B, self.cfg.cls_cnt, _torch().int32, device, stream)
 
     # ---- run ------------------------------------------------------------------------------------------
     def _workspace(self, B, T, slot=0):
@@ -441,16 +443,14 @@ class Engine:
                                          int(bool(dropout_on)), p(mask_bits), p(ws), ws.numel(), p(boxes), p(rows), p(kept),
                                          p(count), ctypes.c_void_p(stream)))
         res = dict(boxes=boxes, rows=rows, kept=kept, count=count)
-        if want_nms and self.cfg.nms_mode == _lib.NMS_PER_CLASS:
-            res["class_counts"] = self._class_counts(B, dev, stream)
-        if want_nms and self._box_vote is not None:       # 'rows' are the voted rows (byolo_set_box_vote)
-            vn = torch.empty((B, self.out_cap), dtype=torch.int32, device=dev)
-            check(self._h, lib.byolo_box_vote_counts(self._h, ctypes.c_void_p(vn.data_ptr()), B, self.out_cap, ctypes.c_void_p(stream)))
-            res["vote_n"] = vn
-        if want_nms and self._score_recal is not None:    # 'rows' carry the calibrated score in obj (byolo_set_score_recal)
-            sc = torch.empty((B, self.out_cap), dtype=torch.float32, device=dev)
-            check(self._h, lib.byolo_score_recal_scores(self._h, ctypes.c_void_p(sc.data_ptr()), B, self.out_cap, ctypes.c_void_p(stream)))
-            res["score"] = sc
+        # what the stages around the NMS leave per image: (key, active, getter, dtype, columns).  With vote_n 'rows' are the voted rows
+        # (byolo_set_box_vote), with score they carry the calibrated score in obj (byolo_set_score_recal)
+        for key, on, call, dtype, cols in (
+                ("class_counts", self.cfg.nms_mode == _lib.NMS_PER_CLASS, lib.byolo_nms_class_counts, torch.int32, self.cfg.cls_cnt),
+                ("vote_n", self._box_vote is not None, lib.byolo_box_vote_counts, torch.int32, self.out_cap),
+                ("score", self._score_recal is not None, lib.byolo_score_recal_scores, torch.float32, self.out_cap)):
+            if want_nms and on:
+                res[key] = self._side_out(call, B, cols, dtype, dev, stream)
         return res
 
     # ---- variance voting (include/byolo.h "variance voting") ---------------------------------

@@ -245,12 +245,10 @@ extern "C" int32_t byolo_box_vote(byolo_t* h, const float* d_boxes, int32_t B, i
                                   void* d_ws, size_t ws_bytes, void* stream) {
     const char* what = "byolo_box_vote";
     if (!h || !d_boxes || !cfg || !d_rows_in || !d_kept || !d_count || !d_rows_out || !d_vote_n || !d_ws) return fail(h, BYOLO_ERR_ARG, "%s: null argument", what);
-    if (B < 1 || B > 65535 || N < 1 || N >= (1ll << 31) || D < 5 || obj_idx < 4 || obj_idx >= D || cap < 1) return fail(h, BYOLO_ERR_ARG, "%s: bad shape", what);
-    if (nms_mode < BYOLO_NMS_AGNOSTIC || nms_mode > BYOLO_NMS_PER_CLASS) return fail(h, BYOLO_ERR_ARG, "%s: unknown nms_mode %d", what, nms_mode);
-    const int32_t C = nms_classes(nms_mode, h->cfg.cls_cnt);
-    if (C < 1 || C > BYOLO_NMS_MAX_CLASSES) return fail(h, BYOLO_ERR_ARG, "%s: 1 .. %d classes", what, BYOLO_NMS_MAX_CLASSES);
-    if (C > 1 && (cls_start_idx < 0 || (int64_t)cls_start_idx + C > D)) return fail(h, BYOLO_ERR_ARG, "%s: bad cls_start_idx (class columns outside the row)", what);
-    int32_t rc = vote_check_settings(h, cfg, what); if (rc) return rc;
+    int32_t C = 0;
+    int32_t rc = check_rows_shape(h, what, B, 65535, N, D, obj_idx, cls_start_idx, nms_mode, &C); if (rc) return rc;
+    if (cap < 1) return fail(h, BYOLO_ERR_ARG, "%s: bad shape", what);
+    rc = vote_check_settings(h, cfg, what); if (rc) return rc;
     rc = vote_check_columns(h, cfg->var, cfg->ale_col, cfg->epi_col, D, what); if (rc) return rc;
     VoteParams p; memset(&p, 0, sizeof p);
     if (cfg->var != BYOLO_VOTE_NONE) { rc = vote_check_geom(h, geom, D, &p.geom, what); if (rc) return rc; }
@@ -308,7 +306,7 @@ extern "C" int32_t byolo_set_box_vote(byolo_t* h, const byolo_vote_cfg* cfg) {
         h->vote_cfg = *cfg;
     }
     h->vote_on = cfg != nullptr;
-    h->vn_ptr = nullptr;
+    side_out_forget(&h->out_vote_n);
     // the stage's workspace is part of the plan, and a captured forward holds the launches of the old setting
     invalidate_plan(h);
     return BYOLO_OK;
@@ -316,9 +314,6 @@ extern "C" int32_t byolo_set_box_vote(byolo_t* h, const byolo_vote_cfg* cfg) {
 
 extern "C" int32_t byolo_box_vote_counts(byolo_t* h, int32_t* d_vote_n, int32_t B, int32_t cap, void* stream) {
     if (!h || !d_vote_n) return fail(h, BYOLO_ERR_ARG, "byolo_box_vote_counts: null argument");
-    if (!h->vn_ptr) return fail(h, BYOLO_ERR_STATE, "byolo_box_vote_counts: no byolo_forward with box voting (byolo_set_box_vote) and d_rows has run on this handle");
-    if (B != h->vn_B || cap != h->vn_cap) return fail(h, BYOLO_ERR_ARG, "byolo_box_vote_counts: the last voting forward ran [%d, %d], asked for [%d, %d]", h->vn_B, h->vn_cap, B, cap);
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipMemcpyAsync(d_vote_n, h->vn_ptr, (size_t)B * cap * sizeof(int32_t), hipMemcpyDeviceToDevice, reinterpret_cast<hipStream_t>(stream)));
-    return BYOLO_OK;
+    if (!h->out_vote_n.ptr) return fail(h, BYOLO_ERR_STATE, "byolo_box_vote_counts: no byolo_forward with box voting (byolo_set_box_vote) and d_rows has run on this handle");
+    return side_out_copy(h, &h->out_vote_n, d_vote_n, B, cap, "byolo_box_vote_counts", stream);
 }

@@ -153,11 +153,9 @@ extern "C" int32_t byolo_destroy(byolo_t* h) {
         if (h->d_zeros) (void)hipFree(h->d_zeros);
         if (h->ev_convs) (void)hipEventDestroy(h->ev_convs);
         if (h->d_status) (void)hipFree(h->d_status);
-        if (h->pc_own) (void)hipFree(h->pc_own);
-        if (h->vn_own) (void)hipFree(h->vn_own);
+        for (SideOut* s : {&h->out_class_counts, &h->out_vote_n, &h->out_score}) side_out_free(s);
         if (h->vr.dev) (void)hipFree(h->vr.dev);
         if (h->sr.dev) (void)hipFree(h->sr.dev);
-        if (h->sr_own) (void)hipFree(h->sr_own);
         if (h->h_status) (void)hipHostFree(h->h_status);
         for (auto& ps : h->prof) {
             for (auto& e : ps.ev) if (e) (void)hipEventDestroy(e);
@@ -875,6 +873,14 @@ static int32_t range_error(byolo_t* h, const char* what, unsigned flags, unsigne
                     "tensor (lib_yolo/layers.py:550) holds it -- run this model with byolo_set_precision(BYOLO_PREC_F32)", what, layer, scope, 65504.0 / ACT_SCALE);
     return fail(h, BYOLO_ERR_RANGE, "%s: a raw detection output is inf / NaN (non-finite activations upstream, or weights the float32 reference overflows on as well)", what);
 }
+// Wait for `st` and read the status words; a raised status is an ERROR named after `what`, and the words are cleared for the next call
+static int32_t check_range_status(byolo_t* h, hipStream_t st, const char* what) {
+    unsigned f = 0, ly = 0xFFFFFFFFu;
+    int32_t rc = read_status(h, st, &f, &ly); if (rc) return rc;
+    if (!f) return BYOLO_OK;
+    (void)byolo_clear_status(h, st);
+    return range_error(h, what, f, ly);
+}
 
 extern "C" int32_t byolo_set_async(byolo_t* h, int32_t on) {
     if (!h) return fail(nullptr, BYOLO_ERR_ARG, "byolo_set_async: null handle");
@@ -925,128 +931,122 @@ extern "C" int32_t byolo_normalize_u8(byolo_t* h, const uint8_t* d_u8, int64_t n
 
 extern "C" const char* byolo_precision_note(const byolo_t* h) { return h ? h->prec_note.c_str() : ""; }
 
-static int32_t forward_piece(byolo_t* h, const float* d_img, int32_t B, int32_t T, uint64_t seed, int32_t dropout_on,
-                             const uint32_t* d_mask_bits, void* d_workspace, size_t workspace_bytes, float* d_boxes, float* d_rows,
-                             int32_t* d_kept, int32_t* d_count, void* stream);
 static SoftNmsParams soft_params(const byolo_soft_nms_cfg& c);
+// The arguments of one byolo_forward call, from the ABI boundary down
 struct FwdArgs { const float* d_img; int32_t B, T; uint64_t seed; int32_t dropout_on; const uint32_t* d_mask_bits; void* d_workspace;
                  float* d_boxes; float* d_rows; int32_t* d_kept; int32_t* d_count; };
+static int32_t forward_piece(byolo_t* h, FwdArgs a, size_t workspace_bytes, hipStream_t st);
 static int32_t enqueue_forward(byolo_t* h, const FwdArgs& a, hipStream_t st, bool capturing, bool wait_convs, bool heads_only = false);
-static int32_t finish_forward(byolo_t* h, hipStream_t st, void* stream);
+static int32_t enqueue_tail(byolo_t* h, const FwdArgs& a, char* ws, hipStream_t st);
+static int32_t finish_forward(byolo_t* h, hipStream_t st);
 static int32_t forward_graph(byolo_t* h, const FwdArgs& a, hipStream_t st, bool* done);
+
+// Images [lo, lo + n) of call `a` as a call of their own in the same workspace (an output the caller did not ask for stays null);
+// without injected masks, which describe ONE piece
+static FwdArgs piece_args(const byolo_t* h, const FwdArgs& a, int64_t lo, int32_t n) {
+    const size_t i = (size_t)lo, cap = (size_t)nms_out_cap(h);
+    FwdArgs p = a;
+    p.B = n; p.d_mask_bits = nullptr;
+    if (a.d_img) p.d_img = a.d_img + i * h->cfg.img_h * h->cfg.img_w * h->cfg.img_c;
+    if (a.d_boxes) p.d_boxes = a.d_boxes + i * h->n_boxes * h->row_len;
+    if (a.d_rows) p.d_rows = a.d_rows + i * cap * h->row_len;
+    if (a.d_kept) p.d_kept = a.d_kept + i * cap;
+    if (a.d_count) p.d_count = a.d_count + i * 2;
+    return p;
+}
+
+// side output `s` sits in a buffer of the handle's own for B images (a forward that runs in pieces)
+static int32_t side_out_reserve(byolo_t* h, SideOut* s, int32_t B, int32_t cols) {
+    const size_t bytes = (size_t)B * cols * SIDE_OUT_EL;
+    if (s->own_bytes >= bytes) return BYOLO_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (s->own) { HIPCHK(h, hipDeviceSynchronize()); HIPCHK(h, hipFree(s->own)); s->own = nullptr; s->own_bytes = 0; }
+    HIPCHK(h, hipMalloc(&s->own, bytes));
+    s->own_bytes = bytes;
+    return BYOLO_OK;
+}
+// ... and the piece that just pointed `s` into the shared workspace, images from `lo` on, is copied behind itself
+static int32_t side_out_keep_piece(byolo_t* h, const SideOut* s, int64_t lo, const char* what, hipStream_t st) {
+    const hipError_t e = hipMemcpyAsync(static_cast<char*>(s->own) + (size_t)lo * s->cols * SIDE_OUT_EL, s->ptr, (size_t)s->B * s->cols * SIDE_OUT_EL, hipMemcpyDeviceToDevice, st);
+    return e == hipSuccess ? BYOLO_OK : fail(h, BYOLO_ERR_HIP, "byolo_forward: %s of a piece: %s", what, hipGetErrorString(e));
+}
+int32_t side_out_copy(byolo_t* h, const SideOut* s, void* d_dst, int32_t B, int32_t cols, const char* what, void* stream) {
+    if (B != s->B || cols != s->cols) return fail(h, BYOLO_ERR_ARG, "%s: [%d, %d] asked for, the last call left [%d, %d]", what, B, cols, s->B, s->cols);
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipMemcpyAsync(d_dst, s->ptr, (size_t)B * cols * SIDE_OUT_EL, hipMemcpyDeviceToDevice, reinterpret_cast<hipStream_t>(stream)));
+    return BYOLO_OK;
+}
 
 // A batch beyond byolo_max_images(h, T) -- the convolutions address their sources with 32-bit byte offsets -- runs as consecutive
 // pieces of at most that many images in the SAME workspace: images are independent end to end (the NMS is per image) and every
 // piece draws the dropout masks of its position in the logical batch (first_image), so the result does not depend on the cut.
-static int32_t forward_impl(byolo_t* h, const float* d_img, int32_t B, int32_t T, uint64_t seed, int32_t dropout_on,
-                                 const uint32_t* d_mask_bits, void* d_workspace, size_t workspace_bytes, float* d_boxes, float* d_rows,
-                                 int32_t* d_kept, int32_t* d_count, void* stream) {
-    if (h && h->finalized && B >= 1 && T >= 1) {
+static int32_t forward_impl(byolo_t* h, const FwdArgs& a, size_t workspace_bytes, hipStream_t st) {
+    if (h && h->finalized && a.B >= 1 && a.T >= 1) {
         if (!h->lowered) { int32_t rc = lower(h); if (rc) return rc; }
-        const int64_t cap = piece_cap(h, T);
-        if (cap >= 1 && B > cap) {
-            if (d_mask_bits && dropout_on)
-                return fail(h, BYOLO_ERR_ARG, "byolo_forward: injected masks describe ONE piece: keep B <= byolo_max_images (%lld at T = %d)", (long long)cap, T);
+        const int64_t cap = piece_cap(h, a.T);
+        if (cap >= 1 && a.B > cap) {
+            if (a.d_mask_bits && a.dropout_on)
+                return fail(h, BYOLO_ERR_ARG, "byolo_forward: injected masks describe ONE piece: keep B <= byolo_max_images (%lld at T = %d)", (long long)cap, a.T);
             const int64_t first = h->first_image;
-            const size_t img_el = (size_t)h->cfg.img_h * h->cfg.img_w * h->cfg.img_c;
-            const bool per_class = h->cfg.nms_mode == BYOLO_NMS_PER_CLASS && d_rows;
-            const size_t out_cap = (size_t)h->cfg.max_out * (h->cfg.nms_mode == BYOLO_NMS_TWO_CLASS ? 2 : h->cfg.nms_mode == BYOLO_NMS_PER_CLASS ? h->cfg.cls_cnt : 1);
-            // the pieces share one workspace, so each piece's per-class counts are copied out behind it (byolo_nms_class_counts)
-            const size_t cc = (size_t)h->cfg.cls_cnt;
-            if (per_class && h->pc_own_cap < (size_t)B * cc) {
-                HIPCHK(h, hipSetDevice(h->device));
-                if (h->pc_own) { HIPCHK(h, hipDeviceSynchronize()); HIPCHK(h, hipFree(h->pc_own)); h->pc_own = nullptr; h->pc_own_cap = 0; }
-                HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->pc_own), (size_t)B * cc * sizeof(int32_t)));
-                h->pc_own_cap = (size_t)B * cc;
-            }
-            const bool voting = h->vote_on && d_rows;
-            if (voting && h->vn_own_cap < (size_t)B * out_cap) {
-                HIPCHK(h, hipSetDevice(h->device));
-                if (h->vn_own) { HIPCHK(h, hipDeviceSynchronize()); HIPCHK(h, hipFree(h->vn_own)); h->vn_own = nullptr; h->vn_own_cap = 0; }
-                HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->vn_own), (size_t)B * out_cap * sizeof(int32_t)));
-                h->vn_own_cap = (size_t)B * out_cap;
-            }
-            const bool scoring = h->sr.on && d_rows;
-            if (scoring && h->sr_own_cap < (size_t)B * out_cap) {
-                HIPCHK(h, hipSetDevice(h->device));
-                if (h->sr_own) { HIPCHK(h, hipDeviceSynchronize()); HIPCHK(h, hipFree(h->sr_own)); h->sr_own = nullptr; h->sr_own_cap = 0; }
-                HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->sr_own), (size_t)B * out_cap * sizeof(float)));
-                h->sr_own_cap = (size_t)B * out_cap;
-            }
+            // the pieces share one workspace, so each piece's side outputs are copied out behind it, for their getters
+            const bool nms = a.d_rows != nullptr;
+            const struct { SideOut* s; bool on; int32_t cols; const char* what; } side[3] = {
+                {&h->out_class_counts, nms && h->cfg.nms_mode == BYOLO_NMS_PER_CLASS, h->cfg.cls_cnt, "per-class counts"},
+                {&h->out_vote_n, nms && h->vote_on, (int32_t)nms_out_cap(h), "vote counts"},
+                {&h->out_score, nms && h->sr.on, (int32_t)nms_out_cap(h), "calibrated scores"}};
             int32_t rc = BYOLO_OK;
-            for (int64_t lo = 0; lo < B && rc == BYOLO_OK; lo += cap) {
-                const int32_t n = (int32_t)std::min<int64_t>(cap, B - lo);
+            for (const auto& o : side) if (o.on) { rc = side_out_reserve(h, o.s, a.B, o.cols); if (rc) return rc; }
+            for (int64_t lo = 0; lo < a.B && rc == BYOLO_OK; lo += cap) {
                 h->first_image = first + lo;
-                rc = forward_piece(h, d_img ? d_img + lo * img_el : nullptr, n, T, seed, dropout_on, nullptr, d_workspace, workspace_bytes,
-                                   d_boxes ? d_boxes + (size_t)lo * h->n_boxes * h->row_len : nullptr,
-                                   d_rows ? d_rows + (size_t)lo * out_cap * h->row_len : nullptr, d_kept ? d_kept + (size_t)lo * out_cap : nullptr,
-                                   d_count ? d_count + (size_t)lo * 2 : nullptr, stream);
-                if (rc == BYOLO_OK && per_class) {
-                    const hipError_t e = hipMemcpyAsync(h->pc_own + (size_t)lo * cc, h->pc_counts, (size_t)n * cc * sizeof(int32_t),
-                                                        hipMemcpyDeviceToDevice, reinterpret_cast<hipStream_t>(stream));
-                    if (e != hipSuccess) rc = fail(h, BYOLO_ERR_HIP, "byolo_forward: per-class counts of a piece: %s", hipGetErrorString(e));
-                }
-                if (rc == BYOLO_OK && voting) {
-                    const hipError_t e = hipMemcpyAsync(h->vn_own + (size_t)lo * out_cap, h->vn_ptr, (size_t)n * out_cap * sizeof(int32_t),
-                                                        hipMemcpyDeviceToDevice, reinterpret_cast<hipStream_t>(stream));
-                    if (e != hipSuccess) rc = fail(h, BYOLO_ERR_HIP, "byolo_forward: vote counts of a piece: %s", hipGetErrorString(e));
-                }
-                if (rc == BYOLO_OK && scoring) {
-                    const hipError_t e = hipMemcpyAsync(h->sr_own + (size_t)lo * out_cap, h->sr_ptr, (size_t)n * out_cap * sizeof(float),
-                                                        hipMemcpyDeviceToDevice, reinterpret_cast<hipStream_t>(stream));
-                    if (e != hipSuccess) rc = fail(h, BYOLO_ERR_HIP, "byolo_forward: calibrated scores of a piece: %s", hipGetErrorString(e));
-                }
+                rc = forward_piece(h, piece_args(h, a, lo, (int32_t)std::min<int64_t>(cap, a.B - lo)), workspace_bytes, st);
+                for (const auto& o : side) if (rc == BYOLO_OK && o.on) rc = side_out_keep_piece(h, o.s, lo, o.what, st);
             }
-            if (rc == BYOLO_OK && scoring) { h->sr_ptr = h->sr_own; h->sr_B = B; }
-            if (rc == BYOLO_OK && per_class) { h->pc_counts = h->pc_own; h->pc_B = B; }
-            if (rc == BYOLO_OK && voting) { h->vn_ptr = h->vn_own; h->vn_B = B; }
+            for (const auto& o : side) if (rc == BYOLO_OK && o.on) side_out_adopt(o.s, a.B);
             h->first_image = first;
             return rc;
         }
     }
-    return forward_piece(h, d_img, B, T, seed, dropout_on, d_mask_bits, d_workspace, workspace_bytes, d_boxes, d_rows, d_kept, d_count, stream);
+    return forward_piece(h, a, workspace_bytes, st);
 }
 extern "C" int32_t byolo_forward(byolo_t* h, const float* d_img, int32_t B, int32_t T, uint64_t seed, int32_t dropout_on,
                                  const uint32_t* d_mask_bits, void* d_workspace, size_t workspace_bytes, float* d_boxes, float* d_rows,
                                  int32_t* d_kept, int32_t* d_count, void* stream) {
-    return guarded(h, "byolo_forward", [&] { return forward_impl(h, d_img, B, T, seed, dropout_on, d_mask_bits, d_workspace, workspace_bytes, d_boxes, d_rows, d_kept, d_count, stream); });
+    const FwdArgs a{d_img, B, T, seed, dropout_on, d_mask_bits, d_workspace, d_boxes, d_rows, d_kept, d_count};
+    return guarded(h, "byolo_forward", [&] { return forward_impl(h, a, workspace_bytes, reinterpret_cast<hipStream_t>(stream)); });
 }
 
-static int32_t forward_piece(byolo_t* h, const float* d_img, int32_t B, int32_t T, uint64_t seed, int32_t dropout_on,
-                             const uint32_t* d_mask_bits, void* d_workspace, size_t workspace_bytes, float* d_boxes, float* d_rows,
-                             int32_t* d_kept, int32_t* d_count, void* stream) {
+static int32_t forward_piece(byolo_t* h, FwdArgs a, size_t workspace_bytes, hipStream_t st) {
+    const int32_t B = a.B, T = a.T;
+    void* const d_workspace = a.d_workspace; float* const d_boxes = a.d_boxes; float* const d_rows = a.d_rows;
     int32_t rc = check_run(h, B, T, "byolo_forward"); if (rc) return rc;
-    if (!d_img || !d_workspace) return fail(h, BYOLO_ERR_ARG, "byolo_forward: null image or workspace");
-    if ((d_rows || d_kept || d_count) && !(d_rows && d_kept && d_count))
+    if (!a.d_img || !d_workspace) return fail(h, BYOLO_ERR_ARG, "byolo_forward: null image or workspace");
+    if ((d_rows || a.d_kept || a.d_count) && !(d_rows && a.d_kept && a.d_count))
         return fail(h, BYOLO_ERR_ARG, "byolo_forward: d_rows, d_kept and d_count go together");
-    const bool inject = d_mask_bits != nullptr && dropout_on;
+    const bool inject = a.d_mask_bits != nullptr && a.dropout_on;
     // rate 0 (any rate whose 16-bit threshold is 2^16): the layer is the identity, as tf.layers.dropout(rate=0) is (byolo_rng.h);
     // injected bits are applied whatever the rate
-    if (dropout_on && !inject && byolo_drop_is_identity((double)h->cfg.drop_prob)) dropout_on = 0;
+    if (a.dropout_on && !inject && byolo_drop_is_identity((double)h->cfg.drop_prob)) a.dropout_on = 0;
     make_plan(h, B, T, inject);
     if (workspace_bytes < h->plan.total)
         return fail(h, BYOLO_ERR_NOMEM, "byolo_forward: workspace %zu < required %zu bytes", workspace_bytes, h->plan.total);
     HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    char* const ws = static_cast<char*>(d_workspace);
     h->last_ws = d_workspace;
     if (d_rows && h->cfg.nms_mode == BYOLO_NMS_PER_CLASS) {
         // refused before anything is enqueued (a replayed graph never comes back through enqueue_forward)
         if (h->cls_start + h->cfg.cls_cnt > h->row_len) return fail(h, BYOLO_ERR_ARG, "byolo_forward: per-class NMS: class columns outside the row");
-        h->pc_counts = h->soft_on ? soft_nms_class_counts_ptr(static_cast<char*>(d_workspace) + h->plan.soft_off, B, h->n_boxes, h->cfg.cls_cnt)
-                                  : nms_class_counts_ptr(static_cast<char*>(d_workspace) + h->plan.nms_off, B, h->n_boxes, h->cfg.cls_cnt);
-        h->pc_B = B; h->pc_C = h->cfg.cls_cnt;
+        side_out_point(&h->out_class_counts, h->soft_on ? soft_nms_class_counts_ptr(ws + h->plan.soft_off, B, h->n_boxes, h->cfg.cls_cnt)
+                                                        : nms_class_counts_ptr(ws + h->plan.nms_off, B, h->n_boxes, h->cfg.cls_cnt), B, h->cfg.cls_cnt);
     }
     if (d_rows && h->vote_on) {                             // refused here as well: a variance kind the handle's rows do not have
         VoteParams v;
         rc = byolo_vote_from_handle(h, &v, "byolo_forward"); if (rc) return rc;
-        h->vn_ptr = reinterpret_cast<const int32_t*>(static_cast<char*>(d_workspace) + h->plan.vote_n_off);
-        h->vn_B = B; h->vn_cap = (int32_t)nms_out_cap(h);
+        side_out_point(&h->out_vote_n, ws + h->plan.vote_n_off, B, (int32_t)nms_out_cap(h));
     }
     if (h->vr.on && h->vr.dirty) { rc = byolo_recal_upload(h, &h->vr, byolo_var_recal_pack, st); if (rc) return rc; }      // once per byolo_set_var_recal, in front of any capture
     if (d_rows && h->sr.on) {
         if (h->sr.dirty) { rc = byolo_recal_upload(h, &h->sr, byolo_score_recal_pack, st); if (rc) return rc; }           // likewise once per byolo_set_score_recal
-        h->sr_ptr = reinterpret_cast<const float*>(static_cast<char*>(d_workspace) + h->plan.score_off);
-        h->sr_B = B; h->sr_cap = (int32_t)nms_out_cap(h);
+        side_out_point(&h->out_score, ws + h->plan.score_off, B, (int32_t)nms_out_cap(h));
     }
     // (see ev_convs)  Only where a forward fills the chip by itself: a small one -- 8 images at 416 x 416 are 0.5 TFLOP in launches of
     // a few dozen tiles -- gains from running beside the next (config 2: 2480 img/s one after the other, 3110 side by side).
@@ -1059,7 +1059,6 @@ static int32_t forward_piece(byolo_t* h, const float* d_img, int32_t B, int32_t 
     if (h->tshard_T > 0)
         for (const auto& l : h->layers)
             if (l.op == OP_DETECTION && l.det_kind != BYOLO_DET_EPISTEMIC) return fail(h, BYOLO_ERR_ARG, "T sharding (byolo_set_tshard) is defined for epistemic detection layers");
-    const FwdArgs a{d_img, B, T, seed, dropout_on, d_mask_bits, d_workspace, d_boxes, d_rows, d_kept, d_count};
     // Launch-graph replay (include/byolo.h byolo_plan_opts.graphs): a forward that does NOT fill the chip by itself (below the
     // `serialize` threshold: detect.py's batch-1 loop, BASELINE configs[0..1]) is ~85 dependent launches of 5 - 60 us; its whole
     // launch sequence is captured once per (arguments, plan) and replayed with ONE hipGraphLaunch.  Per-launch profiling, the
@@ -1068,7 +1067,7 @@ static int32_t forward_piece(byolo_t* h, const float* d_img, int32_t B, int32_t 
         bool done = false;
         if (serialize && h->ev_convs_valid && h->convs_stream != st) HIPCHK(h, hipStreamWaitEvent(st, h->ev_convs, 0));      // (graphs == 2 only)
         rc = forward_graph(h, a, st, &done); if (rc) return rc;
-        if (done) return finish_forward(h, st, stream);
+        if (done) return finish_forward(h, st);
     }
     const bool wait = serialize && h->ev_convs_valid && h->convs_stream != st;
     // Per-launch profiling wants a quiet device: a forward recorded at level 2, and the one enqueued after it, wait for the other
@@ -1077,7 +1076,7 @@ static int32_t forward_piece(byolo_t* h, const float* d_img, int32_t B, int32_t 
     const bool quiet = h->profiling >= 2 || h->quiet_next;
     h->quiet_next = h->profiling >= 2;
     rc = enqueue_forward(h, a, st, false, wait, h->opts.serialize_heads != 0 && !quiet); if (rc) return rc;
-    return finish_forward(h, st, stream);
+    return finish_forward(h, st);
 }
 
 // One forward as ONE hipGraphLaunch.  The first call with a given argument set runs eagerly (function attributes are set, one-off
@@ -1146,13 +1145,8 @@ static int32_t forward_graph(byolo_t* h, const FwdArgs& a, hipStream_t st, bool*
 
 // Split precision: wait for the forward and read the status words, unless the caller does that itself (byolo_set_async +
 // byolo_status).  A raised status is an ERROR here, not a row of inf / NaN: the words are cleared for the next call.
-static int32_t finish_forward(byolo_t* h, hipStream_t st, void* stream) {
-    if (h->precision == 1 && !h->async_status) {
-        unsigned f = 0, ly = 0xFFFFFFFFu;
-        int32_t rc = read_status(h, st, &f, &ly); if (rc) return rc;
-        if (f) { (void)byolo_clear_status(h, stream); return range_error(h, "byolo_forward", f, ly); }
-    }
-    return BYOLO_OK;
+static int32_t finish_forward(byolo_t* h, hipStream_t st) {
+    return h->precision == 1 && !h->async_status ? check_range_status(h, st, "byolo_forward") : BYOLO_OK;
 }
 
 // The epilogue of layer `layer` (a convolution or a detection head) in call `a`: flags, scale array, and with the masks on this
@@ -1184,7 +1178,6 @@ static int32_t layer_epi(byolo_t* h, int layer, const FwdArgs& a, EpiArgs& e) {
 // decode, sort + NMS.  `capturing`: the stream is in capture mode (forward_graph) -- no event is recorded or waited for in here.
 static int32_t enqueue_forward(byolo_t* h, const FwdArgs& a, hipStream_t st, bool capturing, bool wait_convs, bool heads_only) {
     const float* d_img = a.d_img; const int32_t B = a.B, T = a.T;
-    float* d_boxes = a.d_boxes; float* d_rows = a.d_rows; int32_t* d_kept = a.d_kept; int32_t* d_count = a.d_count;
     int32_t rc;
     char* ws = reinterpret_cast<char*>(a.d_workspace);
     if (h->profiling) {
@@ -1329,43 +1322,49 @@ static int32_t enqueue_forward(byolo_t* h, const FwdArgs& a, hipStream_t st, boo
         if (!h->ev_convs) HIPCHK(h, hipEventCreateWithFlags(&h->ev_convs, hipEventDisableTiming));
         HIPCHK(h, hipEventRecord(h->ev_convs, st)); h->convs_stream = st; h->ev_convs_valid = true;
     }
-    float* boxes = d_boxes ? d_boxes : reinterpret_cast<float*>(ws + h->plan.boxes_off);
-    if (d_boxes || d_rows) { rc = run_decode(h, ws, boxes, B, T, st, h->tshard_T > 0 ? 1 : 0); if (rc) return rc; }
-    if ((d_boxes || d_rows) && h->vr.on && h->tshard_T == 0) {      // variance recalibration, in place on the pre-NMS rows (var_recal.hip); a T shard holds sums
+    rc = enqueue_tail(h, a, ws, st); if (rc) return rc;
+    if (h->profiling) { HIPCHK(h, hipEventRecord(h->wslot().ev[4], st)); h->wslot().ev_valid = true; }
+    return BYOLO_OK;
+}
+
+// What a forward puts on the stream behind its convolution stack: decode -> variance recalibration -> NMS or soft-NMS -> score
+// recalibration -> vote, each only where the call and the handle's settings ask for it
+static int32_t enqueue_tail(byolo_t* h, const FwdArgs& a, char* ws, hipStream_t st) {
+    const int32_t B = a.B;
+    float* d_rows = a.d_rows;
+    int32_t rc;
+    float* boxes = a.d_boxes ? a.d_boxes : reinterpret_cast<float*>(ws + h->plan.boxes_off);
+    if (a.d_boxes || d_rows) { rc = run_decode(h, ws, boxes, B, a.T, st, h->tshard_T > 0 ? 1 : 0); if (rc) return rc; }
+    if ((a.d_boxes || d_rows) && h->vr.on && h->tshard_T == 0) {    // variance recalibration, in place on the pre-NMS rows (var_recal.hip); a T shard holds sums
         VarRecalParams v;
         byolo_var_recal_from_handle(h, &v);
         v.in = boxes; v.out = boxes; v.n = (int64_t)B * h->n_boxes;
         HIPCHK(h, launch_var_recal(v, st));
     }
     if (h->profiling) HIPCHK(h, hipEventRecord(h->wslot().ev[3], st));
-    if (d_rows) {
-        NmsParams n; memset(&n, 0, sizeof n);
-        n.boxes = boxes; n.B = B; n.N = h->n_boxes; n.D = h->row_len; n.obj_idx = h->obj_idx; n.cls_start = h->cls_start;
-        n.C = nms_classes(h->cfg.nms_mode, h->cfg.cls_cnt); n.max_out = h->cfg.max_out; n.iou_thr = h->cfg.iou_thresh;
-        n.ws = ws + h->plan.nms_off; n.ws_bytes = nms_workspace_bytes_ex(B, h->n_boxes, h->cfg.nms_mode, h->cfg.cls_cnt);
-        n.rows = d_rows; n.kept = d_kept; n.count = d_count; n.general_only = h->opts.nms_general != 0;
-        if (h->cfg.nms_mode == BYOLO_NMS_TWO_CLASS && h->cfg.cls_cnt != 2) return fail(h, BYOLO_ERR_ARG, "byolo_forward: 2-class NMS needs cls_cnt == 2");
-        if (h->soft_on) {                                   // the soft-NMS in place of the hard one (tail_kernels.hip soft_*)
-            SoftNmsParams sp = soft_params(h->soft_cfg);
-            sp.n = n; sp.n.ws = ws + h->plan.soft_off; sp.n.ws_bytes = soft_nms_workspace_bytes(B, h->n_boxes, n.C);
-            HIPCHK(h, launch_soft_nms(sp, st));
-        } else HIPCHK(h, launch_sort_nms(n, st));
-        if (h->sr.on) {                                     // score recalibration, in place on the kept rows (score_recal.hip): reads d_count on the device
-            ScoreRecalParams s;
-            byolo_score_recal_from_handle(h, &s);
-            s.in = d_rows; s.out = d_rows; s.count = d_count; s.score = reinterpret_cast<float*>(ws + h->plan.score_off); s.B = B; s.cap = (int)nms_out_cap(h);
-            HIPCHK(h, launch_score_recal(s, st));
-        }
-        if (h->vote_on) {                                   // variance voting, in place on the kept rows (box_vote.hip)
-            VoteParams v;
-            rc = byolo_vote_from_handle(h, &v, "byolo_forward"); if (rc) return rc;
-            v.boxes = boxes; v.B = B; v.rows_in = d_rows; v.rows_out = d_rows; v.kept = d_kept; v.count = d_count; v.cap = (int)nms_out_cap(h);
-            v.vote_n = reinterpret_cast<int32_t*>(ws + h->plan.vote_n_off);
-            v.ws = ws + h->plan.vote_off; v.ws_bytes = box_vote_workspace_bytes(B, h->n_boxes);
-            HIPCHK(h, launch_box_vote(v, st));
-        }
+    if (!d_rows) return BYOLO_OK;
+    const NmsParams n = nms_params(boxes, B, h->n_boxes, h->row_len, h->obj_idx, h->cls_start, nms_classes(h->cfg.nms_mode, h->cfg.cls_cnt), h->cfg.max_out, h->cfg.iou_thresh,
+                                   ws + h->plan.nms_off, nms_workspace_bytes_ex(B, h->n_boxes, h->cfg.nms_mode, h->cfg.cls_cnt), d_rows, a.d_kept, a.d_count, h->opts.nms_general != 0);
+    if (h->cfg.nms_mode == BYOLO_NMS_TWO_CLASS && h->cfg.cls_cnt != 2) return fail(h, BYOLO_ERR_ARG, "byolo_forward: 2-class NMS needs cls_cnt == 2");
+    if (h->soft_on) {                                       // the soft-NMS in place of the hard one (tail_kernels.hip soft_*)
+        SoftNmsParams sp = soft_params(h->soft_cfg);
+        sp.n = n; sp.n.ws = ws + h->plan.soft_off; sp.n.ws_bytes = soft_nms_workspace_bytes(B, h->n_boxes, n.C);
+        HIPCHK(h, launch_soft_nms(sp, st));
+    } else HIPCHK(h, launch_sort_nms(n, st));
+    if (h->sr.on) {                                         // score recalibration, in place on the kept rows (score_recal.hip): reads d_count on the device
+        ScoreRecalParams s;
+        byolo_score_recal_from_handle(h, &s);
+        s.in = d_rows; s.out = d_rows; s.count = a.d_count; s.score = reinterpret_cast<float*>(ws + h->plan.score_off); s.B = B; s.cap = (int)nms_out_cap(h);
+        HIPCHK(h, launch_score_recal(s, st));
     }
-    if (h->profiling) { HIPCHK(h, hipEventRecord(h->wslot().ev[4], st)); h->wslot().ev_valid = true; }
+    if (h->vote_on) {                                       // variance voting, in place on the kept rows (box_vote.hip)
+        VoteParams v;
+        rc = byolo_vote_from_handle(h, &v, "byolo_forward"); if (rc) return rc;
+        v.boxes = boxes; v.B = B; v.rows_in = d_rows; v.rows_out = d_rows; v.kept = a.d_kept; v.count = a.d_count; v.cap = (int)nms_out_cap(h);
+        v.vote_n = reinterpret_cast<int32_t*>(ws + h->plan.vote_n_off);
+        v.ws = ws + h->plan.vote_off; v.ws_bytes = box_vote_workspace_bytes(B, h->n_boxes);
+        HIPCHK(h, launch_box_vote(v, st));
+    }
     return BYOLO_OK;
 }
 
@@ -1381,12 +1380,7 @@ int32_t byolo_run_backbone(byolo_t* h, const float* d_img, int32_t B, void* d_wo
     rc = enqueue_forward(h, a, st, false, false);
     h->stop_layer = -1;
     if (rc) return rc;
-    if (h->precision == 1) {
-        unsigned f = 0, ly = 0xFFFFFFFFu;
-        rc = read_status(h, st, &f, &ly); if (rc) return rc;
-        if (f) { (void)byolo_clear_status(h, st); return range_error(h, "byolo_trainer_step (backbone)", f, ly); }
-    }
-    return BYOLO_OK;
+    return h->precision == 1 ? check_range_status(h, st, "byolo_trainer_step (backbone)") : BYOLO_OK;
 }
 
 extern "C" int32_t byolo_layer_output(const byolo_t* h, int32_t idx, const float** d_ptr, int64_t shape[4]) {
@@ -1464,34 +1458,26 @@ extern "C" int32_t byolo_sort_nms(byolo_t* h, const float* d_boxes, int32_t B, i
                                   int32_t cls_start_idx, int32_t nms_mode, int32_t max_out, float iou_thresh,
                                   void* d_sort_ws, size_t ws_bytes, float* d_rows, int32_t* d_kept, int32_t* d_count,
                                   void* stream) {
-    if (!h || !d_boxes || !d_sort_ws || !d_rows || !d_kept || !d_count) return fail(h, BYOLO_ERR_ARG, "byolo_sort_nms: null argument");
-    if (B < 1 || N < 1 || D < 5 || obj_idx < 4 || obj_idx >= D) return fail(h, BYOLO_ERR_ARG, "byolo_sort_nms: bad shape");
-    if (nms_mode == BYOLO_NMS_TWO_CLASS && (cls_start_idx < 0 || cls_start_idx + 1 >= D)) return fail(h, BYOLO_ERR_ARG, "byolo_sort_nms: bad cls_start_idx");
-    if (max_out < 1 || max_out > 2048) return fail(h, BYOLO_ERR_ARG, "byolo_sort_nms: max_out out of [1,2048]");
-    if (nms_mode < BYOLO_NMS_AGNOSTIC || nms_mode > BYOLO_NMS_PER_CLASS) return fail(h, BYOLO_ERR_ARG, "byolo_sort_nms: unknown nms_mode %d", nms_mode);
+    const char* what = "byolo_sort_nms";
+    if (!h || !d_boxes || !d_sort_ws || !d_rows || !d_kept || !d_count) return fail(h, BYOLO_ERR_ARG, "%s: null argument", what);
+    int32_t C = 0;                                           // (the class count of the per-class mode is the handle's)
+    int32_t rc = check_rows_shape(h, what, B, INT32_MAX, N, D, obj_idx, cls_start_idx, nms_mode, &C); if (rc) return rc;     // any B: unlike the soft-NMS and the vote
     const bool per_class = nms_mode == BYOLO_NMS_PER_CLASS;
-    const int32_t C = h->cfg.cls_cnt;                        // the class count of the per-class mode is the handle's
-    if (per_class && (C < 1 || C > BYOLO_NMS_MAX_CLASSES)) return fail(h, BYOLO_ERR_ARG, "byolo_sort_nms: per-class NMS takes 1 .. %d classes", BYOLO_NMS_MAX_CLASSES);
-    if (per_class && (cls_start_idx < 0 || (int64_t)cls_start_idx + C > D)) return fail(h, BYOLO_ERR_ARG, "byolo_sort_nms: bad cls_start_idx (class columns outside the row)");
-    if (N >= (1ll << 31)) return fail(h, BYOLO_ERR_ARG, "byolo_sort_nms: bad shape");
-    if (ws_bytes < nms_workspace_bytes_ex(B, N, nms_mode, C)) return fail(h, BYOLO_ERR_NOMEM, "byolo_sort_nms: workspace too small");
+    // one class in the per-class mode reads no class column, and this entry point still wants it inside the row (the other two do not)
+    if (per_class && C == 1 && (cls_start_idx < 0 || cls_start_idx >= D)) return fail(h, BYOLO_ERR_ARG, "%s: bad cls_start_idx (class columns outside the row)", what);
+    if (max_out < 1 || max_out > 2048) return fail(h, BYOLO_ERR_ARG, "%s: max_out out of [1,2048]", what);
+    if (ws_bytes < nms_workspace_bytes_ex(B, N, nms_mode, C)) return fail(h, BYOLO_ERR_NOMEM, "%s: workspace too small", what);
     HIPCHK(h, hipSetDevice(h->device));
-    NmsParams n; memset(&n, 0, sizeof n);
-    n.boxes = d_boxes; n.B = B; n.N = N; n.D = D; n.obj_idx = obj_idx; n.cls_start = cls_start_idx;
-    n.C = nms_classes(nms_mode, C); n.max_out = max_out; n.iou_thr = iou_thresh;
-    n.ws = d_sort_ws; n.ws_bytes = ws_bytes; n.rows = d_rows; n.kept = d_kept; n.count = d_count; n.general_only = h->opts.nms_general != 0;
+    const NmsParams n = nms_params(d_boxes, B, N, D, obj_idx, cls_start_idx, C, max_out, iou_thresh, d_sort_ws, ws_bytes, d_rows, d_kept, d_count, h->opts.nms_general != 0);
     HIPCHK(h, launch_sort_nms(n, reinterpret_cast<hipStream_t>(stream)));
-    if (per_class) { h->pc_counts = nms_class_counts_ptr(d_sort_ws, B, N, C); h->pc_B = B; h->pc_C = C; }
+    if (per_class) side_out_point(&h->out_class_counts, nms_class_counts_ptr(d_sort_ws, B, N, C), B, C);
     return BYOLO_OK;
 }
 
 extern "C" int32_t byolo_nms_class_counts(byolo_t* h, int32_t* d_class_counts, int32_t B, int32_t cls_cnt, void* stream) {
     if (!h || !d_class_counts) return fail(h, BYOLO_ERR_ARG, "byolo_nms_class_counts: null argument");
-    if (!h->pc_counts) return fail(h, BYOLO_ERR_STATE, "byolo_nms_class_counts: no per-class NMS (BYOLO_NMS_PER_CLASS) has run on this handle");
-    if (B != h->pc_B || cls_cnt != h->pc_C) return fail(h, BYOLO_ERR_ARG, "byolo_nms_class_counts: the last per-class NMS ran [%d, %d], asked for [%d, %d]", h->pc_B, h->pc_C, B, cls_cnt);
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipMemcpyAsync(d_class_counts, h->pc_counts, (size_t)B * cls_cnt * sizeof(int32_t), hipMemcpyDeviceToDevice, reinterpret_cast<hipStream_t>(stream)));
-    return BYOLO_OK;
+    if (!h->out_class_counts.ptr) return fail(h, BYOLO_ERR_STATE, "byolo_nms_class_counts: no per-class NMS (BYOLO_NMS_PER_CLASS) has run on this handle");
+    return side_out_copy(h, &h->out_class_counts, d_class_counts, B, cls_cnt, "byolo_nms_class_counts", stream);
 }
 
 // ---- soft-NMS (include/byolo.h "soft-NMS") ---------------------------------------------------------------------------------
@@ -1523,21 +1509,16 @@ extern "C" int32_t byolo_soft_nms(byolo_t* h, const float* d_boxes, int32_t B, i
                                   void* d_ws, size_t ws_bytes, float* d_rows, int32_t* d_kept, int32_t* d_count, void* stream) {
     const char* what = "byolo_soft_nms";
     if (!h || !d_boxes || !cfg || !d_ws || !d_rows || !d_kept || !d_count) return fail(h, BYOLO_ERR_ARG, "%s: null argument", what);
-    if (B < 1 || B > 65535 || N < 1 || N >= (1ll << 31) || D < 5 || obj_idx < 4 || obj_idx >= D) return fail(h, BYOLO_ERR_ARG, "%s: bad shape", what);
+    int32_t C = 0;
+    int32_t rc = check_rows_shape(h, what, B, 65535, N, D, obj_idx, cls_start_idx, nms_mode, &C); if (rc) return rc;
     if (max_out < 1 || max_out > 2048) return fail(h, BYOLO_ERR_ARG, "%s: max_out out of [1,2048]", what);
-    if (nms_mode < BYOLO_NMS_AGNOSTIC || nms_mode > BYOLO_NMS_PER_CLASS) return fail(h, BYOLO_ERR_ARG, "%s: unknown nms_mode %d", what, nms_mode);
-    const bool per_class = nms_mode == BYOLO_NMS_PER_CLASS;
-    const int32_t C = nms_classes(nms_mode, h->cfg.cls_cnt);
-    if (C < 1 || C > BYOLO_NMS_MAX_CLASSES) return fail(h, BYOLO_ERR_ARG, "%s: per-class NMS takes 1 .. %d classes", what, BYOLO_NMS_MAX_CLASSES);
-    if (C > 1 && (cls_start_idx < 0 || (int64_t)cls_start_idx + C > D)) return fail(h, BYOLO_ERR_ARG, "%s: bad cls_start_idx (class columns outside the row)", what);
-    int32_t rc = soft_check_settings(h, cfg, what); if (rc) return rc;
+    rc = soft_check_settings(h, cfg, what); if (rc) return rc;
     if (ws_bytes < soft_nms_workspace_bytes(B, N, C)) return fail(h, BYOLO_ERR_NOMEM, "%s: workspace %zu < byolo_soft_nms_workspace_bytes = %zu", what, ws_bytes, soft_nms_workspace_bytes(B, N, C));
     HIPCHK(h, hipSetDevice(h->device));
     SoftNmsParams p = soft_params(*cfg);
-    p.n.boxes = d_boxes; p.n.B = B; p.n.N = N; p.n.D = D; p.n.obj_idx = obj_idx; p.n.cls_start = cls_start_idx; p.n.C = C; p.n.max_out = max_out;
-    p.n.ws = d_ws; p.n.ws_bytes = ws_bytes; p.n.rows = d_rows; p.n.kept = d_kept; p.n.count = d_count; p.n.general_only = h->opts.nms_general != 0;
+    p.n = nms_params(d_boxes, B, N, D, obj_idx, cls_start_idx, C, max_out, 0.f, d_ws, ws_bytes, d_rows, d_kept, d_count, h->opts.nms_general != 0);      // (iou_thr is not read)
     HIPCHK(h, launch_soft_nms(p, reinterpret_cast<hipStream_t>(stream)));
-    if (per_class) { h->pc_counts = soft_nms_class_counts_ptr(d_ws, B, N, C); h->pc_B = B; h->pc_C = C; }
+    if (nms_mode == BYOLO_NMS_PER_CLASS) side_out_point(&h->out_class_counts, soft_nms_class_counts_ptr(d_ws, B, N, C), B, C);
     return BYOLO_OK;
 }
 
@@ -1548,7 +1529,7 @@ extern "C" int32_t byolo_set_soft_nms(byolo_t* h, const byolo_soft_nms_cfg* cfg)
         h->soft_cfg = *cfg;
     }
     h->soft_on = cfg != nullptr;
-    h->pc_counts = nullptr;
+    side_out_forget(&h->out_class_counts);
     // the stage's workspace is part of the plan, and a captured forward holds the launches of the old setting
     invalidate_plan(h);
     return BYOLO_OK;
@@ -1652,16 +1633,10 @@ static int32_t calibrate_bn_impl(byolo_t* h, const float* d_img, int32_t B, void
     // Split precision: every activation this call stores is range-checked like a forward's (BYOLO_ERR_RANGE naming the layer, never a
     // stored inf).  The words are read after each layer -- the next layer's statistics would be those of the inf -- so a flag an
     // asynchronous forward left unread is reported first, under its own name, rather than taken for a layer of this call.
-    auto range_check = [&](const char* what) -> int32_t {
-        unsigned f = 0, ly = 0xFFFFFFFFu;
-        int32_t rc = read_status(h, st, &f, &ly); if (rc) return rc;
-        if (f) { (void)byolo_clear_status(h, stream); return range_error(h, what, f, ly); }
-        return BYOLO_OK;
-    };
-    if (h->precision == 1) { rc = range_check("byolo_calibrate_bn: left by an earlier byolo_forward"); if (rc) return rc; }
+    if (h->precision == 1) { rc = check_range_status(h, st, "byolo_calibrate_bn: left by an earlier byolo_forward"); if (rc) return rc; }
     if (h->precision == 1 && h->img_split) {
         HIPCHK(h, launch_f32_to_split(d_img, reinterpret_cast<float*>(ws + h->plan.img_split_off), (int64_t)B * h->cfg.img_h * h->cfg.img_w * h->cfg.img_c, ACT_SCALE, st, h->d_status));
-        rc = range_check("byolo_calibrate_bn"); if (rc) return rc;
+        rc = check_range_status(h, st, "byolo_calibrate_bn"); if (rc) return rc;
     }
     for (const Step& s : h->steps) {
         Layer& l = h->layers[s.layer];
@@ -1716,9 +1691,9 @@ static int32_t calibrate_bn_impl(byolo_t* h, const float* d_img, int32_t B, void
         const float* res = l.fused_residual >= 0
             ? reinterpret_cast<const float*>(ws + h->plan.off[h->layers[l.fused_residual].ref[0]]) : nullptr;
         HIPCHK(h, launch_bn_act_inplace(p.dst, p.M, N, dptr(h, l.scale_off), dptr(h, l.shift_off), res, 1, split, st, split ? h->d_status : nullptr, s.layer));
-        if (split) { rc = range_check("byolo_calibrate_bn"); if (rc) return rc; }
+        if (split) { rc = check_range_status(h, st, "byolo_calibrate_bn"); if (rc) return rc; }
     }
-    if (h->precision == 1) return range_check("byolo_calibrate_bn");     // (a trailing element-wise add; waits for the stream)
+    if (h->precision == 1) return check_range_status(h, st, "byolo_calibrate_bn");     // (a trailing element-wise add; waits for the stream)
     HIPCHK(h, hipStreamSynchronize(st));
     return BYOLO_OK;
 }

@@ -164,6 +164,15 @@ struct RecalTable {
     double host[(BYOLO_VAR_RECAL_TABLE_BYTES > BYOLO_SCORE_RECAL_TABLE_BYTES ? BYOLO_VAR_RECAL_TABLE_BYTES : BYOLO_SCORE_RECAL_TABLE_BYTES) / sizeof(double)] = {};
 };
 
+// A per-image side output of a forward, [B, cols] words of SIDE_OUT_EL bytes (int32 counts, float scores): where the last call left
+// it for its getter -- inside that call's workspace, or in `own` (own_bytes of the handle's; a forward that ran in pieces).
+struct SideOut { const void* ptr = nullptr; int32_t B = 0, cols = 0; void* own = nullptr; size_t own_bytes = 0; };
+static constexpr size_t SIDE_OUT_EL = 4;
+static inline void side_out_point(SideOut* s, const void* ptr, int32_t B, int32_t cols) { s->ptr = ptr; s->B = B; s->cols = cols; }
+static inline void side_out_forget(SideOut* s) { s->ptr = nullptr; }       // a setting changed: the getter has nothing until the next call
+static inline void side_out_adopt(SideOut* s, int32_t B) { s->ptr = s->own; s->B = B; }
+static inline void side_out_free(SideOut* s) { if (s->own) (void)hipFree(s->own); }
+
 }  // namespace byi
 using namespace byi;
 
@@ -223,25 +232,17 @@ struct byolo {
     int64_t n_boxes = 0; int row_len = 0, obj_idx = 0, cls_start = 0;
     Plan plan;
     void* last_ws = nullptr;
-    // byolo_nms_class_counts: where the last per-class NMS left its [pc_B, pc_C] counts -- inside that call's workspace, or in
-    // pc_own (a forward that ran in pieces)
-    const int32_t* pc_counts = nullptr; int32_t pc_B = 0, pc_C = 0;
-    int32_t* pc_own = nullptr; size_t pc_own_cap = 0;
-    // byolo_set_box_vote: byolo_forward votes in place behind the NMS (box_vote.hip).  vn_ptr: where the last such forward left
-    // vote_n [vn_B, vn_cap] -- inside that call's workspace, or in vn_own (a forward that ran in pieces)
+    // What the getters hand out: the [B, cls_cnt] counts of the last per-class NMS (byolo_nms_class_counts), vote_n [B, cap] of the last
+    // voting forward (byolo_box_vote_counts), score [B, cap] of the last forward with score recalibration (byolo_score_recal_scores)
+    SideOut out_class_counts, out_vote_n, out_score;
+    // byolo_set_box_vote: byolo_forward votes in place behind the NMS (box_vote.hip)
     bool vote_on = false; byolo_vote_cfg vote_cfg = {};
     // byolo_set_soft_nms: byolo_forward runs the soft-NMS (tail_kernels.hip soft_*) in place of the hard one
     bool soft_on = false; byolo_soft_nms_cfg soft_cfg = {};
     // byolo_set_var_recal: byolo_forward applies vr_cfg's table (vr) in place behind the decode (var_recal.hip)
     byolo_var_recal_cfg vr_cfg = {}; RecalTable vr{BYOLO_VAR_RECAL_TABLE_BYTES};
-    // byolo_set_score_recal: byolo_forward applies sr_cfg's table (sr) in place on the kept rows behind the NMS (score_recal.hip).
-    // sr_ptr: where the last such forward left score [sr_B, sr_cap] -- inside that call's workspace, or in sr_own (a forward that
-    // ran in pieces), as vn_ptr / vn_own
+    // byolo_set_score_recal: byolo_forward applies sr_cfg's table (sr) in place on the kept rows behind the NMS (score_recal.hip)
     byolo_score_recal_cfg sr_cfg = {}; RecalTable sr{BYOLO_SCORE_RECAL_TABLE_BYTES};
-    const float* sr_ptr = nullptr; int32_t sr_B = 0, sr_cap = 0;
-    float* sr_own = nullptr; size_t sr_own_cap = 0;
-    const int32_t* vn_ptr = nullptr; int32_t vn_B = 0, vn_cap = 0;
-    int32_t* vn_own = nullptr; size_t vn_own_cap = 0;
     int64_t first_image = 0;       // position of a call's first image in the logical batch (dropout stream)
     int stop_layer = -1;           // >= 0: enqueue_forward stops in front of the first step of this layer (byolo_run_backbone)
     int tshard_t0 = 0, tshard_T = 0;   // byolo_set_tshard: this call's T samples are samples t0 .. t0 + T - 1 of tshard_T per image (0 = off)
@@ -326,4 +327,26 @@ void byolo_var_recal_from_handle(const byolo_t* h, VarRecalParams* p);
 void byolo_score_recal_pack(const byolo_t* h, double* tab);
 void byolo_score_recal_from_handle(const byolo_t* h, ScoreRecalParams* p);
 static inline int64_t nms_out_cap(const byolo_t* h) { return (int64_t)h->cfg.max_out * nms_classes(h->cfg.nms_mode, h->cfg.cls_cnt); }
+// byolo_api.hip: a getter's copy of side output `s` to the caller's [B, cols] on `stream` (BYOLO_ERR_ARG: the last call left another shape)
+int32_t side_out_copy(byolo_t* h, const SideOut* s, void* d_dst, int32_t B, int32_t cols, const char* what, void* stream);
+// Rows [B, N, D] with score column obj_idx and class columns from cls_start under a BYOLO_NMS_* mode, as byolo_sort_nms, byolo_soft_nms
+// and byolo_box_vote take them; *C: the classes the mode runs (the handle's cls_cnt in the per-class mode).  B_max: the largest batch
+// the entry point takes.  BYOLO_ERR_ARG, nothing launched.
+static inline int32_t check_rows_shape(byolo_t* h, const char* what, int32_t B, int32_t B_max, int64_t N, int32_t D, int32_t obj_idx, int32_t cls_start,
+                                       int32_t nms_mode, int32_t* C) {
+    if (B < 1 || B > B_max || N < 1 || N >= (1ll << 31) || D < 5 || obj_idx < 4 || obj_idx >= D) return fail(h, BYOLO_ERR_ARG, "%s: bad shape", what);
+    if (nms_mode < BYOLO_NMS_AGNOSTIC || nms_mode > BYOLO_NMS_PER_CLASS) return fail(h, BYOLO_ERR_ARG, "%s: unknown nms_mode %d", what, nms_mode);
+    *C = nms_classes(nms_mode, h->cfg.cls_cnt);
+    if (*C < 1 || *C > BYOLO_NMS_MAX_CLASSES) return fail(h, BYOLO_ERR_ARG, "%s: per-class NMS takes 1 .. %d classes", what, BYOLO_NMS_MAX_CLASSES);
+    if (*C > 1 && (cls_start < 0 || (int64_t)cls_start + *C > D)) return fail(h, BYOLO_ERR_ARG, "%s: bad cls_start_idx (class columns outside the row)", what);
+    return BYOLO_OK;
+}
+// The NmsParams of one run of the NMS pipeline (hard or soft) over C classes
+static inline NmsParams nms_params(const float* boxes, int32_t B, int64_t N, int32_t D, int32_t obj_idx, int32_t cls_start, int32_t C, int32_t max_out,
+                                   float iou_thr, void* ws, size_t ws_bytes, float* rows, int32_t* kept, int32_t* count, bool general_only) {
+    NmsParams n; memset(&n, 0, sizeof n);
+    n.boxes = boxes; n.B = B; n.N = N; n.D = D; n.obj_idx = obj_idx; n.cls_start = cls_start; n.C = C; n.max_out = max_out; n.iou_thr = iou_thr;
+    n.ws = ws; n.ws_bytes = ws_bytes; n.rows = rows; n.kept = kept; n.count = count; n.general_only = general_only;
+    return n;
+}
 int32_t byolo_run_backbone(byolo_t* h, const float* d_img, int32_t B, void* d_workspace, size_t workspace_bytes, hipStream_t st);

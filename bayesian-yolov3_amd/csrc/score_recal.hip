@@ -449,7 +449,7 @@ extern "C" int32_t byolo_set_score_recal(byolo_t* h, const byolo_score_recal_cfg
         h->sr.dirty = true;
     }
     h->sr.on = cfg != nullptr;
-    h->sr_ptr = nullptr;
+    side_out_forget(&h->out_score);
     // a captured forward holds the launches of the old setting, and the plan has score [B, cap] only while this is on (as byolo_set_box_vote)
     invalidate_plan(h);
     return BYOLO_OK;
@@ -457,11 +457,8 @@ extern "C" int32_t byolo_set_score_recal(byolo_t* h, const byolo_score_recal_cfg
 
 extern "C" int32_t byolo_score_recal_scores(byolo_t* h, float* d_score, int32_t B, int32_t cap, void* stream) {
     if (!h || !d_score) return fail(h, BYOLO_ERR_ARG, "byolo_score_recal_scores: null argument");
-    if (!h->sr_ptr) return fail(h, BYOLO_ERR_STATE, "byolo_score_recal_scores: no byolo_forward with score recalibration (byolo_set_score_recal) and d_rows has run on this handle");
-    if (B != h->sr_B || cap != h->sr_cap) return fail(h, BYOLO_ERR_ARG, "byolo_score_recal_scores: [%d, %d] asked for, the last forward left [%d, %d]", B, cap, h->sr_B, h->sr_cap);
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipMemcpyAsync(d_score, h->sr_ptr, (size_t)B * cap * sizeof(float), hipMemcpyDeviceToDevice, reinterpret_cast<hipStream_t>(stream)));
-    return BYOLO_OK;
+    if (!h->out_score.ptr) return fail(h, BYOLO_ERR_STATE, "byolo_score_recal_scores: no byolo_forward with score recalibration (byolo_set_score_recal) and d_rows has run on this handle");
+    return side_out_copy(h, &h->out_score, d_score, B, cap, "byolo_score_recal_scores", stream);
 }
 
 extern "C" int32_t byolo_score_recal_features(const byolo_score_recal_cfg* cfg, const float* d_src, int64_t n, int32_t stride, int32_t score_col,
