@@ -168,7 +168,13 @@ __global__ __launch_bounds__(256) void decode_epi_kernel(const DecodeParams p) {
     const int cells = p.lh * p.lw;
     const int64_t total = (int64_t)p.B * cells * 3;
     const size_t sample_stride = (size_t)cells * LDC;
-    const float invT = 1.0f / (float)p.T;
+    // Every mean is the sum DIVIDED by T, as tf.reduce_mean forms it, not multiplied by a rounded 1 / T (tests/test_decode_f64_gpu.py):
+    //  * `sum * invT` is up to an ulp of the mean off, and E[l l^T] - E[l] E[l]^T turns an ulp of E[l^2] into an absolute error: T = 7
+    //    samples of a logit of 800 came out with a variance of -0.098 where the reference has 0 (5600 * fl(1 / 7) rounds to 800.00006);
+    //  * a product can be contracted into what follows: `1 - s_obj * invT` became one fused multiply-add, so T = 50 samples of a
+    //    saturated objectness (every sigmoid 1) had 1 - mean = 2.2e-8 beside a mean of 1, and the entropy 3.9e-7 where the reference
+    //    has 0 * log 0 = NaN.  A quotient is rounded once and T / T is 1.
+    const float Tf = (float)p.T;
     for (int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; gid < total;
          gid += (int64_t)gridDim.x * blockDim.x) {
         const int pr = (int)(gid % 3);
@@ -227,14 +233,14 @@ __global__ __launch_bounds__(256) void decode_epi_kernel(const DecodeParams p) {
         }
         float ev[4], cov[4][4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) ev[i] = s_loc[i] * invT;
+        for (int i = 0; i < 4; ++i) ev[i] = s_loc[i] / Tf;
         {
             int q = 0;
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
                 for (int j = i; j < 4; ++j) {
-                    const float c = s_ll[q++] * invT - ev[i] * ev[j];   // E[l l^T] - E[l]E[l]^T (layers.py:383)
+                    const float c = s_ll[q++] / Tf - ev[i] * ev[j];   // E[l l^T] - E[l]E[l]^T (layers.py:383)
                     cov[i][j] = c; cov[j][i] = c;
                 }
         }
@@ -244,23 +250,23 @@ __global__ __launch_bounds__(256) void decode_epi_kernel(const DecodeParams p) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             out[4 + i] = cov[i][i];
-            const float a = s_var[i] * invT;
+            const float a = s_var[i] / Tf;
             out[8 + i] = a;
             ale_sum += a;
         }
         out[12] = det4_(cov);
         out[13] = ale_sum;
-        const float obj_mean = s_obj * invT;
+        const float obj_mean = s_obj / Tf;
         const float objH = logistic_entropy_(obj_mean);
         out[14] = obj_mean;
-        out[15] = objH - s_objH * invT;
+        out[15] = objH - s_objH / Tf;
         out[16] = objH;
 #pragma unroll
-        for (int c = 0; c < CM; ++c) if (EXACT || c < C) out[17 + c] = s_cls[c] * invT;
+        for (int c = 0; c < CM; ++c) if (EXACT || c < C) out[17 + c] = s_cls[c] / Tf;
         const float clsH = softmax_entropy_<CM, EXACT>(out + 17, C);
 #pragma unroll
         for (int i = 0; i < 17 + CM; ++i) if (EXACT || i < 17 + C) o[i] = out[i];
-        o[17 + C] = clsH - s_clsH * invT;
+        o[17 + C] = clsH - s_clsH / Tf;
         o[18 + C] = clsH;
         o[19 + C] = (float)p.layer_id;
         o[20 + C] = (float)pr;
@@ -279,7 +285,7 @@ __global__ __launch_bounds__(256) void epi_stats_kernel(const DecodeParams p, fl
     const int cells = p.lh * p.lw;
     const int64_t total = (int64_t)p.B * cells * 3;
     const size_t sample_stride = (size_t)cells * LDC;
-    const float invT = 1.0f / (float)p.T;
+    const float Tf = (float)p.T;                                  // divided, not multiplied by 1 / T: see decode_epi_kernel
     for (int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; gid < total;
          gid += (int64_t)gridDim.x * blockDim.x) {
         const int pr = (int)(gid % 3);
@@ -310,7 +316,7 @@ __global__ __launch_bounds__(256) void epi_stats_kernel(const DecodeParams p, fl
         }
         float ev[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) ev[i] = s_loc[i] * invT;
+        for (int i = 0; i < 4; ++i) ev[i] = s_loc[i] / Tf;
         const size_t o = ((size_t)b * cells + cell) * 3 + pr;                        // [B, lh, lw, 3]
         if (ev_loc) {
 #pragma unroll
@@ -322,7 +328,7 @@ __global__ __launch_bounds__(256) void epi_stats_kernel(const DecodeParams p, fl
             for (int i = 0; i < 4; ++i)
 #pragma unroll
                 for (int j = i; j < 4; ++j) {
-                    const float c = s_ll[q++] * invT - ev[i] * ev[j];                // E[l l^T] - E[l]E[l]^T (layers.py:383)
+                    const float c = s_ll[q++] / Tf - ev[i] * ev[j];                // E[l l^T] - E[l]E[l]^T (layers.py:383)
                     covar[o * 16 + i * 4 + j] = c; covar[o * 16 + j * 4 + i] = c;
                 }
         }

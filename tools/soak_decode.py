@@ -26,6 +26,7 @@ def one_case(g, idx):
     import torch
     from byolo import Engine
     from conftest import assert_close
+    from _decode_ref import det_scaled_error
     from oracle import cpu_ref
     kind = int(g.integers(0, 3))
     variant = VARIANTS[kind]
@@ -85,16 +86,9 @@ def one_case(g, idx):
     assert np.array_equal(got[inf_mask], ref[inf_mask]), "inf signs"
     got = np.where(inf_mask, 0, got); ref = np.where(inf_mask, 0, ref)
     if kind == 2:
-        with np.errstate(all="ignore"):
-            # Hadamard's bound on the product of the diagonal -- of the matrix float32 ACTUALLY holds: every entry of the one-pass
-            # covariance E[l l^T] - E[l] E[l]^T (layers.py:383) carries an absolute error of a few ulps of E[l^2], so a variance of
-            # 1e-4 beside E[l^2] = 900 (three samples of a logit near 30) is half noise, and the determinant of the rank <= T - 1
-            # matrix moves by that noise times a cofactor (seed 62, case 239: T = 3, logit scale 30 -- one failure in 2 400 cases
-            # of six seeds under the bound on the exact diagonal, where the float32 CPU oracle happened to sit at 7e-8)
-            raw5d = raw.reshape(B, T, lh, lw, 3, -1)[..., :4].astype(np.float64)
-            m2d = (raw5d ** 2).mean(1).transpose(0, 3, 1, 2, 4).reshape(B, -1, 4)        # E[l^2], prior-major like concat_bbox
-            hb = np.maximum(1.0, np.abs(np.prod(np.abs(ref[..., 4:8].astype(np.float64)) + 16 * 6e-8 * m2d, axis=-1)))
-            derr = np.abs(got[..., 12].astype(np.float64) - ref[..., 12]) / hb
+        # at the scale of Hadamard's bound on the matrix float32 ACTUALLY holds: one definition, shared with the suite's float64
+        # check of this stage (tests/_decode_ref.py, where the reasoning and the seed that asked for it are written down)
+        derr = det_scaled_error(got, ref, raw, B, T)
         assert not (np.nan_to_num(derr, nan=0.0) >= 1e-4).any(), "det(epi covar): scaled error %.3e" % np.nanmax(derr)
         assert np.array_equal(np.isnan(got[..., 12]), np.isnan(ref[..., 12])), "det NaN pattern"
         got = got.copy(); ref = ref.copy()
