@@ -11,6 +11,7 @@ OK, ERR_ARG, ERR_STATE, ERR_HIP, ERR_NOMEM, ERR_RANGE = 0, -1, -2, -3, -4, -5
 DET_STANDARD, DET_ALEATORIC, DET_EPISTEMIC = 0, 1, 2
 NMS_AGNOSTIC, NMS_TWO_CLASS, NMS_PER_CLASS = 0, 1, 2
 NMS_MAX_CLASSES = 128          # BYOLO_NMS_MAX_CLASSES
+T_LADDER_MAX, T_LADDER_MAX_CLASSES = 16, 48      # BYOLO_T_LADDER_MAX, BYOLO_T_LADDER_MAX_CLASSES
 NORM_BN, NORM_DROPOUT = 1, 2
 AUG_SATURATION, AUG_BRIGHTNESS, AUG_HUE = 1, 2, 3
 AUG_COLORED_SALT_N_PEPPER, AUG_SALT_N_PEPPER, AUG_GAUSSIAN = 1, 2, 3
@@ -173,6 +174,8 @@ PROTOTYPES = {
     "byolo_get_precision": (_i32, [_vp]),
     "byolo_decode": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _P(_f32), _i32, _vp, _i64, _i64, _vp]),
     "byolo_epistemic_stats": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "byolo_decode_ladder": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _P(_f32), _i32, _P(_i32), _i32, _vp, _i64, _i64, _vp]),
+    "byolo_forward_ladder": (_i32, [_vp, _i32, _i32, _P(_i32), _i32, _vp, _vp]),
     "byolo_nms_workspace_bytes": (_sz, [_i32, _i64]),
     "byolo_nms_workspace_bytes_ex": (_sz, [_i32, _i64, _i32, _i32]),
     "byolo_nms_class_counts": (_i32, [_vp, _vp, _i32, _i32, _vp]),

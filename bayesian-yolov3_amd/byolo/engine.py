@@ -774,6 +774,53 @@ class Engine:
                                         int(lw), arr, int(layer_id), ctypes.c_void_p(boxes.data_ptr()),
                                         int(boxes.shape[1]), int(box_base), ctypes.c_void_p(stream)))
 
+    # ---- MC sample-count ladder (include/byolo.h "MC sample-count ladder") -------------
+    def _ladder_rungs(self, what, rungs, T):
+        """The rungs as a ctypes array, refused in the library's words (csrc/byolo_api.hip ladder_rungs)."""
+        rungs = [int(r) for r in rungs]
+        if not 1 <= len(rungs) <= _lib.T_LADDER_MAX:
+            raise ValueError("%s: 1 .. %d rungs" % (what, _lib.T_LADDER_MAX))
+        for k, r in enumerate(rungs):
+            if not 1 <= r <= T:
+                raise ValueError("%s: rung %d outside 1 .. T = %d" % (what, r, T))
+            if k and r <= rungs[k - 1]:
+                raise ValueError("%s: the rungs must be strictly increasing" % what)
+        if self.cfg.cls_cnt > _lib.T_LADDER_MAX_CLASSES:
+            raise ValueError("%s: the ladder takes at most %d classes (cls_cnt %d)" % (what, _lib.T_LADDER_MAX_CLASSES, self.cfg.cls_cnt))
+        return (ctypes.c_int32 * len(rungs))(*rungs), len(rungs)
+
+    def decode_ladder(self, raw, B, T, priors_hw, layer_id, rungs, boxes, box_base):
+        """The staged ladder of one epistemic detection layer: raw [B*T,lh,lw,F] dense -> the layer's rows of rung k in
+        boxes[k] (boxes [K,B,N,D]) at box_base; boxes[k] is what decode(2, ...) makes of each image's first rungs[k] samples."""
+        torch = _torch()
+        S, lh, lw, F = raw.shape
+        assert S == B * T and raw.is_cuda and raw.dtype == torch.float32 and raw.is_contiguous()
+        arr_r, K = self._ladder_rungs("byolo_decode_ladder", rungs, int(T))
+        assert boxes.is_cuda and boxes.dtype == torch.float32 and boxes.is_contiguous() and boxes.dim() == 4
+        assert boxes.shape[0] == K and boxes.shape[1] == B and boxes.shape[3] == 21 + self.cfg.cls_cnt
+        arr = (ctypes.c_float * 6)(*[float(v) for p in priors_hw for v in p])
+        stream = torch.cuda.current_stream(raw.device).cuda_stream
+        check(self._h, lib.byolo_decode_ladder(self._h, ctypes.c_void_p(raw.data_ptr()), int(B), int(T), int(lh), int(lw), arr,
+                                               int(layer_id), arr_r, K, ctypes.c_void_p(boxes.data_ptr()), int(boxes.shape[2]),
+                                               int(box_base), ctypes.c_void_p(stream)))
+
+    def t_ladder(self, rungs, B, T, out=None):
+        """The pre-NMS rows of the LAST forward(B, T) at the sample counts `rungs` (strictly increasing, each in 1 .. T):
+        float32 [K,B,N,D] on the engine's device, enqueued on torch's current stream -- the stream of that forward, and before
+        the next forward into the same workspace.  Slab k is the decode of every image's first rungs[k] samples of that forward
+        (rung T: the forward's own 'boxes'), variance-recalibrated where the engine is; see byolo_forward_ladder for what
+        that does and does not promise."""
+        torch = _torch()
+        arr_r, K = self._ladder_rungs("byolo_forward_ladder", rungs, int(T))
+        N, D = self.num_boxes()
+        if out is None:
+            out = torch.empty((K, int(B), N, D), dtype=torch.float32, device=self.torch_device)
+        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (K, int(B), N, D)
+        assert out.device.index == self.device
+        stream = torch.cuda.current_stream(out.device).cuda_stream
+        check(self._h, lib.byolo_forward_ladder(self._h, int(B), int(T), arr_r, K, ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(stream)))
+        return out
+
     def epistemic_stats(self, raw, B, T):
         """decode_epistemic's dict entries outside the box row from a raw epistemic detection output [B*T,lh,lw,F]:
         dict(ev_loc [B,lh,lw,3,4], epi_covar_loc [B,lh,lw,3,4,4], obj_samples [B*T,lh,lw,3], cls_samples [B*T,lh,lw,3,C])."""

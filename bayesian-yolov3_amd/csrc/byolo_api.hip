@@ -1447,6 +1447,86 @@ extern "C" int32_t byolo_epistemic_stats(byolo_t* h, const float* d_raw, int32_t
     return BYOLO_OK;
 }
 
+// ---- the MC sample-count ladder (include/byolo.h): the epistemic decode finished at several sample counts in one pass ----
+static_assert(BYOLO_T_LADDER_MAX == T_LADDER_MAX && BYOLO_T_LADDER_MAX_CLASSES == T_LADDER_MAX_CLASSES, "byolo_kernels.h restates the ladder's limits");
+// the rungs of both entry points, the class count included; byolo/engine.py words the same refusals
+static int32_t ladder_rungs(byolo_t* h, const char* what, int32_t T, const int32_t* rungs, int32_t n_rungs, LadderParams* r) {
+    if (!rungs || n_rungs < 1 || n_rungs > BYOLO_T_LADDER_MAX) return fail(h, BYOLO_ERR_ARG, "%s: 1 .. %d rungs", what, BYOLO_T_LADDER_MAX);
+    memset(r, 0, sizeof *r);
+    for (int k = 0; k < n_rungs; ++k) {
+        if (rungs[k] < 1 || rungs[k] > T) return fail(h, BYOLO_ERR_ARG, "%s: rung %d outside 1 .. T = %d", what, rungs[k], T);
+        if (k && rungs[k] <= rungs[k - 1]) return fail(h, BYOLO_ERR_ARG, "%s: the rungs must be strictly increasing", what);
+        r->rungs[k] = rungs[k];
+    }
+    r->n_rungs = n_rungs;
+    if (h->cfg.cls_cnt > BYOLO_T_LADDER_MAX_CLASSES)
+        return fail(h, BYOLO_ERR_ARG, "%s: the ladder takes at most %d classes (cls_cnt %d)", what, BYOLO_T_LADDER_MAX_CLASSES, h->cfg.cls_cnt);
+    return BYOLO_OK;
+}
+
+extern "C" int32_t byolo_decode_ladder(byolo_t* h, const float* d_raw, int32_t B, int32_t T, int32_t lh, int32_t lw,
+                                       const float* priors_hw, int32_t layer_id, const int32_t* rungs, int32_t n_rungs,
+                                       float* d_boxes, int64_t n_total, int64_t box_base, void* stream) {
+    const char* what = "byolo_decode_ladder";
+    if (!h || !d_raw || !d_boxes || !priors_hw) return fail(h, BYOLO_ERR_ARG, "%s: null argument", what);
+    if (B < 1 || T < 1 || lh < 1 || lw < 1 || box_base < 0 || n_total < box_base + (int64_t)3 * lh * lw) return fail(h, BYOLO_ERR_ARG, "%s: bad argument", what);
+    LadderParams r;
+    int32_t rc = ladder_rungs(h, what, T, rungs, n_rungs, &r); if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    DecodeParams d; memset(&d, 0, sizeof d);
+    d.raw = d_raw; d.boxes = d_boxes; d.B = B; d.T = T; d.lh = lh; d.lw = lw; d.C = h->cfg.cls_cnt;
+    d.n_total = n_total; d.box_base = box_base; d.layer_id = layer_id;
+    for (int k = 0; k < 3; ++k) { d.ph[k] = priors_hw[2 * k]; d.pw[k] = priors_hw[2 * k + 1]; }
+    r.slab_stride = (int64_t)B * n_total * (21 + d.C);
+    hipError_t e = launch_decode_ladder(d, r, reinterpret_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(h, e == hipErrorInvalidValue ? BYOLO_ERR_ARG : BYOLO_ERR_HIP, "%s: %s (cls_cnt %d)", what, hipGetErrorString(e), d.C);
+    return BYOLO_OK;
+}
+
+// Reads what run_decode read (the raw detection outputs the last forward left in its workspace, at the library's own pitch) and, where
+// the handle recalibrates variances, does to every slab what enqueue_tail does to the forward's rows.  Everything is checked before
+// the first launch.
+static int32_t forward_ladder_impl(byolo_t* h, int32_t B, int32_t T, const int32_t* rungs, int32_t n_rungs, float* d_boxes, void* stream) {
+    const char* what = "byolo_forward_ladder";
+    if (!h || !d_boxes) return fail(h, BYOLO_ERR_ARG, "%s: null argument", what);
+    if (!h->last_ws || h->plan.B < 0) return fail(h, BYOLO_ERR_STATE, "%s: no forward has run", what);
+    if (B != h->plan.B || T != h->plan.T)
+        return fail(h, BYOLO_ERR_ARG, "%s: (B, T) = (%d, %d), the workspace holds a forward of (%d, %d) (a batch beyond byolo_max_images runs in pieces: no ladder)", what, B, T, h->plan.B, h->plan.T);
+    if (h->tshard_T > 0) return fail(h, BYOLO_ERR_ARG, "%s: a T shard (byolo_set_tshard) has no ladder", what);
+    int n_det = 0;
+    for (const auto& l : h->layers) {
+        if (l.op != OP_DETECTION) continue;
+        ++n_det;
+        if (l.det_kind != BYOLO_DET_EPISTEMIC || !l.stacked) return fail(h, BYOLO_ERR_ARG, "%s: the ladder is defined for stacked epistemic detection layers", what);
+    }
+    if (!n_det) return fail(h, BYOLO_ERR_ARG, "%s: the graph has no detection layer", what);
+    LadderParams r;
+    int32_t rc = ladder_rungs(h, what, T, rungs, n_rungs, &r); if (rc) return rc;
+    r.slab_stride = (int64_t)B * h->n_boxes * h->row_len;
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const char* ws = reinterpret_cast<const char*>(h->last_ws);
+    for (const auto& l : h->layers) {
+        if (l.op != OP_DETECTION) continue;
+        DecodeParams d; memset(&d, 0, sizeof d);
+        d.raw = reinterpret_cast<const float*>(ws + h->plan.off[l.out_tensor]);
+        d.boxes = d_boxes; d.B = B; d.T = T; d.lh = l.H; d.lw = l.W; d.C = h->cfg.cls_cnt;
+        d.n_total = h->n_boxes; d.box_base = l.box_base; d.layer_id = l.det_id; d.ld = layer_pitch(l);
+        for (int k = 0; k < 3; ++k) { d.ph[k] = l.priors[2 * k]; d.pw[k] = l.priors[2 * k + 1]; }
+        HIPCHK(h, launch_decode_ladder(d, r, st));
+    }
+    if (h->vr.on) {                                         // the slabs lie back to back: one launch over all of them
+        VarRecalParams v;
+        byolo_var_recal_from_handle(h, &v);
+        v.in = d_boxes; v.out = d_boxes; v.n = (int64_t)n_rungs * B * h->n_boxes;
+        HIPCHK(h, launch_var_recal(v, st));
+    }
+    return BYOLO_OK;
+}
+extern "C" int32_t byolo_forward_ladder(byolo_t* h, int32_t B, int32_t T, const int32_t* rungs, int32_t n_rungs, float* d_boxes, void* stream) {
+    return guarded(h, "byolo_forward_ladder", [&] { return forward_ladder_impl(h, B, T, rungs, n_rungs, d_boxes, stream); });
+}
+
 extern "C" size_t byolo_nms_workspace_bytes(int32_t B, int64_t N) { return nms_workspace_bytes(B, N, 2); }   // modes 0 and 1
 extern "C" size_t byolo_nms_workspace_bytes_ex(int32_t B, int64_t N, int32_t nms_mode, int32_t cls_cnt) {
     if (B < 1 || N < 1) return 0;

@@ -264,6 +264,16 @@ struct DecodeParams {
     int mode;
 };
 hipError_t launch_decode(int kind, const DecodeParams& p, hipStream_t st);
+// ---- the MC sample-count ladder (include/byolo.h "MC sample-count ladder"): the epistemic decode finished at several sample counts ----
+constexpr int T_LADDER_MAX = 16;             // BYOLO_T_LADDER_MAX (byolo_api.hip asserts the two agree)
+constexpr int T_LADDER_MAX_CLASSES = 48;     // the largest build of decode_epi_ladder_kernel that stays out of scratch (tests/test_no_scratch.py)
+struct LadderParams {
+    int32_t n_rungs;                         // 1 .. T_LADDER_MAX
+    int32_t rungs[T_LADDER_MAX];             // strictly increasing, 1 <= rungs[k] <= DecodeParams::T
+    int64_t slab_stride;                     // floats from rung k's rows to rung k + 1's (B * n_total * D for dense slabs)
+};
+// p as launch_decode(BYOLO_DET_EPISTEMIC, ...) takes it with mode 0 (p.status is not read); rung k's rows -> p.boxes + k * slab_stride
+hipError_t launch_decode_ladder(const DecodeParams& p, const LadderParams& r, hipStream_t st);
 // decode_epistemic's dict entries outside the box row: ev_loc [B,lh,lw,3,4], covar [B,lh,lw,3,4,4], obj / cls samples
 hipError_t launch_epi_stats(const DecodeParams& p, float* ev_loc, float* covar, float* obj_s, float* cls_s, hipStream_t st);
 

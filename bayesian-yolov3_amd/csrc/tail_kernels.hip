@@ -158,6 +158,54 @@ __device__ __forceinline__ float det4_(float a[4][4]) {
     return det;
 }
 
+// The finish of one row from a lane's running sums over its first Tf samples: means by division (see decode_epi_kernel on why),
+// covariance, determinant, entropies and mutual informations, corners, layer / prior ids.  ONE copy: decode_epi_kernel (modes 0
+// and 2) and decode_epi_ladder_kernel both end here, so a rung of the ladder cannot drift from the decode of the same samples.
+template <int CM, bool EXACT>
+__device__ __forceinline__ void epi_finish_(const DecodeParams& p, const float (&s_loc)[4], const float (&s_ll)[10], const float (&s_var)[4],
+                                            float s_obj, float s_objH, const float (&s_cls)[CM], float s_clsH, float Tf, int C,
+                                            int cell, int pr, float* o) {
+    float ev[4], cov[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) ev[i] = s_loc[i] / Tf;
+    {
+        int q = 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = i; j < 4; ++j) {
+                const float c = s_ll[q++] / Tf - ev[i] * ev[j];   // E[l l^T] - E[l]E[l]^T (layers.py:383)
+                cov[i][j] = c; cov[j][i] = c;
+            }
+    }
+    float out[17 + CM];
+    corners_(ev[0], ev[1], ev[2], ev[3], cell % p.lw, cell / p.lw, p.lw, p.lh, p.pw[pr], p.ph[pr], out);
+    float ale_sum = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        out[4 + i] = cov[i][i];
+        const float a = s_var[i] / Tf;
+        out[8 + i] = a;
+        ale_sum += a;
+    }
+    out[12] = det4_(cov);
+    out[13] = ale_sum;
+    const float obj_mean = s_obj / Tf;
+    const float objH = logistic_entropy_(obj_mean);
+    out[14] = obj_mean;
+    out[15] = objH - s_objH / Tf;
+    out[16] = objH;
+#pragma unroll
+    for (int c = 0; c < CM; ++c) if (EXACT || c < C) out[17 + c] = s_cls[c] / Tf;
+    const float clsH = softmax_entropy_<CM, EXACT>(out + 17, C);
+#pragma unroll
+    for (int i = 0; i < 17 + CM; ++i) if (EXACT || i < 17 + C) o[i] = out[i];
+    o[17 + C] = clsH - s_clsH / Tf;
+    o[18 + C] = clsH;
+    o[19 + C] = (float)p.layer_id;
+    o[20 + C] = (float)pr;
+}
+
 // One lane per (image, cell, prior): a single pass over the image's T samples keeps
 // 4 + 10 + 4 + 1 + 1 + C + 1 running sums in registers.
 template <int CM, bool EXACT>
@@ -231,45 +279,99 @@ __global__ __launch_bounds__(256) void decode_epi_kernel(const DecodeParams p) {
             o[20 + C] = s_clsH;
             continue;
         }
-        float ev[4], cov[4][4];
+        epi_finish_<CM, EXACT>(p, s_loc, s_ll, s_var, s_obj, s_objH, s_cls, s_clsH, Tf, C, cell, pr, o);
+    }
+}
+
+// The MC sample-count ladder (include/byolo.h "MC sample-count ladder"): decode_epi_kernel's walk -- same lane mapping, loads and
+// running sums -- taken rung by rung: t = 0 .. rungs[0] - 1, on to rungs[1] - 1, ..., and behind every rung the finish with
+// Tf = rungs[k].  After k samples the sums ARE what a T = k reduction of the image's first k samples holds, so rung k's row, written
+// into slab k (boxes + k * slab_stride, inside the slab at decode_epi_kernel's position), is decode_epi_kernel's row of those
+// samples.  The image stride of `raw` stays p.T samples whatever the rungs are, and the walk ends at the last rung.  The rung loop is
+// uniform across the launch, and the rungs are read from the kernel arguments only (scalar loads at a uniform index): nothing goes
+// to scratch.  Builds up to 48 class slots (the 128-slot build of the other decode kernels spills; tests/test_no_scratch.py exempts
+// only those): launch_decode_ladder refuses more.
+//
+// BIT FOR BIT is the contract, and sharing epi_finish_ is not enough for it.  Under -ffp-contract=fast the compiler decides per basic
+// block which product of a sum of two it fuses -- H = -(a log a + b log b) has two candidates -- after the SLP vectoriser has paired
+// the running sums, and it pairs them by where they are loaded and stored: decode_epi_kernel's T-shard paths (p.mode 1 and 2) among
+// them.  A walk without those paths, or without the check of the raw values, came out an ulp off in the summed entropies in most
+// builds (the mutual informations of a single sample were 0 in one kernel and 6e-8 in the other).  So the per-lane body below is
+// decode_epi_kernel's statement for statement, the sum load / store paths and `chk` included, although launch_decode_ladder admits
+// mode 0 only and its callers pass no status word (the forward's own decode has looked at the same raw values): they are never
+// taken.  tests/test_t_ladder_gpu.py holds every build to the decode, and profiles/t_ladder.md says how far the two kernels' machine
+// code agrees.  Change the walk of one kernel and the other must follow.
+template <int CM, bool EXACT>
+__global__ __launch_bounds__(256) void decode_epi_ladder_kernel(const DecodeParams p, const LadderParams r) {
+    const int C = EXACT ? CM : p.C;
+    const int BLK = 2 * (5 + C), D = 21 + C;
+    const int LDC = p.ld ? p.ld : 3 * BLK;
+    const int cells = p.lh * p.lw;
+    const int64_t total = (int64_t)p.B * cells * 3;
+    const size_t sample_stride = (size_t)cells * LDC;
+    for (int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; gid < total;
+         gid += (int64_t)gridDim.x * blockDim.x) {
+        const int pr = (int)(gid % 3);
+        const int64_t bc = gid / 3;
+        const int cell = (int)(bc % cells), b = (int)(bc / cells);
+        const float* d0 = p.raw + ((size_t)b * p.T) * sample_stride + (size_t)cell * LDC + pr * BLK;
+        float s_loc[4] = {0, 0, 0, 0}, s_ll[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, s_var[4] = {0, 0, 0, 0};
+        float s_obj = 0.f, s_objH = 0.f, s_cls[CM], s_clsH = 0.f;
+        float chk = 0.f;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) ev[i] = s_loc[i] / Tf;
-        {
-            int q = 0;
+        for (int c = 0; c < CM; ++c) s_cls[c] = 0.f;
+        float* o = p.boxes + ((size_t)b * p.n_total + p.box_base + (size_t)pr * cells + cell) * D;
+        if (p.mode == 2) {                                      // (never taken: see above)
 #pragma unroll
-            for (int i = 0; i < 4; ++i)
+            for (int i = 0; i < 4; ++i) { s_loc[i] = o[i]; s_var[i] = o[14 + i]; }
 #pragma unroll
-                for (int j = i; j < 4; ++j) {
-                    const float c = s_ll[q++] / Tf - ev[i] * ev[j];   // E[l l^T] - E[l]E[l]^T (layers.py:383)
-                    cov[i][j] = c; cov[j][i] = c;
+            for (int i = 0; i < 10; ++i) s_ll[i] = o[4 + i];
+            s_obj = o[18]; s_objH = o[19];
+#pragma unroll
+            for (int c = 0; c < CM; ++c) if (EXACT || c < C) s_cls[c] = o[20 + c];
+            s_clsH = o[20 + C];
+        }
+        int t = 0;
+        for (int k = 0; k < r.n_rungs; ++k) {                   // (uniform: every lane of the launch walks the same rungs)
+            const int next = r.rungs[k];
+            for (; t < next; ++t) {
+                const float* d = d0 + (size_t)t * sample_stride;
+                float v[10 + CM];                               // the two std logit groups are not decoded
+#pragma unroll
+                for (int i = 0; i < 10 + CM; ++i) if (EXACT || i < 10 + C) { v[i] = d[i]; chk = fmaf(v[i], 0.f, chk); }
+                int q = 0;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    s_loc[i] += v[i];
+                    s_var[i] += expf(v[4 + i]);
+#pragma unroll
+                    for (int j = i; j < 4; ++j) s_ll[q++] += v[i] * v[j];
                 }
+                const float obj = sigmoidf_(v[8]);
+                s_obj += obj;
+                s_objH += logistic_entropy_(obj);
+                float pc[CM];
+                softmax_<CM, EXACT>(v + 10, pc, C);
+#pragma unroll
+                for (int c = 0; c < CM; ++c) if (EXACT || c < C) s_cls[c] += pc[c];
+                s_clsH += softmax_entropy_<CM, EXACT>(pc, C);
+            }
+            if (p.mode == 1) {                                  // (never taken: see above)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) { o[i] = s_loc[i]; o[14 + i] = s_var[i]; }
+#pragma unroll
+                for (int i = 0; i < 10; ++i) o[4 + i] = s_ll[i];
+                o[18] = s_obj; o[19] = s_objH;
+#pragma unroll
+                for (int c = 0; c < CM; ++c) if (EXACT || c < C) o[20 + c] = s_cls[c];
+                o[20 + C] = s_clsH;
+                o += r.slab_stride;
+                continue;
+            }
+            epi_finish_<CM, EXACT>(p, s_loc, s_ll, s_var, s_obj, s_objH, s_cls, s_clsH, (float)next, C, cell, pr, o);
+            o += r.slab_stride;
         }
-        float out[17 + CM];
-        corners_(ev[0], ev[1], ev[2], ev[3], cell % p.lw, cell / p.lw, p.lw, p.lh, p.pw[pr], p.ph[pr], out);
-        float ale_sum = 0.f;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            out[4 + i] = cov[i][i];
-            const float a = s_var[i] / Tf;
-            out[8 + i] = a;
-            ale_sum += a;
-        }
-        out[12] = det4_(cov);
-        out[13] = ale_sum;
-        const float obj_mean = s_obj / Tf;
-        const float objH = logistic_entropy_(obj_mean);
-        out[14] = obj_mean;
-        out[15] = objH - s_objH / Tf;
-        out[16] = objH;
-#pragma unroll
-        for (int c = 0; c < CM; ++c) if (EXACT || c < C) out[17 + c] = s_cls[c] / Tf;
-        const float clsH = softmax_entropy_<CM, EXACT>(out + 17, C);
-#pragma unroll
-        for (int i = 0; i < 17 + CM; ++i) if (EXACT || i < 17 + C) o[i] = out[i];
-        o[17 + C] = clsH - s_clsH / Tf;
-        o[18 + C] = clsH;
-        o[19 + C] = (float)p.layer_id;
-        o[20 + C] = (float)pr;
+        if (chk != 0.f && p.status) atomicOr(p.status, 2u);
     }
 }
 
@@ -381,6 +483,33 @@ hipError_t launch_decode(int kind, const DecodeParams& p, hipStream_t st) {
     if (p.C <= 24) return launch_decode_c<24, false>(kind, p, st);
     if (p.C <= 48) return launch_decode_c<48, false>(kind, p, st);
     return launch_decode_c<BYOLO_MAX_CLASSES, false>(kind, p, st);
+}
+
+template <int CM, bool EXACT>
+static hipError_t launch_decode_ladder_c(const DecodeParams& p, const LadderParams& r, hipStream_t st) {
+    const int64_t total = (int64_t)p.B * p.lh * p.lw * 3;
+    const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(4096, (total + 255) / 256));
+    hipLaunchKernelGGL((decode_epi_ladder_kernel<CM, EXACT>), dim3((unsigned)blocks), dim3(256), 0, st, p, r);
+    return hipGetLastError();
+}
+
+// The exact and capacity builds of launch_decode below the 128-slot one; what the callers have checked is checked again, because
+// a rung outside 1 .. T walks past the end of `raw`.
+hipError_t launch_decode_ladder(const DecodeParams& p, const LadderParams& r, hipStream_t st) {
+    if (p.C < 1 || p.C > T_LADDER_MAX_CLASSES || p.mode != 0 || r.n_rungs < 1 || r.n_rungs > T_LADDER_MAX) return hipErrorInvalidValue;
+    for (int k = 0; k < r.n_rungs; ++k)
+        if (r.rungs[k] < (k ? r.rungs[k - 1] + 1 : 1) || r.rungs[k] > p.T) return hipErrorInvalidValue;
+    switch (p.C) {
+        case 1: return launch_decode_ladder_c<1, true>(p, r, st);
+        case 2: return launch_decode_ladder_c<2, true>(p, r, st);
+        case 3: return launch_decode_ladder_c<3, true>(p, r, st);
+        case 4: return launch_decode_ladder_c<4, true>(p, r, st);
+        case 8: return launch_decode_ladder_c<8, true>(p, r, st);
+        default: break;
+    }
+    if (p.C <= 8) return launch_decode_ladder_c<8, false>(p, r, st);
+    if (p.C <= 24) return launch_decode_ladder_c<24, false>(p, r, st);
+    return launch_decode_ladder_c<48, false>(p, r, st);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -58,6 +58,16 @@ region and by their height, AP and LAMR.  A box whose record label is 0 (`ignore
 the boxes to (`crop_img_size[0]` when `crop`, else `full_img_size[0]`).  The shards carry no occlusion tags: 'ecp_heights' is the
 height half of the EuroCity Persons subsets reasonable [40, inf), small [30, 60) and all [20, inf).
 
+`t_ladder` (a list of 1 .. 8 strictly increasing MC sample counts below `T`; the Bayesian model only; absent: off, metrics.json is
+what it was): the model still runs ONCE per batch at `T`; behind every forward `Engine.t_ladder` finishes the pre-NMS rows at each
+of these sample counts from the forward's own raw detection outputs (rung k: the decode of every image's first k samples, bit for
+bit -- INTEGRATION.md "MC sample-count ladder" says what that does and does not promise), each rung's rows pass through the tail the
+model is configured with (NMS or soft-NMS, then `score_recal`, then `box_vote`, by the standalone stages) and feed an evaluator of
+their own -- the IoU ladder, the subsets and the localisation tables included when set.  metrics.json gains 't_ladder':
+[{'T': k, **result}, ...] and one line per rung is logged, the full-T line last: mean AP, LAMR, ECE and, with the localisation
+tables, NLL and ENCE -- the evidence for choosing `T`.  Refused together with any `*_compare` key and with `box_vote_sweep`: one
+comparison per run.
+
 `Model.run` -> `Evaluator.add` per batch (byolo/evaluate.py: one matching kernel per batch on the forward's stream); batches
 run one after the other (`Model.run` re-runs a batch that leaves the split-f16 range in fp32 by itself).  One process, one
 GPU: multi-GPU evaluation is out of scope.  Writes `<out_path>_<step>/metrics.json`: the dict of `Evaluator.finish`, the
@@ -74,6 +84,7 @@ import numpy as np
 MODELS = {'standard': 'yolov3', 'aleatoric': 'yolov3_aleatoric', 'bayesian': 'bayesian_yolov3_aleatoric'}
 VOTE_SETTINGS = ('var', 'sigma_t', 'iou_min', 'min_score', 'var_floor')      # byolo.engine.Engine.box_vote
 MAX_SWEEP = 8
+MAX_T_LADDER = 8
 REQUIRED = ('full_img_size', 'cls_cnt', 'batch_size', 'crop', 'priors', 'implicit_background_class', 'data', 'out_path')
 
 
@@ -205,6 +216,23 @@ def check_config(config, model='bayesian'):
     cfg.setdefault('T', 1)
     if not 0.0 <= float(cfg['iou_thresh']) <= 1.0:
         raise ValueError('iou_thresh outside [0, 1]')
+    if cfg.get('t_ladder') is not None:                              # the key stays absent when absent
+        rungs = cfg['t_ladder']
+        if model != 'bayesian':
+            raise ValueError('t_ladder: only the bayesian model draws MC samples')
+        if not isinstance(rungs, (list, tuple)) or not 1 <= len(rungs) <= MAX_T_LADDER:
+            raise ValueError('t_ladder is a list of 1 .. {} sample counts'.format(MAX_T_LADDER))
+        if any(isinstance(r, bool) or not isinstance(r, (int, np.integer)) for r in rungs):
+            raise ValueError('t_ladder: every rung is an int, not {!r}'.format(list(rungs)))
+        rungs = [int(r) for r in rungs]
+        if rungs[0] < 1 or any(b <= a for a, b in zip(rungs, rungs[1:])):
+            raise ValueError('t_ladder: the rungs must be strictly increasing from 1 up, not {}'.format(rungs))
+        if rungs[-1] >= int(cfg['T']):
+            raise ValueError('t_ladder: every rung lies below T = {} (the full T is always scored), not {}'.format(int(cfg['T']), rungs))
+        others = [k for k in sorted(cfg) if k.endswith('_compare') and cfg[k]] + (['box_vote_sweep'] if cfg.get('box_vote_sweep') is not None else [])
+        if others:
+            raise ValueError('t_ladder together with {}: one comparison per run'.format(', '.join(others)))
+        cfg['t_ladder'] = rungs
     cfg['training'] = False
     cfg['aleatoric_loss'] = False
     cfg['inference_mode'] = True
@@ -234,8 +262,24 @@ def build_model(cfg):
     return m, checkpoint
 
 
+def rung_tail(eng, model, boxes):
+    """The tail `eng` is configured with on pre-NMS rows `boxes` [B, N, D] that its forward did not make (a rung of
+    Engine.t_ladder; variance recalibration is already in them), stage by stage in the forward's order by the standalone calls:
+    sort_nms or soft_nms, then score_recal, then box_vote.  Returns the dict of the NMS stage with 'rows' those of the last stage
+    (and 'score' / 'vote_n' where those stages run): at rung T it equals the forward's own result bit for bit."""
+    if eng._soft_nms is not None:
+        res = eng.soft_nms(boxes, model.obj_idx, model.cls_start_idx, **eng._soft_nms)
+    else:
+        res = eng.sort_nms(boxes, model.obj_idx, model.cls_start_idx)
+    if eng._score_recal is not None:
+        res.update(eng.score_recal(res['rows'], res['count'], eng._score_recal))
+    if eng._box_vote is not None:
+        res.update(eng.box_vote(boxes, res, model.obj_idx, model.cls_start_idx, geom=model.det_layers, **eng._box_vote))
+    return res
+
+
 def score(model, feed, evaluator, seed=0, max_batches=None, points=None, vote=None, vote_evaluator=None, sweep=(), soft=None,
-          soft_evaluator=None, recal=None, recal_evaluator=None, score_cal=None, score_evaluator=None):
+          soft_evaluator=None, recal=None, recal_evaluator=None, score_cal=None, score_evaluator=None, t_ladder=()):
     """Model.run -> Evaluator.add over the batches of `feed` (the 'eval' split of lib_yolo.dataset_utils._Feed); returns the
     number of images.  points: a list that receives (time, images so far) after every batch.  vote (settings) and
     vote_evaluator: every batch's NMS rows are also voted (Engine.box_vote) and the voted rows scored by vote_evaluator.
@@ -243,13 +287,21 @@ def score(model, feed, evaluator, seed=0, max_batches=None, points=None, vote=No
     soft_evaluator: Engine.soft_nms runs on every batch's pre-NMS rows beside the model's hard NMS (and, where the model votes, is
     voted with the same settings) and its rows are scored by soft_evaluator.  recal (a VarCalibration) and recal_evaluator:
     Engine.var_recal calibrates every batch's kept rows beside the raw ones and recal_evaluator scores them.  score_cal (a
-    ScoreCalibration) and score_evaluator: likewise with Engine.score_recal."""
+    ScoreCalibration) and score_evaluator: likewise with Engine.score_recal.  t_ladder: [(sample count, evaluator)], increasing
+    counts: Engine.t_ladder finishes every batch's pre-NMS rows at these counts right behind the forward, on the engine that ran
+    it, and each rung's rows go through rung_tail into its evaluator."""
     images = 0
     for step, b in enumerate(feed):
         if max_batches is not None and step >= max_batches:
             break
         res = model.run(b['img'], seed=seed + step, want_boxes=vote_evaluator is not None or soft_evaluator is not None)
         evaluator.add(res['rows'], res['count'][:, 0], b['boxes'], b['labels'], b['counts'])
+        if t_ladder:                                      # (reads the forward's workspace: nothing forwards on this engine in between)
+            eng = res.get('engine', model.engine)
+            slabs = eng.t_ladder([k for k, _ in t_ladder], int(b['img'].shape[0]), model.T)
+            for slab, (_, rev) in zip(slabs, t_ladder):
+                rres = rung_tail(eng, model, slab)
+                rev.add(rres['rows'], rres['count'][:, 0], b['boxes'], b['labels'], b['counts'])
         for settings, vev in ([(vote, vote_evaluator)] if vote_evaluator is not None else []) + list(sweep):
             voted = res.get('engine', model.engine).box_vote(res['boxes'], res, model.obj_idx, model.cls_start_idx,
                                                              geom=model.det_layers, **({} if settings is True else dict(settings)))
@@ -324,6 +376,31 @@ def sweep_lines(sweep, results, iou_thresh):
     return lines
 
 
+def _mean_over_gt(result, key):
+    vals = [c[key] for c in result['classes'] if c['n_gt'] > 0]
+    return float(np.cumsum(vals)[-1] / len(vals)) if vals else float('nan')
+
+
+def t_ladder_lines(results, iou_thresh):
+    """The table of a sample-count ladder: per entry of `results` ({'T': k, **result}; the full T last) the mean AP (of the IoU
+    ladder when there is one, else AP at iou_thresh), LAMR and ECE, each averaged over the classes with ground truth, and with
+    the localisation tables NLL and ENCE of the widest variance kind scored, averaged over the four coordinates."""
+    from byolo import eval_loc
+    lines = []
+    for r in results:
+        if 'ladder' in r:
+            what, ap = 'mean AP', r['ladder']['ap_mean']
+        else:
+            what, ap = 'AP at IoU {:.2f}'.format(iou_thresh), _mean_over_gt(r, 'ap')
+        line = 't_ladder T = {:3d}: {} {:.4f}, LAMR {:.4f}, ECE {:.4f}'.format(r['T'], what, ap, _mean_over_gt(r, 'lamr'), _mean_over_gt(r, 'ece'))
+        kinds = [k for k in eval_loc.KINDS if k in r.get('localisation', {})]
+        if kinds:
+            loc = r['localisation'][kinds[-1]]
+            line += ', {} variance NLL {:.4f}, ENCE {:.4f}'.format(kinds[-1], *[float(np.mean([loc[c][key] for c in eval_loc.COORDS])) for key in ('nll', 'ence')])
+        lines.append(line)
+    return lines
+
+
 def subset_options(cfg):
     """The Evaluator arguments of the config's eval_subsets keys ({} without them).  img_h: the frame the 'eval' split of the
     feed normalises the boxes to."""
@@ -365,14 +442,16 @@ def evaluate(config, model='bayesian'):
         score_cal.check(MODELS[cfg['model']], m.cls_cnt)
         score_cal.warn_settings(getattr(m.engine, '_soft_nms', None), getattr(m.engine, '_var_recal', None))
         ev_score = new_ev()
+    rungs = [(k, new_ev()) for k in (cfg.get('t_ladder') or [])]
     feed =dataset_utils._Feed(cfg, 'data', 'eval', device=m.engine.torch_device)
     try:
         t0 = time.time()
         points = []
         images = score(m, feed, ev, seed=int(cfg['seed']), max_batches=cfg['eval_batches'], points=points, vote=cfg['box_vote'],
                        vote_evaluator=ev_vote, sweep=sweep, soft=cfg.get('soft_nms'), soft_evaluator=ev_soft, recal=recal,
-                       recal_evaluator=ev_recal, score_cal=score_cal, score_evaluator=ev_score)
+                       recal_evaluator=ev_recal, score_cal=score_cal, score_evaluator=ev_score, t_ladder=rungs)
         metrics = ev.finish()
+        rung_metrics = [dict(e.finish(), T=k) for k, e in rungs]
         score_metrics = ev_score.finish() if ev_score is not None else None
         recal_metrics = ev_recal.finish() if ev_recal is not None else None
         soft_metrics = ev_soft.finish() if ev_soft is not None else None
@@ -392,6 +471,8 @@ def evaluate(config, model='bayesian'):
             ev_recal.close()
         if ev_score is not None:
             ev_score.close()
+        for _, e in rungs:
+            e.close()
     if score_metrics is not None:
         for c, v in zip(metrics['classes'], score_metrics['classes']):
             logging.info('class {:3d}: raw rows AP {:.4f}, LAMR {:.4f}, ECE {:.4f}; score_recal rows AP {:.4f}, LAMR {:.4f}, ECE {:.4f}'.format(
@@ -428,6 +509,9 @@ def evaluate(config, model='bayesian'):
         from byolo import eval_loc
         for line in eval_loc.log_lines(metrics['localisation']):
             logging.info(line)
+    if rungs:                                             # the full T last: the rung every other is read against
+        for line in t_ladder_lines(rung_metrics + [dict(metrics, T=int(cfg['T']))], cfg['iou_thresh']):
+            logging.info(line)
     metrics.update(images=images, checkpoint=checkpoint, model=MODELS[cfg['model']], loop_seconds=loop_seconds,
                    steady_img_s=steady_rate(points),
                    config=json.loads(json.dumps(cfg, default=lambda x: str(x))))
@@ -443,6 +527,8 @@ def evaluate(config, model='bayesian'):
     if score_metrics is not None:                         # likewise: the raw rows' result beside the score-recalibrated rows'
         metrics = dict({k: v for k, v in metrics.items() if k not in score_metrics}, raw={k: metrics[k] for k in score_metrics},
                        score_recal=score_metrics)
+    if rungs:
+        metrics['t_ladder'] = rung_metrics
     if sweep:
         metrics['box_vote_sweep'] = [dict(r, settings=settings) for (settings, _), r in zip(sweep, sweep_metrics)]
     with open(os.path.join(out_path, 'metrics.json'), 'w') as f:

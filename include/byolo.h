@@ -336,6 +336,35 @@ BYOLO_API int32_t byolo_decode(byolo_t* h, int32_t kind, const float* d_raw, int
 BYOLO_API int32_t byolo_epistemic_stats(byolo_t* h, const float* d_raw, int32_t B, int32_t T, int32_t lh, int32_t lw,
                                         float* d_ev_loc, float* d_epi_covar, float* d_obj_samples, float* d_cls_samples,
                                         void* stream);
+/* ---- MC sample-count ladder: the epistemic rows at several sample counts T from ONE forward ----
+ * The epistemic decode walks an image's T samples in order with running sums; the sums after k samples are what a T = k
+ * reduction of the image's first k samples holds.  One pass over the raw detection outputs therefore finishes the rows at every
+ * "rung" of a ladder of sample counts: rungs[0] < rungs[1] < ... , each in 1 .. T, at most BYOLO_T_LADDER_MAX of them; rung k's
+ * rows fill slab k of d_boxes [n_rungs][B][N][21+C].  Models of at most BYOLO_T_LADDER_MAX_CLASSES classes (the builds of the
+ * ladder kernel that keep their per-lane state in registers; more is refused with BYOLO_ERR_ARG).
+ *   byolo_decode_ladder   staged, one detection layer: like byolo_decode(kind = EPISTEMIC, ...), d_raw dense
+ *       [B*T, lh, lw, 3*2*(5+C)]; the layer's rows of rung k go to slab k at box offset box_base, nothing else is written.
+ *   byolo_forward_ladder  the LAST forward's raw detection outputs, every detection layer -> d_boxes [n_rungs][B][N][D]; with a
+ *       variance recalibration set on the handle (byolo_set_var_recal) every slab is recalibrated in place as a forward's rows
+ *       are, so a slab is what a forward would hand the NMS.
+ * What is promised: rung k is the existing decode of THIS forward's first k samples of every image, bit for bit (the slab of
+ * rung T equals the forward's own d_boxes).  Those samples are independent draws like any other k.
+ * What is NOT promised: that rung k equals a separate byolo_forward(T = k).  The per-layer plan (split-K, stream-K, the Winograd
+ * choice) depends on B*T and changes the order of summation, and for images after the first the dropout element index depends
+ * on T (see byolo_set_first_image), so such a forward draws other masks.
+ * Ordering: the call reads the workspace of the forward it follows.  It must be ordered on `stream` BEHIND that forward, and
+ * come BEFORE the next forward into the same workspace; it launches on `stream` and does not wait.
+ * BYOLO_ERR_STATE: no forward has run (or the plan is not valid).  BYOLO_ERR_ARG, before anything is launched: B or T are not
+ * the last forward's (this includes a batch beyond byolo_max_images, which ran in pieces), a T shard is set (byolo_set_tshard),
+ * a detection layer that is not epistemic or not stacked, no rungs, more than BYOLO_T_LADDER_MAX, rungs that are not strictly
+ * increasing or lie outside 1 .. T, more classes than the limit. */
+#define BYOLO_T_LADDER_MAX 16
+#define BYOLO_T_LADDER_MAX_CLASSES 48
+BYOLO_API int32_t byolo_decode_ladder(byolo_t* h, const float* d_raw, int32_t B, int32_t T, int32_t lh, int32_t lw,
+                            const float* priors_hw /*[3][2] host*/, int32_t layer_id, const int32_t* rungs /*host*/, int32_t n_rungs,
+                            float* d_boxes, int64_t n_total, int64_t box_base, void* stream);
+BYOLO_API int32_t byolo_forward_ladder(byolo_t* h, int32_t B, int32_t T, const int32_t* rungs /*host*/, int32_t n_rungs,
+                             float* d_boxes, void* stream);
 /* tf.image.non_max_suppression + tf.gather per image on d_boxes [B,N,D] (scores = column obj_idx).
  * d_sort_ws: >= byolo_nms_workspace_bytes(B, N), the size of two classes, enough for BYOLO_NMS_AGNOSTIC and BYOLO_NMS_TWO_CLASS;
  * BYOLO_NMS_PER_CLASS: >= byolo_nms_workspace_bytes_ex(B, N, nms_mode, cls_cnt) (the other modes: the same value as
