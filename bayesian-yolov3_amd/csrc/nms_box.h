@@ -54,9 +54,10 @@ __device__ __forceinline__ float iou_value_rn(const NBox& i, const NBox& j) {
 // ---- score and class of a row, as the NMS pipeline (tail_kernels.hip pc_*) and the vote stage (box_vote.hip) decide them ----
 __device__ __forceinline__ unsigned int score_key(float f) {
     // ascending key == descending score; NaN and scores <= -FLT_MAX are not candidates
-    // (TF: `score > std::numeric_limits<float>::lowest()`), they sort last.
+    // (TF: `score > std::numeric_limits<float>::lowest()`), they sort last.  Equal scores are equal keys: -0.0 == +0.0,
+    // so either zero takes the key of +0.0 and the row index alone orders them (a select: `f + 0.f` may be folded away).
     if (!(f > -FLT_MAX)) return 0xFFFFFFFFu;
-    unsigned int u = __float_as_uint(f);
+    unsigned int u = (f == 0.f) ? 0u : __float_as_uint(f);
     u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
     return ~u;
 }

@@ -366,6 +366,8 @@ BYOLO_API int32_t byolo_decode_ladder(byolo_t* h, const float* d_raw, int32_t B,
 BYOLO_API int32_t byolo_forward_ladder(byolo_t* h, int32_t B, int32_t T, const int32_t* rungs /*host*/, int32_t n_rungs,
                              float* d_boxes, void* stream);
 /* tf.image.non_max_suppression + tf.gather per image on d_boxes [B,N,D] (scores = column obj_idx).
+ * Visiting order: descending score, the lower row index first among equal scores.  Equal is the float32 comparison: -0.0 and
+ * +0.0 are one score and their rows are ordered by index alone.  A NaN score or one <= -FLT_MAX is no candidate.
  * d_sort_ws: >= byolo_nms_workspace_bytes(B, N), the size of two classes, enough for BYOLO_NMS_AGNOSTIC and BYOLO_NMS_TWO_CLASS;
  * BYOLO_NMS_PER_CLASS: >= byolo_nms_workspace_bytes_ex(B, N, nms_mode, cls_cnt) (the other modes: the same value as
  * byolo_nms_workspace_bytes; 0 for arguments the mode refuses).  BYOLO_NMS_AGNOSTIC ignores cls_start_idx.  The per-class mode takes
