@@ -81,6 +81,15 @@ class EvalSubsetsCfg(ctypes.Structure):
                 ("height_slack", ctypes.c_float), ("ignore_other_classes", ctypes.c_int32)]
 
 
+PDQ_MAX_DET, PDQ_MAX_FRAME, PDQ_RECORD_BYTES = 1024, 4096, 56             # BYOLO_PDQ_*
+
+
+class EvalPdqCfg(ctypes.Structure):
+    """include/byolo.h byolo_eval_pdq_cfg (field for field; tests/test_pdq_cpu.py compares the two)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("struct_bytes", "var", "ale_col", "epi_col", "img_h", "img_w")] + \
+               [("min_score", ctypes.c_float), ("reserved", ctypes.c_int32)] + [(n, ctypes.c_double) for n in ("p_min", "eps", "var_floor")]
+
+
 class EvalSummary(ctypes.Structure):
     """include/byolo.h byolo_eval_summary."""
     _fields_ = [(n, ctypes.c_int32) for n in ("struct_bytes", "overflow", "record_words", "reserved")] + \
@@ -243,6 +252,14 @@ PROTOTYPES = {
     "byolo_eval_set_subsets": (_i32, [_vp, _P(EvalSubsetsCfg), _vp, _vp]),
     "byolo_eval_subsets_records": (_i32, [_vp, _vp, _i64, _i64, _vp]),
     "byolo_eval_subsets_counts": (_i32, [_vp, _P(_i64), _i32, _vp]),
+    "byolo_eval_pdq_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "byolo_eval_pdq_state_bytes": (_sz, []),
+    "byolo_eval_set_pdq": (_i32, [_vp, _P(EvalPdqCfg), _P(EvalLocCfg), _vp, _i64, _vp, _i64, _vp, _vp, _sz]),
+    "byolo_eval_set_pdq_workspace": (_i32, [_vp, _vp, _sz]),
+    "byolo_eval_pdq_images": (_i32, [_vp, _vp, _i64, _i64, _P(_i64), _vp]),
+    "byolo_eval_pdq_pairs": (_i32, [_vp, _vp, _i64, _i64, _P(_i64), _vp]),
+    "byolo_eval_pdq_matrix": (_i32, [_vp, _i32, _P(_i32), _vp, _vp, _vp, _vp]),
+    "byolo_pdq_assign": (_i32, [_vp, _i32, _i32, _vp, _vp]),
     "byolo_box_vote_workspace_bytes": (_sz, [_i32, _i64]),
     "byolo_box_vote": (_i32, [_vp, _vp, _i32, _i64, _i32, _i32, _i32, _i32, _P(VoteCfg), _P(EvalLocCfg), _vp, _vp, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
     "byolo_set_box_vote": (_i32, [_vp, _P(VoteCfg)]),

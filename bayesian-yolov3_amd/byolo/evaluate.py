@@ -222,11 +222,17 @@ class Evaluator:
     detection is ignored when its own height is below min_height / height_slack or at least max_height * height_slack.
     ignore_other_classes: boxes of the other classes are ignore regions too.  A ground-truth label outside [0, cls_cnt) -- the
     feed's -1 for a record label 0 under implicit_background_class -- is an ignore region of every class.  The shards carry no
-    occlusion tags: a subset is a height range and nothing else.  Everything else is the same with and without subsets."""
+    occlusion tags: a subset is a height range and nothing else.  Everything else is the same with and without subsets.
+    pdq: probabilistic detection quality (byolo/pdq.py `settings`: None, True or a dict of var, min_score, p_min, eps, var_floor,
+    img_h, img_w); the result gains 'pdq'.  img_h / img_w: the pixel frame the boxes are normalised to.  pdq_images / pdq_pairs:
+    records the two PDQ tables hold (56 bytes each); one that does not fit makes `finish` raise ByoloError(ERR_NOMEM).  The pair
+    matrix of a batch lives in a workspace that `add` allocates and grows as the batches ask (`_pdq_workspace`).  A layout
+    dict may carry 'ale_col' / 'epi_col' where the rows are not a variant's.  Everything else is the same with and without it."""
 
     def __init__(self, model_or_layout, iou_thresh=0.5, min_score=0.0, capacity=1 << 20, device=None, table=None, loc=None, loc_table=None,
                  iou_thresholds=None, ladder_table=None, subsets=None, img_h=None, ignore_thresh=0.5, height_slack=1.25,
-                 ignore_other_classes=False, subsets_table=None):
+                 ignore_other_classes=False, subsets_table=None, pdq=None, img_w=None, pdq_images=1 << 16, pdq_pairs=1 << 20,
+                 pdq_image_table=None, pdq_pair_table=None):
         import torch
         lay = model_or_layout
         if not isinstance(lay, dict):
@@ -264,6 +270,9 @@ class Evaluator:
         self.subsets, self.subsets_table = height_subsets(subsets), None
         if self.subsets is not None:
             self._setup_subsets(img_h, ignore_thresh, height_slack, ignore_other_classes, subsets_table)
+        self.pdq = None
+        if pdq is not None and pdq is not False:
+            self._setup_pdq(lay, pdq, img_h, img_w, pdq_images, pdq_pairs, pdq_image_table, pdq_pair_table)
 
     def _side_table(self, given, words):
         """A table of `words` int32 words per record: a new one, or the caller's tensor (tests put a guard region behind it)."""
@@ -311,6 +320,58 @@ class Evaluator:
         for k, (lo, hi) in enumerate(ranges[:_lib.EVAL_SUBSETS_MAX]):
             cfg.lo[k], cfg.hi[k] = float(lo), float(hi)
         return lib.byolo_eval_set_subsets(self._h, ctypes.byref(cfg), ctypes.c_void_p(ptr), ctypes.c_void_p(counts_ptr))
+
+    def _setup_pdq(self, lay, pdq, img_h, img_w, n_images, n_pairs, image_table, pair_table):
+        """Checks the settings and allocates the two record tables and the state; the workspace follows the first batch."""
+        import torch
+        from . import pdq as _pdq
+        try:
+            variant = variant_of(self.row_len, self.cls_cnt)
+        except ValueError:
+            variant = None
+        cols = {'yolov3_aleatoric': (4, -1), 'bayesian_yolov3_aleatoric': (8, 4)}.get(variant, (-1, -1))
+        self._pdq_cols = (int(lay.get('ale_col', cols[0])), int(lay.get('epi_col', cols[1])))
+        self.pdq = _pdq.settings(pdq, self._pdq_cols[0], self._pdq_cols[1], img_h=img_h if img_h is None else int(img_h), img_w=img_w)
+        self._pdq_geom = None
+        if self.pdq['var'] != 'none':
+            ids = lay.get('id_cols') or (eval_loc.id_columns(variant, self.cls_cnt) if variant is not None else None)
+            if ids is None or lay.get('det_layers') is None:
+                raise ValueError("pdq: var %r needs the rows' layer_id / prior_id columns and a 'det_layers' entry" % (self.pdq['var'],))
+            self._pdq_geom = eval_loc.loc_cfg(ids[0], ids[1], eval_loc.geometry(lay['det_layers']))
+        self.pdq_image_capacity, self.pdq_pair_capacity = int(n_images), int(n_pairs)
+        words = _lib.PDQ_RECORD_BYTES // 8
+        tab = lambda given, n: torch.zeros((n, words), dtype=torch.int64, device=self.device) if given is None else given
+        self.pdq_image_table, self.pdq_pair_table = tab(image_table, self.pdq_image_capacity), tab(pair_table, self.pdq_pair_capacity)
+        for t, n in ((self.pdq_image_table, self.pdq_image_capacity), (self.pdq_pair_table, self.pdq_pair_capacity)):
+            assert t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.numel() >= n * words
+        assert lib.byolo_eval_pdq_state_bytes() % 8 == 0
+        self._pdq_state = torch.zeros(lib.byolo_eval_pdq_state_bytes() // 8, dtype=torch.int64, device=self.device)
+        self._pdq_ws = torch.zeros(1, dtype=torch.int64, device=self.device)      # grows with the batches (_pdq_workspace)
+        self._check(self._set_pdq(self._pdq_ws))                                  # refusals come now, not at the first add
+
+    def _set_pdq(self, ws, struct_bytes=None, **kw):
+        """byolo_eval_set_pdq with this evaluator's settings (kw: others) and the workspace tensor `ws`; returns its code."""
+        from . import pdq as _pdq
+        s = dict(self.pdq, **{k: v for k, v in kw.items() if k in self.pdq})
+        cfg = _pdq.cfg_of(s, kw.get('ale_col', self._pdq_cols[0]), kw.get('epi_col', self._pdq_cols[1]), struct_bytes)
+        geom = ctypes.byref(self._pdq_geom) if self._pdq_geom is not None else None
+        p = lambda t: ctypes.c_void_p(t.data_ptr() + kw.get('misalign', 0))
+        return lib.byolo_eval_set_pdq(self._h, ctypes.byref(cfg), geom, p(self.pdq_image_table), kw.get('image_capacity', self.pdq_image_capacity),
+                                      p(self.pdq_pair_table), kw.get('pair_capacity', self.pdq_pair_capacity), p(self._pdq_state), p(ws), ws.numel() * 8)
+
+    def _pdq_workspace(self, B, cap, gmax):
+        """The workspace of a batch.  It is the scratch of one `add` and the library takes a new one at any time
+        (byolo_eval_set_pdq_workspace), so it grows on demand: gmax is a batch's own padding, and a crowded image may come late in
+        a run.  A new one has room for twice the boxes per image that asked for it (at least 64), so a run allocates a few times
+        at the most.  The launches already on the stream keep the old one, which the allocator hands out again in stream order."""
+        import torch
+        need = lib.byolo_eval_pdq_workspace_bytes(B, cap, gmax)
+        if need <= self._pdq_ws.numel() * 8:
+            return
+        room = lib.byolo_eval_pdq_workspace_bytes(B, cap, min(_lib.EVAL_MAX_GT, max(2 * gmax, 64)))
+        self._pdq_ws.record_stream(torch.cuda.current_stream(self.device))
+        self._pdq_ws = torch.empty(max(need, room) // 8, dtype=torch.int64, device=self.device)
+        self._check(lib.byolo_eval_set_pdq_workspace(self._h, ctypes.c_void_p(self._pdq_ws.data_ptr()), self._pdq_ws.numel() * 8))
 
     def _setup_loc(self, lay, loc, loc_table):
         """Decides whether the residuals are recorded, and hands the geometry table and the loc table to the library."""
@@ -395,8 +456,11 @@ class Evaluator:
         gc = self._gt(gt_counts, torch.int32, ())
         assert gb.shape[0] == B and gl.shape[0] == B and gc.shape[0] == B
         p = lambda t: ctypes.c_void_p(t.data_ptr())
+        if self.pdq is not None:
+            self._pdq_workspace(B, cap, gmax)
         self._check(lib.byolo_eval_add(self._h, p(rows), B, cap, p(count), int(count.stride(0)), p(gb), p(gl), p(gc), gmax, self._stream()))
         self.sorted = None
+        self._pdq_last = (B, cap, gmax)
 
     def _summary(self):
         """byolo_eval_finish (waits for the stream): (its code, the summary, the eligible boxes per class)."""
@@ -507,7 +571,53 @@ class Evaluator:
             sub_h = sub.cpu().numpy()
             self.sorted['subsets_state'], self.sorted['subsets_cum_tp'], self.sorted['subsets_cum_fp'] = sub_h[0].astype(np.int32), sub_h[1], sub_h[2]
             out['subsets'] = subset_metrics(self.subsets, self.sorted['subsets_state'], sub_h[1], sub_h[2], start_h, self.subsets_counts(), self.n_images)
+        if self.pdq is not None:
+            from . import pdq as _pdq
+            out['pdq'] = _pdq.reduce(self.pdq_images(), self.pdq_pairs(), self.pdq)
         return out
+
+    # ---- probabilistic detection quality (byolo/pdq.py) ----------------------------------------------------------------------
+    def _pdq_fetch(self, fn, dtype, capacity):
+        """The records of one PDQ table (waits for the stream); ByoloError(ERR_NOMEM) when a record did not fit or an image had
+        more than 1024 detections."""
+        if self.pdq is None:
+            raise RuntimeError('pdq is off for this evaluator')
+        total = ctypes.c_int64()
+        rc = fn(self._h, None, 0, 0, ctypes.byref(total), self._stream())
+        n = min(int(total.value), capacity)
+        out = np.zeros(n, dtype=dtype)
+        if n:
+            rc = fn(self._h, out.ctypes.data_as(ctypes.c_void_p), 0, n, ctypes.byref(total), self._stream())
+        self._check(rc)
+        return out
+
+    def pdq_images(self):
+        """One record per image added, in image order (`pdq.IMAGE_DTYPE`): n_det, n_gt, n_tp, flags and the float64 sums of
+        pPDQ, Q_S, Q_L, exp(-L_FG), exp(-L_BG) over the image's true positives."""
+        from . import pdq as _pdq
+        return self._pdq_fetch(lib.byolo_eval_pdq_images, _pdq.IMAGE_DTYPE, self.pdq_image_capacity)
+
+    def pdq_matrix(self, image):
+        """For tests and tools: the pair matrix of image `image` of the LAST batch added -> {'rows' [n_det] in matching order,
+        'gts' [n_gt] the counted boxes, 'planes' [5, n_det, n_gt] float64: pPDQ, Q_S, Q_L, L_FG, L_BG}.  Waits for the stream."""
+        if self.pdq is None:
+            raise RuntimeError('pdq is off for this evaluator')
+        B, cap, gmax = self._pdq_last
+        nd = min(cap, _lib.PDQ_MAX_DET)
+        counts, rows, gts = np.zeros(2, np.int32), np.zeros(nd, np.int32), np.zeros(gmax, np.int32)
+        planes = np.zeros((5, nd, gmax), np.float64)
+        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        self._check(lib.byolo_eval_pdq_matrix(self._h, int(image), counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), vp(rows), vp(gts), vp(planes),
+                                              self._stream()))
+        n_det, n_gt = int(counts[0]), int(counts[1])
+        return {'rows': rows[:n_det].copy(), 'gts': gts[:n_gt].copy(), 'planes': planes[:, :n_det, :n_gt].copy()}
+
+    def pdq_pairs(self):
+        """One record per true positive (`pdq.PAIR_DTYPE`: img, row, gt, pPDQ, Q_S, Q_L, L_FG, L_BG), ordered by image and then
+        by the detection's place in its image's matching order (the device appends the images in no fixed order)."""
+        from . import pdq as _pdq
+        recs = self._pdq_fetch(lib.byolo_eval_pdq_pairs, _pdq.PAIR_DTYPE, self.pdq_pair_capacity)
+        return recs[np.argsort(recs['img'], kind='stable')]
 
     # ---- localisation: residuals against predicted variances ---------------------------------------------------------------
     def _loc_device(self, t, tf):

@@ -45,14 +45,19 @@
 // A true positive's box and its matched ground-truth box are taken back to the raw location values t_x, t_y, t_w, t_h at the
 // detection's own cell and prior (the row's layer_id / prior_id columns), in float64, one operation per line as
 // tests/_eval_loc_ref.py restates them; the residuals t(ground truth) - t(detection) go to a second table, six words per record.
+//
+// Probabilistic detection quality (byolo_eval_set_pdq): its three kernels live in eval_pdq.hip and follow the launches above on the
+// same stream; they read the rows and the ground truth, not the tables here.  This file keeps the handle and the C-ABI around them.
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
 #include <cstdio>
+#include <cstring>
 #include <new>
 #include <string>
 
 #include "../../include/byolo.h"
+#include "eval_pdq.h"
 #include "nms_box.h"
 
 namespace byk {
@@ -559,17 +564,19 @@ struct byolo_eval {
     byolo_eval_subsets_cfg subsets;                             // valid while d_subsets is set (byolo_eval_set_subsets)
     int32_t* d_subsets = nullptr;
     int32_t* d_subset_counts = nullptr;
+    byk::PdqSide pdq;                                           // valid while pdq.d_images is set (byolo_eval_set_pdq)
     std::string err;
 };
 
 static thread_local std::string g_eval_err;
 
-static int32_t efail(byolo_eval_t* ev, int32_t code, const char* fmt, ...) {
+int32_t byk::efail(byolo_eval_t* ev, int32_t code, const char* fmt, ...) {     // eval_pdq.h: csrc/eval_pdq.hip reports through it too
     char buf[512];
     va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
     if (ev) ev->err = buf; else g_eval_err = buf;
     return code;
 }
+using byk::efail;
 #define EVHIP(ev, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) \
     return efail(ev, BYOLO_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); } while (0)
 
@@ -615,6 +622,8 @@ extern "C" int32_t byolo_eval_reset(byolo_eval_t* ev, void* stream) {
     if (ev->d_subsets)
         EVHIP(ev, hipMemsetAsync(ev->d_subset_counts, 0, sizeof(int32_t) * (size_t)ev->subsets.n_subsets * (size_t)ev->cfg.cls_cnt,
                                  static_cast<hipStream_t>(stream)));
+    if (ev->pdq.d_images)
+        EVHIP(ev, hipMemsetAsync(ev->pdq.d_state, 0, byolo_eval_pdq_state_bytes(), static_cast<hipStream_t>(stream)));
     ev->launches = 0;
     ev->images = 0;
     return BYOLO_OK;
@@ -629,6 +638,9 @@ extern "C" int32_t byolo_eval_add(byolo_eval_t* ev, const float* d_rows, int32_t
     if (gmax < 1 || gmax > BYOLO_EVAL_MAX_GT) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_add: gmax outside 1 .. %d boxes per image", BYOLO_EVAL_MAX_GT);
     if (count_stride < 1) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_add: count_stride below 1");
     if (ev->images + B > 0x7fffffffll) return efail(ev, BYOLO_ERR_ARG, "byolo_eval_add: more than 2^31 - 1 images");
+    if (ev->pdq.d_images && byk::pdq_workspace_bytes(B, cap, gmax) > ev->pdq.ws_bytes)
+        return efail(ev, BYOLO_ERR_NOMEM, "byolo_eval_add: the PDQ workspace holds %zu bytes, this batch needs byolo_eval_pdq_workspace_bytes(%d, %d, %d) = %zu",
+                     ev->pdq.ws_bytes, B, cap, gmax, byk::pdq_workspace_bytes(B, cap, gmax));
     byk::EvalArgs a;
     a.rows = d_rows; a.count = d_count; a.count_stride = count_stride;
     a.gt_boxes = d_gt_boxes; a.gt_labels = d_gt_labels; a.gt_counts = d_gt_counts;
@@ -677,6 +689,15 @@ extern "C" int32_t byolo_eval_add(byolo_eval_t* ev, const float* d_rows, int32_t
         }
         hipLaunchKernelGGL(byk::eval_subset_kernel, dim3(B), dim3(64 * sa.n_sub), 0, static_cast<hipStream_t>(stream), sa);
         EVHIP(ev, hipGetLastError());
+    }
+    if (ev->pdq.d_images) {                                     // csrc/eval_pdq.hip: reads the rows and the ground truth, none of the tables above
+        byk::PdqBatch pb;
+        pb.rows = d_rows; pb.count = d_count; pb.count_stride = count_stride;
+        pb.gt_boxes = d_gt_boxes; pb.gt_labels = d_gt_labels; pb.gt_counts = d_gt_counts;
+        pb.B = B; pb.cap = cap; pb.D = ev->cfg.row_len; pb.obj_idx = ev->cfg.obj_idx; pb.cls_start = ev->cfg.cls_start_idx; pb.C = ev->cfg.cls_cnt;
+        pb.gmax = gmax; pb.img_base = a.img_base;
+        EVHIP(ev, byk::pdq_launch(ev->pdq, pb, static_cast<hipStream_t>(stream)));
+        ev->pdq.last_B = B; ev->pdq.last_cap = cap; ev->pdq.last_gmax = gmax;
     }
     ev->launches += 1;
     ev->images += B;
@@ -838,5 +859,90 @@ extern "C" int32_t byolo_eval_subsets_counts(byolo_eval_t* ev, int64_t* h_counts
     EVHIP(ev, hipMemcpyAsync(st, ev->d_subset_counts, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
     EVHIP(ev, hipStreamSynchronize(s));
     for (int k = 0; k < n; ++k) h_counts[k] = st[k];
+    return BYOLO_OK;
+}
+
+// ---- probabilistic detection quality (csrc/eval_pdq.hip) ---------------------------------------------------------------------
+extern "C" int32_t byolo_eval_set_pdq(byolo_eval_t* ev, const byolo_eval_pdq_cfg* cfg, const byolo_eval_loc_cfg* geom, void* d_image_table,
+                                      int64_t image_capacity, void* d_pair_table, int64_t pair_capacity, void* d_state, void* d_workspace,
+                                      size_t workspace_bytes) {
+    const char* fn = "byolo_eval_set_pdq";
+    if (!ev) return efail(nullptr, BYOLO_ERR_ARG, "%s: null handle", fn);
+    if (ev->launches) return efail(ev, BYOLO_ERR_STATE, "%s: records were added since the last byolo_eval_reset", fn);
+    if (!d_image_table) { ev->pdq.d_images = nullptr; return BYOLO_OK; }
+    if (!cfg) return efail(ev, BYOLO_ERR_ARG, "%s: null cfg", fn);
+    if (cfg->struct_bytes != (int32_t)sizeof(byolo_eval_pdq_cfg))
+        return efail(ev, BYOLO_ERR_ARG, "%s: struct_bytes %d, this library's byolo_eval_pdq_cfg has %d", fn, cfg->struct_bytes, (int)sizeof(byolo_eval_pdq_cfg));
+    if (const char* why = byk::pdq_check(cfg, geom, ev->cfg.row_len)) return efail(ev, BYOLO_ERR_ARG, "%s: %s", fn, why);
+    if (image_capacity < 1 || image_capacity > 0x7fffffffll || pair_capacity < 1 || pair_capacity > 0x7fffffffll)
+        return efail(ev, BYOLO_ERR_ARG, "%s: a capacity outside 1 .. 2^31 - 1 records", fn);
+    if (!d_pair_table || !d_state || !d_workspace) return efail(ev, BYOLO_ERR_ARG, "%s: null d_pair_table / d_state / d_workspace", fn);
+    if ((reinterpret_cast<uintptr_t>(d_image_table) | reinterpret_cast<uintptr_t>(d_pair_table) | reinterpret_cast<uintptr_t>(d_state) |
+         reinterpret_cast<uintptr_t>(d_workspace)) & 7)
+        return efail(ev, BYOLO_ERR_ARG, "%s: the tables, d_state and d_workspace must be 8-byte aligned", fn);
+    EVHIP(ev, byk::pdq_prepare(*cfg));                          // the last thing that can fail, and before any batch is launched
+    ev->pdq.cfg = *cfg;
+    if (cfg->var != BYOLO_VOTE_NONE) ev->pdq.geom = *geom;
+    ev->pdq.d_pairs = d_pair_table; ev->pdq.d_state = d_state; ev->pdq.d_ws = d_workspace;
+    ev->pdq.image_capacity = image_capacity; ev->pdq.pair_capacity = pair_capacity; ev->pdq.ws_bytes = workspace_bytes;
+    ev->pdq.d_images = d_image_table;
+    ev->pdq.last_B = 0;
+    return BYOLO_OK;
+}
+
+// The workspace carries nothing from one byolo_eval_add to the next, so it alone may be replaced at any time: the launches already on
+// the stream keep the pointer they were given, which the caller keeps alive in stream order
+extern "C" int32_t byolo_eval_set_pdq_workspace(byolo_eval_t* ev, void* d_workspace, size_t workspace_bytes) {
+    const char* fn = "byolo_eval_set_pdq_workspace";
+    if (!ev) return efail(nullptr, BYOLO_ERR_ARG, "%s: null handle", fn);
+    if (!ev->pdq.d_images) return efail(ev, BYOLO_ERR_STATE, "%s: no PDQ tables are set (byolo_eval_set_pdq)", fn);
+    if (!d_workspace) return efail(ev, BYOLO_ERR_ARG, "%s: null d_workspace", fn);
+    if (reinterpret_cast<uintptr_t>(d_workspace) & 7) return efail(ev, BYOLO_ERR_ARG, "%s: d_workspace must be 8-byte aligned", fn);
+    ev->pdq.d_ws = d_workspace;
+    ev->pdq.ws_bytes = workspace_bytes;
+    ev->pdq.last_B = 0;                                         // byolo_eval_pdq_matrix: the new workspace holds no batch yet
+    return BYOLO_OK;
+}
+
+// byolo_eval_pdq_images / _pairs (fn): the count so far, then n_records records from `first` of d_table
+static int32_t fetch_pdq(byolo_eval_t* ev, const char* fn, bool pairs, void* h_dst, int64_t first, int64_t n_records, int64_t* n_total, void* stream) {
+    if (!ev) return efail(nullptr, BYOLO_ERR_ARG, "%s: null handle", fn);
+    if (!ev->pdq.d_images) return efail(ev, BYOLO_ERR_STATE, "%s: no PDQ tables are set (byolo_eval_set_pdq)", fn);
+    const int64_t capacity = pairs ? ev->pdq.pair_capacity : ev->pdq.image_capacity;
+    if (first < 0 || n_records < 0 || first + n_records > capacity) return efail(ev, BYOLO_ERR_ARG, "%s: records outside the table", fn);
+    if (n_records && !h_dst) return efail(ev, BYOLO_ERR_ARG, "%s: null argument", fn);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int32_t st[byk::PDQ_ST_WORDS];
+    EVHIP(ev, hipMemcpyAsync(st, ev->pdq.d_state, sizeof st, hipMemcpyDeviceToHost, s));
+    if (n_records)
+        EVHIP(ev, hipMemcpyAsync(h_dst, static_cast<const char*>(pairs ? ev->pdq.d_pairs : ev->pdq.d_images) + (size_t)first * BYOLO_PDQ_RECORD_BYTES,
+                                 (size_t)n_records * BYOLO_PDQ_RECORD_BYTES, hipMemcpyDeviceToHost, s));
+    EVHIP(ev, hipStreamSynchronize(s));
+    unsigned long long cursor;
+    memcpy(&cursor, st + byk::PDQ_ST_CURSOR, sizeof cursor);
+    if (n_total) *n_total = pairs ? (int64_t)cursor : ev->images;
+    const int flags = st[byk::PDQ_ST_FLAGS];
+    if (flags)
+        return efail(ev, BYOLO_ERR_NOMEM, "%s: %s%s%s", fn, flags & byk::PDQ_FLAG_DET ? "an image had more than 1024 detections at min_score; " : "",
+                     flags & byk::PDQ_FLAG_IMAGES ? "more images than the image table holds; " : "",
+                     flags & byk::PDQ_FLAG_PAIRS ? "more true positives than the pair table holds" : "");
+    return BYOLO_OK;
+}
+
+extern "C" int32_t byolo_eval_pdq_images(byolo_eval_t* ev, void* h_dst, int64_t first, int64_t n_records, int64_t* n_total, void* stream) {
+    return fetch_pdq(ev, "byolo_eval_pdq_images", false, h_dst, first, n_records, n_total, stream);
+}
+
+extern "C" int32_t byolo_eval_pdq_pairs(byolo_eval_t* ev, void* h_dst, int64_t first, int64_t n_records, int64_t* n_total, void* stream) {
+    return fetch_pdq(ev, "byolo_eval_pdq_pairs", true, h_dst, first, n_records, n_total, stream);
+}
+
+extern "C" int32_t byolo_eval_pdq_matrix(byolo_eval_t* ev, int32_t image, int32_t* h_counts, int32_t* h_rows, int32_t* h_gts, double* h_planes, void* stream) {
+    const char* fn = "byolo_eval_pdq_matrix";
+    if (!ev) return efail(nullptr, BYOLO_ERR_ARG, "%s: null handle", fn);
+    if (!ev->pdq.d_images || !ev->pdq.last_B) return efail(ev, BYOLO_ERR_STATE, "%s: no byolo_eval_add has run behind byolo_eval_set_pdq", fn);
+    if (!h_counts || !h_rows || !h_gts || !h_planes) return efail(ev, BYOLO_ERR_ARG, "%s: null argument", fn);
+    if (image < 0 || image >= ev->pdq.last_B) return efail(ev, BYOLO_ERR_ARG, "%s: image %d outside the last batch of %d", fn, image, ev->pdq.last_B);
+    EVHIP(ev, byk::pdq_fetch_matrix(ev->pdq, ev->pdq.last_cap, ev->pdq.last_gmax, image, h_counts, h_rows, h_gts, h_planes, static_cast<hipStream_t>(stream)));
     return BYOLO_OK;
 }

@@ -68,6 +68,13 @@ their own -- the IoU ladder, the subsets and the localisation tables included wh
 tables, NLL and ENCE -- the evidence for choosing `T`.  Refused together with any `*_compare` key and with `box_vote_sweep`: one
 comparison per run.
 
+`pdq` (True, or a dict of `var`, `min_score`, `p_min`, `eps`, `var_floor`; absent: off, metrics.json is what it was): probabilistic
+detection quality (Hall et al., WACV 2020; INTEGRATION.md "Evaluation" has the definition), the detection-level figure that reads
+the predicted variances.  The pixel frame is the one the 'eval' split normalises the boxes to.  Every evaluator of the run carries it
+-- the voted rows', the soft-NMS rows', the recalibrated rows', every sweep entry's and every `t_ladder` rung's -- so every result
+dict gains 'pdq' and one line per result is logged: one run shows PDQ raw against recalibrated.  PDQ's `min_score` (0.5) is its
+own operating point; the evaluator's `min_score` does not enter it.
+
 `Model.run` -> `Evaluator.add` per batch (byolo/evaluate.py: one matching kernel per batch on the forward's stream); batches
 run one after the other (`Model.run` re-runs a batch that leaves the split-f16 range in fp32 by itself).  One process, one
 GPU: multi-GPU evaluation is out of scope.  Writes `<out_path>_<step>/metrics.json`: the dict of `Evaluator.finish`, the
@@ -193,6 +200,12 @@ def check_config(config, model='bayesian'):
             raise ValueError('eval_height_slack must be finite and at least 1')
         if cfg['eval_ignore_other_classes'] not in (True, False):
             raise ValueError('eval_ignore_other_classes is True or False')
+    if cfg.get('pdq') is not None:                                    # the key stays absent when absent
+        from byolo import pdq as _pdq
+        h, w = (cfg['crop_img_size'] if cfg['crop'] else cfg['full_img_size'])[:2]
+        ale_col, epi_col = {'standard': (-1, -1), 'aleatoric': (4, -1), 'bayesian': (8, 4)}[model]
+        if cfg['pdq'] is not False:
+            _pdq.settings(cfg['pdq'], ale_col, epi_col, img_h=int(h), img_w=int(w))         # ValueError on bad settings
     if cfg.get('box_vote_sweep') is not None:
         sweep = cfg['box_vote_sweep']
         if not cfg['box_vote_compare']:
@@ -411,6 +424,18 @@ def subset_options(cfg):
                 ignore_other_classes=cfg.get('eval_ignore_other_classes', False))
 
 
+def pdq_options(cfg):
+    """The Evaluator arguments of the config's pdq key ({} without it, or with False).  The frame is the one the 'eval' split of
+    the feed normalises the boxes to, as for the subsets."""
+    if cfg.get('pdq') is None or cfg['pdq'] is False:
+        return {}
+    h, w = (cfg['crop_img_size'] if cfg['crop'] else cfg['full_img_size'])[:2]
+    opts = dict(pdq=cfg['pdq'], img_w=int(w))
+    if cfg.get('eval_subsets') is None:                  # with subsets, subset_options hands over the same img_h
+        opts['img_h'] = int(h)
+    return opts
+
+
 def evaluate(config, model='bayesian'):
     """Scores the checkpoint and writes <out_path>_<step>/metrics.json; returns its content."""
     from byolo import inference as _inf
@@ -424,7 +449,7 @@ def evaluate(config, model='bayesian'):
     out_path = '{}_{}'.format(cfg['out_path'], _inf.step_of(checkpoint))
     os.makedirs(out_path)                                 # like the inference scripts: refuses to overwrite an existing run
     new_ev = lambda: Evaluator(m, iou_thresh=cfg['iou_thresh'], min_score=cfg['min_score'], capacity=cfg['eval_capacity'], loc=cfg['localisation'],
-                               iou_thresholds=cfg.get('iou_thresholds'), **subset_options(cfg))
+                               iou_thresholds=cfg.get('iou_thresholds'), **subset_options(cfg), **pdq_options(cfg))
     ev = new_ev()
     ev_vote = new_ev() if cfg['box_vote_compare'] else None
     sweep = [(settings, new_ev()) for settings in (cfg.get('box_vote_sweep') or [])]
@@ -503,6 +528,15 @@ def evaluate(config, model='bayesian'):
         from byolo.evaluate import subset_lines
         for line in subset_lines(metrics['subsets']):
             logging.info(line)
+    if 'pdq' in metrics:                                  # one line per result: raw against voted, recalibrated, every rung
+        from byolo.pdq import log_line
+        named = [('', metrics), ('box_vote rows: ', voted_metrics), ('soft-NMS rows: ', soft_metrics), ('var_recal rows: ', recal_metrics),
+                 ('score_recal rows: ', score_metrics)]
+        named += [('box_vote_sweep[{}]: '.format(k), r) for k, r in enumerate(sweep_metrics)]
+        named += [('t_ladder T = {:3d}: '.format(r['T']), r) for r in rung_metrics]
+        for prefix, r in named:
+            if r is not None:
+                logging.info(log_line(r['pdq'], prefix))
     for line in sweep_lines(cfg.get('box_vote_sweep') or [], sweep_metrics, cfg['iou_thresh']):
         logging.info(line)
     if 'localisation' in metrics:
@@ -559,6 +593,7 @@ def main(argv=None):
         'iou_thresh': 0.5,
         'min_score': 0.0,
         # 'eval_subsets': 'ecp_heights',  # LAMR / AP per height subset with ignore regions, as the pedestrian benchmarks score
+        # 'pdq': True,  # probabilistic detection quality (or a dict of settings: var, min_score, p_min, eps, var_floor)
         'data': {
             'path': '$HOME/data/ecp/tfrecords',  # edit
             'file_pattern': 'ecp-day-val-*-of-*',  # edit: LABELLED shards

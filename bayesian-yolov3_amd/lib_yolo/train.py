@@ -210,7 +210,9 @@ class EvalHook:
     'coco' or a list, as byolo.evaluate.Evaluator's iou_thresholds) adds '{step} evlad >>> class c: AP@0.50 .., ..., mean ..'.
     config['eval_subsets'] (absent: off; 'ecp_heights' or a list, as byolo.evaluate.Evaluator's subsets, with the optional
     'eval_ignore_thresh', 'eval_height_slack' and 'eval_ignore_other_classes') adds
-    '{step} evsub >>> reasonable class 0: LAMR .., AP .., n_gt ..; ...' (`evsub_line`).  Reads the trainer, never writes it; the
+    '{step} evsub >>> reasonable class 0: LAMR .., AP .., n_gt ..; ...' (`evsub_line`).  config['eval_pdq'] (absent: off; True or a
+    dict of settings, as byolo.evaluate.Evaluator's pdq) adds '{step} evpdq >>> PDQ .., pPDQ .., spatial .., label .., TP/FP/FN ..'.
+    Reads the trainer, never writes it; the
     'eval' split draws no random number, so the training and validation streams are what they are without the hook."""
 
     def __init__(self, model_cls, config):
@@ -242,6 +244,9 @@ class EvalHook:
             subsets=cfg['eval_subsets'], img_h=(cfg['crop_img_size'] if cfg['crop'] else cfg['full_img_size'])[0],
             ignore_thresh=cfg.get('eval_ignore_thresh', 0.5), height_slack=cfg.get('eval_height_slack', 1.25),
             ignore_other_classes=cfg.get('eval_ignore_other_classes', False))
+        if cfg.get('eval_pdq') is not None and cfg['eval_pdq'] is not False:
+            h, w = (cfg['crop_img_size'] if cfg['crop'] else cfg['full_img_size'])[:2]
+            sub = dict(sub, pdq=cfg['eval_pdq'], img_h=int(h), img_w=int(w))
         ev = Evaluator(self.model, capacity=int(cfg.get('eval_capacity', 1 << 18)), iou_thresholds=cfg.get('eval_iou_thresholds'), **sub)
         feed = dataset_utils._Feed(self.config, 'val', 'eval', device=self.model.engine.torch_device)
         try:
@@ -268,6 +273,9 @@ class EvalHook:
                 ', mean {:.4f}'.format(c['ap_mean']) for c in lad['classes']) + '; mean AP {:.4f}'.format(lad['ap_mean']))
         if 'subsets' in self.last:
             logging.info(evsub_line(step, self.last['subsets']))
+        if 'pdq' in self.last:
+            from byolo.pdq import log_line
+            logging.info(log_line(self.last['pdq'], prefix='{:5d} evpdq >>> '.format(step)))
         return self.last
 
     def close(self):

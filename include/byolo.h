@@ -754,6 +754,77 @@ BYOLO_API int32_t byolo_eval_set_subsets(byolo_eval_t* ev, const byolo_eval_subs
 BYOLO_API int32_t byolo_eval_subsets_records(byolo_eval_t* ev, int32_t* h_dst, int64_t first, int64_t n_records, void* stream);
 BYOLO_API int32_t byolo_eval_subsets_counts(byolo_eval_t* ev, int64_t* h_counts, int32_t n_counts, void* stream);
 
+/* Probabilistic detection quality (Hall et al., WACV 2020; csrc/eval_pdq.hip; INTEGRATION.md "Evaluation" has the definition in
+ * full, tests/_pdq_ref.py restates it).  With the PDQ tables set, byolo_eval_add launches three more kernels behind the matching
+ * on the same stream (no host wait): the image's detections and counted boxes are listed, every (detection, box) pair gets its
+ * spatial and label quality, and the one-to-one assignment that maximises the sum of pPDQ is found per image.  All float64.
+ *   detections     kept rows whose score (class and score as above) is finite and >= cfg.min_score -- the evaluator's own
+ *                  min_score is not applied --, in descending score, ties to the lower row.  More than BYOLO_PDQ_MAX_DET in one
+ *                  image raise the overflow flag; none is dropped silently
+ *   counted box    label inside [0, cls_cnt), finite corners and a non-empty pixel rectangle u in [ceil(X0 - 0.5), ceil(X1 - 0.5))
+ *                  clipped to the frame (X0 = x0 * img_w ...).  No ignore handling
+ *   detection      Gaussian corners: means X0 = x0 * img_w ..., sx^2 = max((var_cx + var_w / 4) * img_w^2, var_floor) with var_cx,
+ *                  var_w as the variance voting forms them (var, ale_col, epi_col, geom as there; BYOLO_VOTE_NONE: 0).
+ *                  px[u] = Phi((u + 0.5 - X0) / sx) * Phi((X1 - u - 0.5) / sx), p(u, v) = px[u] * py[v], segment {p >= p_min}.
+ *                  A row with a non-finite box value, bad ids or a variance that is not finite and >= 0 matches nothing
+ *   pair           without a shared pixel every value is 0; otherwise L_FG = -(1 / |G|) sum over G of log(max(p if p >= p_min
+ *                  else 0, eps)), L_BG = -(1 / |G|) sum over segment \ G of log(max(1 - p, eps)), Q_S = exp(-(L_FG + L_BG)),
+ *                  Q_L = obj * cls[label] (one float32 multiply, clamped to [0, 1], NaN: 0), pPDQ = sqrt(Q_S * Q_L)
+ *   assignment     shortest augmenting paths with potentials on cost = -pPDQ; the smaller side is the rows (equal: the
+ *                  detections), the column minimum of a step goes to the lowest column on ties.  A true positive is an
+ *                  assigned pair with pPDQ > 0
+ *   image record   BYOLO_PDQ_RECORD_BYTES bytes at index (image sequence number): int32 n_det, n_gt, n_tp, flags (bit 0: the
+ *                  image had too many detections and none was evaluated); float64 sum of pPDQ, Q_S, Q_L, exp(-L_FG),
+ *                  exp(-L_BG) over the true positives in ascending detection order
+ *   pair record    one per true positive, appended through an atomic cursor (images in no fixed order): int32 image, row, box,
+ *                  0; float64 pPDQ, Q_S, Q_L, L_FG, L_BG
+ * d_image_table / d_pair_table hold image_capacity / pair_capacity records, d_state byolo_eval_pdq_state_bytes() bytes (zeroed by
+ * byolo_eval_reset while set), d_workspace byolo_eval_pdq_workspace_bytes(B, cap, gmax) bytes for the batch that is added (0: an
+ * argument outside byolo_eval_add's limits); all caller-owned and 8-byte aligned.  A NULL image table switches PDQ off.  Nothing is
+ * written beyond either capacity; a record that does not fit raises the overflow flag.  byolo_eval_add returns BYOLO_ERR_NOMEM,
+ * before anything is launched, for a batch the workspace is too small for.
+ * The workspace is the scratch of ONE byolo_eval_add and carries nothing to the next, so it alone may be replaced at any time,
+ * also between two adds: byolo_eval_set_pdq_workspace(ev, d_workspace, workspace_bytes) -- a batch with more boxes per image than
+ * any before it (gmax is a batch's own padding) needs a larger one.  The launches already on the stream keep the old pointer: free
+ * it in stream order.  BYOLO_ERR_STATE without PDQ tables, BYOLO_ERR_ARG for a NULL or misaligned pointer.
+ * byolo_eval_set_pdq is refused with BYOLO_ERR_STATE between the first byolo_eval_add and the next byolo_eval_reset, and with
+ * BYOLO_ERR_ARG for a wrong struct_bytes, an unknown var or one whose columns the rows do not have, min_score NaN, p_min outside
+ * (0, 1), eps outside (0, p_min], var_floor not finite and > 0, img_h / img_w outside 1 .. BYOLO_PDQ_MAX_FRAME, a geometry table
+ * beyond its limits (geom may be NULL with BYOLO_VOTE_NONE), a capacity below 1, a NULL or misaligned pointer.
+ * byolo_eval_pdq_images / _pairs wait for `stream`, store the number of records so far in *n_total (images: those added; pairs:
+ * the cursor, which may exceed the capacity) and copy n_records records from `first`; BYOLO_ERR_NOMEM after the copy when the
+ * overflow flag is up.
+ * byolo_eval_pdq_matrix (for tests and tools; waits for `stream`): what the workspace holds of image `image` of the LAST
+ * byolo_eval_add (B, cap, gmax its arguments, nd = min(cap, BYOLO_PDQ_MAX_DET)): h_counts [2] = n_det, n_gt (counted); h_rows [nd]
+ * the detections' rows in matching order; h_gts [gmax] the counted boxes' indices; h_planes [5][nd][gmax] float64: pPDQ, Q_S, Q_L,
+ * L_FG, L_BG of detection d and counted box c at [k][d][c].  Only the first n_det / n_gt entries of each are defined.
+ * BYOLO_ERR_STATE before the first add behind byolo_eval_set_pdq or byolo_eval_set_pdq_workspace.
+ * byolo_pdq_assign: the assignment stage alone on a float64 matrix [n_det, n_gt] of pPDQ on the device (row-major, both sides
+ * 0 .. BYOLO_PDQ_MAX_DET, every entry finite); d_out_match [n_det] int32 receives each detection's box or -1. */
+#define BYOLO_PDQ_MAX_DET 1024
+#define BYOLO_PDQ_MAX_FRAME 4096
+#define BYOLO_PDQ_RECORD_BYTES 56
+typedef struct byolo_eval_pdq_cfg {
+    int32_t struct_bytes;          /* sizeof(byolo_eval_pdq_cfg) of the caller's header: a mismatch is BYOLO_ERR_ARG */
+    int32_t var;                   /* BYOLO_VOTE_* */
+    int32_t ale_col, epi_col;      /* as in byolo_vote_cfg */
+    int32_t img_h, img_w;
+    float min_score;
+    int32_t reserved;
+    double p_min, eps, var_floor;
+} byolo_eval_pdq_cfg;
+BYOLO_API size_t byolo_eval_pdq_workspace_bytes(int32_t B, int32_t cap, int32_t gmax);
+BYOLO_API size_t byolo_eval_pdq_state_bytes(void);
+BYOLO_API int32_t byolo_eval_set_pdq(byolo_eval_t* ev, const byolo_eval_pdq_cfg* cfg, const byolo_eval_loc_cfg* geom, void* d_image_table,
+                                     int64_t image_capacity, void* d_pair_table, int64_t pair_capacity, void* d_state, void* d_workspace,
+                                     size_t workspace_bytes);
+BYOLO_API int32_t byolo_eval_set_pdq_workspace(byolo_eval_t* ev, void* d_workspace, size_t workspace_bytes);
+BYOLO_API int32_t byolo_eval_pdq_images(byolo_eval_t* ev, void* h_dst, int64_t first, int64_t n_records, int64_t* n_total, void* stream);
+BYOLO_API int32_t byolo_eval_pdq_pairs(byolo_eval_t* ev, void* h_dst, int64_t first, int64_t n_records, int64_t* n_total, void* stream);
+BYOLO_API int32_t byolo_eval_pdq_matrix(byolo_eval_t* ev, int32_t image, int32_t* h_counts, int32_t* h_rows, int32_t* h_gts, double* h_planes,
+                                        void* stream);
+BYOLO_API int32_t byolo_pdq_assign(const double* d_matrix, int32_t n_det, int32_t n_gt, int32_t* d_out_match, void* stream);
+
 /* ---- variance voting (He et al., CVPR 2019; no counterpart in the reference; csrc/box_vote.hip; INTEGRATION.md "Variance voting"
  * has the definition in full, tests/_box_vote_ref.py restates it) -------------------------------------------------------------
  * After the NMS every kept row's box is replaced by the weighted mean of the pre-NMS boxes of its class that overlap it:
