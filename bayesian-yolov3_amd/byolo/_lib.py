@@ -142,6 +142,15 @@ class ScoreRecalCfg(ctypes.Structure):
                [("w", (ctypes.c_double * SCORE_RECAL_MAX_K) * SCORE_RECAL_MAX_GROUPS)]
 
 
+TTA_MAX_VIEWS = 8                                                        # BYOLO_TTA_MAX_VIEWS
+
+
+class TtaSupportCfg(ctypes.Structure):
+    """include/byolo.h byolo_tta_support_cfg (field for field; tests/test_tta_cpu.py compares the two)."""
+    _fields_ = [("struct_bytes", ctypes.c_int32), ("n_views", ctypes.c_int32), ("iou_min", ctypes.c_float), ("min_score", ctypes.c_float),
+                ("view_off", ctypes.c_int32 * (TTA_MAX_VIEWS + 1))]
+
+
 _i32, _i64, _f32 = ctypes.c_int32, ctypes.c_int64, ctypes.c_float
 _vp, _cp, _sz, _u64 = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint64
 _P = ctypes.POINTER
@@ -279,6 +288,10 @@ PROTOTYPES = {
     "byolo_score_recal_features": (_i32, [_P(ScoreRecalCfg), _vp, _i64, _i32, _i32, _i32, _i32, _P(ctypes.c_int32), _vp, _vp]),
     "byolo_score_recal_fit_workspace_bytes": (_sz, [_i64, _i32]),
     "byolo_score_recal_fit": (_i32, [_vp, _vp, _vp, _i32, _i64, _i32, ctypes.c_double, _i64, _vp, _vp, _sz, _vp]),
+    "byolo_tta_view_f32": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "byolo_tta_merge": (_i32, [_vp, _i32, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _i64, _vp]),
+    "byolo_tta_support_workspace_bytes": (_sz, [_i32, _i64]),
+    "byolo_tta_support": (_i32, [_vp, _vp, _i32, _i64, _i32, _i32, _i32, _i32, _P(TtaSupportCfg), _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 

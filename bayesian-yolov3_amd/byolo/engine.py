@@ -181,6 +181,28 @@ class Engine:
         t.finalize()
         return t
 
+    def at_size(self, img_hw):
+        """A new finalized handle with this graph, plan, precision and parameters for frames of another size (h, w), owned by the
+        caller: the model of a rescaled test-time-augmentation view (byolo/tta.py).  Its priors are this handle's rescaled by
+        (img_h / h, img_w / w) -- the rule of lib_yolo/model.py img_size_and_priors_if_crop: the network sees an object h / img_h times
+        larger in pixels while its normalised box stays the same.  The NMS-side stages (soft-NMS, voting, score recalibration) are
+        off on it; variance recalibration, which lives behind the decode, is on with the same table."""
+        h, w = int(img_hw[0]), int(img_hw[1])
+        sh, sw = self.cfg.img_h / float(h), self.cfg.img_w / float(w)
+        t = Engine((h, w, self.cfg.img_c), self.cfg.cls_cnt, self.cfg.drop_prob, self.cfg.max_out, self.cfg.iou_thresh, self.cfg.nms_mode,
+                   bool(self.cfg.keep_all_outputs), self.device)
+        for name, args in self._graph:
+            if name == 'add_detection':
+                args = (args[0], args[1], [(ph * sh, pw * sw) for ph, pw in args[2]])
+            getattr(t, name)(*args)
+        t.set_plan_opts(**self.plan_opts())
+        t.set_precision(self.precision)
+        if self._var_recal is not None:
+            t.set_var_recal(self._var_recal)
+        t.set_params(self.get_params())
+        t.finalize()
+        return t
+
     def drop_twin(self):
         if self._twin is not None:
             self._twin.close()
@@ -696,6 +718,83 @@ class Engine:
         res = dict(rows=rows, kept=kept, count=count)
         if int(nms_mode) == _lib.NMS_PER_CLASS:
             res["class_counts"] = self._class_counts(B, boxes.device, stream)
+        return res
+
+    # ---- test-time augmentation (include/byolo.h "test-time augmentation"; byolo/tta.py composes the stages) ------
+    TTA_DEFAULTS = dict(iou_min=0.5, min_score=0.001)          # starting values that nobody has tuned
+
+    @staticmethod
+    def tta_view(frames, flip, out_hw, out=None):
+        """byolo_tta_view_f32: float32 frames [B, sh, sw, 3] -> [B, h, w, 3], TF1's legacy bilinear resize (skipped at the same size)
+        and the left-right flip: the bytes byolo.augment.augment_batch gives for the matching uint8 frames."""
+        torch = _torch()
+        assert frames.is_cuda and frames.dtype == torch.float32 and frames.is_contiguous() and frames.dim() == 4 and frames.shape[3] == 3
+        B, sh, sw = (int(v) for v in frames.shape[:3])
+        h, w = int(out_hw[0]), int(out_hw[1])
+        if out is None:
+            out = torch.empty((B, h, w, 3), dtype=torch.float32, device=frames.device)
+        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (B, h, w, 3) and out.device == frames.device
+        stream = torch.cuda.current_stream(frames.device).cuda_stream
+        check(None, lib.byolo_tta_view_f32(ctypes.c_void_p(frames.data_ptr()), B, sh, sw, int(bool(flip)), h, w, ctypes.c_void_p(out.data_ptr()),
+                                           ctypes.c_void_p(stream)))
+        return out
+
+    def tta_merge(self, rows, union, row_off, flip=False, size_idx=0, kind=None, layer_col=None):
+        """byolo_tta_merge: one view's pre-NMS rows [B, Nv, D] into rows row_off .. of `union` [B, Nu, D], in place; returns `union`.
+        kind / layer_col default to what a row of D columns and this engine's class count is (standard rows have no layer id: -1)."""
+        torch = _torch()
+        for t in (rows, union):
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 3
+        B, Nv, D = (int(v) for v in rows.shape)
+        assert int(union.shape[0]) == B and int(union.shape[2]) == D and union.device == rows.device
+        C = self.cfg.cls_cnt
+        if kind is None:
+            kind = {5 + C: _lib.DET_STANDARD, 14 + C: _lib.DET_ALEATORIC, 21 + C: _lib.DET_EPISTEMIC}.get(D)
+            if kind is None:
+                raise ValueError("tta_merge: D: rows of %d columns are no rows of a model with %d classes" % (D, C))
+        if layer_col is None:
+            layer_col = -1 if int(kind) == _lib.DET_STANDARD else D - 2
+        stream = torch.cuda.current_stream(rows.device).cuda_stream
+        check(None, lib.byolo_tta_merge(ctypes.c_void_p(rows.data_ptr()), B, Nv, D, int(kind), int(layer_col), int(bool(flip)), int(size_idx),
+                                        ctypes.c_void_p(union.data_ptr()), int(union.shape[1]), int(row_off), ctypes.c_void_p(stream)))
+        return union
+
+    @classmethod
+    def _tta_support_cfg(cls, view_off, settings):
+        s = dict(cls.TTA_DEFAULTS, **dict(settings))
+        unknown = sorted(set(s) - set(cls.TTA_DEFAULTS))
+        if unknown:
+            raise TypeError("tta: unknown settings %s" % unknown)
+        off = [int(v) for v in view_off]
+        if not 2 <= len(off) <= _lib.TTA_MAX_VIEWS + 1:
+            raise ValueError("tta: view_off: 1 .. %d views" % _lib.TTA_MAX_VIEWS)
+        cfg = _lib.TtaSupportCfg(struct_bytes=ctypes.sizeof(_lib.TtaSupportCfg), n_views=len(off) - 1, iou_min=float(s["iou_min"]), min_score=float(s["min_score"]))
+        for v, o in enumerate(off):
+            cfg.view_off[v] = o
+        return cfg
+
+    def tta_support(self, union, nms_result, view_off, obj_idx, cls_start_idx, nms_mode=None, **settings):
+        """byolo_tta_support on the union [B, Nu, D] and the result of sort_nms / soft_nms on it: {'view_n', 'view_bits' [B, cap] int32,
+        'view_score' [B, cap], 'view_var' [B, cap, 4] float32}.  view_off: the V + 1 row offsets of the views.  Settings: iou_min
+        (0.5), min_score (0.001) -- starting values, not tuned."""
+        torch = _torch()
+        assert union.is_cuda and union.dtype == torch.float32 and union.is_contiguous() and union.dim() == 3
+        B, Nu, D = (int(v) for v in union.shape)
+        kept, count = nms_result["kept"], nms_result["count"]
+        cap = int(kept.shape[1])
+        assert kept.is_contiguous() and count.is_contiguous() and tuple(kept.shape) == (B, cap) and tuple(count.shape) == (B, 2)
+        nms_mode = self.cfg.nms_mode if nms_mode is None else nms_mode
+        cfg = self._tta_support_cfg(view_off, settings)
+        dev = union.device
+        wsb = int(lib.byolo_tta_support_workspace_bytes(B, Nu))
+        ws = torch.empty(max(wsb, 8), dtype=torch.uint8, device=dev)
+        res = dict(view_n=torch.empty((B, cap), dtype=torch.int32, device=dev), view_bits=torch.empty((B, cap), dtype=torch.int32, device=dev),
+                   view_score=torch.empty((B, cap), dtype=torch.float32, device=dev), view_var=torch.empty((B, cap, 4), dtype=torch.float32, device=dev))
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        p = lambda t: ctypes.c_void_p(t.data_ptr())
+        check(self._h, lib.byolo_tta_support(self._h, p(union), B, Nu, D, int(obj_idx), int(cls_start_idx), int(nms_mode), ctypes.byref(cfg), p(kept),
+                                             p(count), cap, p(res["view_n"]), p(res["view_bits"]), p(res["view_score"]), p(res["view_var"]), p(ws), wsb,
+                                             ctypes.c_void_p(stream)))
         return res
 
     def layer_output(self, idx):

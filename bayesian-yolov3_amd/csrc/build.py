@@ -12,7 +12,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 OUT = os.path.join(HERE, "..", "byolo", "libbyolo.so")
 SRCS = ["byolo_api.hip", "byolo_pack.hip", "byolo_plan.hip", "conv_igemm.hip", "conv_kernels.hip", "winograd.hip", "gemm_stream.hip", "wino_fused.hip", "wino_split.hip", "tail_kernels.hip", "box_vote.hip", "var_recal.hip", "score_recal.hip",
-        "train_kernels.hip", "train_heads.hip", "augment.hip", "eval_kernels.hip", "eval_pdq.hip", "host_io.cpp"]
+        "train_kernels.hip", "train_heads.hip", "augment.hip", "eval_kernels.hip", "eval_pdq.hip", "tta.hip", "host_io.cpp"]
 HDRS = ["byolo_kernels.h", "byolo_internal.h", "byolo_rng.h", "recal_common.h", "mfma_pipe.h", "epilogue.h", "nms_box.h", "eval_pdq.h", os.path.join("..", "..", "include", "byolo.h")]
 DEPS = SRCS + HDRS
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wno-unused-result"]
@@ -24,7 +24,8 @@ _EXACT_F32 = ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]
 # var_recal.hip: likewise the float64 terms of the fit and the factor of the apply (tests/_var_recal_ref.py)
 FILE_FLAGS = {"train_kernels.hip": _EXACT_F32, "augment.hip": _EXACT_F32, "eval_kernels.hip": _EXACT_F32, "box_vote.hip": _EXACT_F32,
               "var_recal.hip": _EXACT_F32, "score_recal.hip": _EXACT_F32,      # score_recal.hip: tests/_score_recal_ref.py
-              "eval_pdq.hip": _EXACT_F32}      # the assignment uses float64 add, subtract and compare only (tests/_pdq_ref.py)
+              "eval_pdq.hip": _EXACT_F32,      # the assignment uses float64 add, subtract and compare only (tests/_pdq_ref.py)
+              "tta.hip": _EXACT_F32}           # the view restates augment.hip's resize, the support its float64 moments (tests/_tta_ref.py)
 
 
 def build(force=False, verbose=False, ablate=0, ablate_wf=0, ablate_ws=0, jobs=None):

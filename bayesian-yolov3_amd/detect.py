@@ -116,8 +116,13 @@ def do_it(files, thresh, config, model_cls, cls_mapping, show=False, save_dir=No
     for file in files:
         img = load_img(config, img_size, file)
         x_dev.copy_(torch.from_numpy(img))
-        model.run(x_dev, seed=int(config.get('seed', 0)), want_nms=False, out=out)
-        boxes = box_op(model).cpu().numpy()
+        if getattr(model, 'tta', None) is not None:
+            # engine_options={'tta': ...}: the views are merged in front of the NMS on the device; its kept rows are the boxes
+            res = model.run(x_dev, seed=int(config.get('seed', 0)), want_boxes=False)
+            boxes = res['rows'][0, :int(res['count'][0, 0])].cpu().numpy()
+        else:
+            model.run(x_dev, seed=int(config.get('seed', 0)), want_nms=False, out=out)
+            boxes = box_op(model).cpu().numpy()
         boxes = filter_boxes(boxes, model.obj_idx, thresh)
         boxes = preproces_boxes(img_size, boxes, model.obj_idx, model.cls_start_idx, model.cls_cnt,
                                 config, cls_mapping=cls_mapping)

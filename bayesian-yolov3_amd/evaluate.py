@@ -75,6 +75,14 @@ the predicted variances.  The pixel frame is the one the 'eval' split normalises
 dict gains 'pdq' and one line per result is logged: one run shows PDQ raw against recalibrated.  PDQ's `min_score` (0.5) is its
 own operating point; the evaluator's `min_score` does not enter it.
 
+`tta` (True or a dict of settings, as `engine_options['tta']`; INTEGRATION.md "Test-time augmentation"): the model runs every view --
+the frame mirrored and / or at a second size --, merges their rows in front of the NMS, and those rows are scored by an evaluator that
+holds the extended geometry (the detection layers of every size) and records `view_n` and `view_var_x .. _h` as further uncertainty
+columns: does the disagreement between views separate false positives?  With `tta_compare: True` the model runs plain, `TTA.run` runs
+beside it on every batch, and metrics.json carries the two result dicts under 'nms' and 'tta' (the ladder, the subsets and PDQ
+included when set), logged side by side per class.  `tta_compare` is refused together with any other `*_compare` (one comparison per
+run), `tta` together with any other `*_compare` and with `t_ladder`.  V views cost V forwards.
+
 `Model.run` -> `Evaluator.add` per batch (byolo/evaluate.py: one matching kernel per batch on the forward's stream); batches
 run one after the other (`Model.run` re-runs a batch that leaves the split-f16 range in fp32 by itself).  One process, one
 GPU: multi-GPU evaluation is out of scope.  Writes `<out_path>_<step>/metrics.json`: the dict of `Evaluator.finish`, the
@@ -180,6 +188,24 @@ def check_config(config, model='bayesian'):
             raise ValueError('score_recal_compare together with box_vote: the stage runs in front of the vote, the comparison could only run behind it')
         if srecal and not cfg['score_recal_compare']:                # the model recalibrates behind its NMS; the comparison beside the raw rows
             cfg['engine_options'] = dict(cfg.get('engine_options', {}), score_recal=srecal)
+    # tta / tta_compare: both keys stay absent when absent
+    if cfg.get('tta') is not None or cfg.get('tta_compare') is not None:
+        from byolo import tta as _tta
+        tta = cfg.setdefault('tta', None)
+        cfg.setdefault('tta_compare', False)
+        if cfg['tta_compare'] not in (True, False):
+            raise ValueError('tta_compare is True or False')
+        others = [k for k in sorted(cfg) if k.endswith('_compare') and k != 'tta_compare' and cfg[k]]
+        if cfg['tta_compare'] and others:
+            raise ValueError('tta_compare together with {}: one comparison per run'.format(', '.join(others)))
+        if cfg['tta_compare'] and not tta:
+            tta = cfg['tta'] = True                                  # the comparison alone: the default settings
+        if tta:
+            if others:
+                raise ValueError('tta together with {}: the comparison stages read one forward\'s rows, not a union of views'.format(', '.join(others)))
+            _tta.check_settings(tta, (cfg['crop_img_size'] if cfg['crop'] else cfg['full_img_size'])[:2])      # ValueError names the field
+            if not cfg['tta_compare']:                               # the model merges its views itself; the comparison runs them beside the plain forward
+                cfg['engine_options'] = dict(cfg.get('engine_options', {}), tta=tta)
     from byolo.evaluate import height_subsets, ladder_thresholds
     ladder_thresholds(cfg.get('iou_thresholds'))                    # ValueError on a bad ladder; both keys stay absent when absent
     height_subsets(cfg.get('eval_subsets'))                          # likewise; the rule's parameters stay absent without subsets
@@ -245,6 +271,8 @@ def check_config(config, model='bayesian'):
         others = [k for k in sorted(cfg) if k.endswith('_compare') and cfg[k]] + (['box_vote_sweep'] if cfg.get('box_vote_sweep') is not None else [])
         if others:
             raise ValueError('t_ladder together with {}: one comparison per run'.format(', '.join(others)))
+        if cfg.get('tta'):
+            raise ValueError('t_ladder together with tta: a rung is finished from ONE forward\'s workspace, a union has one forward per view')
         cfg['t_ladder'] = rungs
     cfg['training'] = False
     cfg['aleatoric_loss'] = False
@@ -291,8 +319,53 @@ def rung_tail(eng, model, boxes):
     return res
 
 
+VIEW_COLUMNS = ('view_n', 'view_var_x', 'view_var_y', 'view_var_w', 'view_var_h')
+
+
+class TtaEvaluator:
+    """The evaluator of rows that test-time augmentation produced (byolo/tta.py): an Evaluator with the EXTENDED geometry -- the ids of
+    merged rows index the detection layers of every size -- for the tables a plain evaluator fills, and a second one on the same rows
+    that records view_n and the four view_var as uncertainty columns (means over TP and FP, AUROC FP over TP: does the disagreement
+    between views separate false positives?).  The two match the same rows with the same rule; finish() is the first one's result
+    with the view columns added to 'uncertainty'."""
+
+    def __init__(self, model, tta, **options):
+        from byolo import eval_loc
+        from byolo.evaluate import Evaluator, uncertainty_columns, variant_of
+        D, C = int(model.engine.num_boxes()[1]), int(model.cls_cnt)
+        variant = variant_of(D, C)
+        ale_col, epi_col = {'yolov3': (-1, -1), 'yolov3_aleatoric': (4, -1), 'bayesian_yolov3_aleatoric': (8, 4)}[variant]
+        lay = dict(row_len=D + len(VIEW_COLUMNS), obj_idx=int(model.obj_idx), cls_start_idx=int(model.cls_start_idx), cls_cnt=C,
+                   det_layers=tta.geometry(), ale_col=ale_col, epi_col=epi_col)
+        ids = eval_loc.id_columns(variant, C)
+        if ids is not None:
+            lay['id_cols'] = ids
+        dev = model.engine.torch_device
+        self.main = Evaluator(dict(lay, unc_cols=uncertainty_columns(variant, C)), device=dev, **options)
+        self.views = Evaluator(dict(lay, unc_cols={name: D + k for k, name in enumerate(VIEW_COLUMNS)}, id_cols=None, det_layers=None), device=dev,
+                               iou_thresh=options.get('iou_thresh', 0.5), min_score=options.get('min_score', 0.0),
+                               capacity=options.get('capacity', 1 << 20), loc=False)
+
+    def add(self, res, gt_boxes, gt_labels, gt_counts):
+        """res: the dict of TTA.run."""
+        import torch
+        rows = torch.cat([res['rows'], res['view_n'].to(torch.float32).unsqueeze(-1), res['view_var']], dim=2).contiguous()
+        for e in (self.main, self.views):
+            e.add(rows, res['count'][:, 0], gt_boxes, gt_labels, gt_counts)
+
+    def finish(self):
+        out = self.main.finish()
+        out['uncertainty'].update(self.views.finish()['uncertainty'])
+        return out
+
+    def close(self):
+        self.main.close()
+        self.views.close()
+
+
 def score(model, feed, evaluator, seed=0, max_batches=None, points=None, vote=None, vote_evaluator=None, sweep=(), soft=None,
-          soft_evaluator=None, recal=None, recal_evaluator=None, score_cal=None, score_evaluator=None, t_ladder=()):
+          soft_evaluator=None, recal=None, recal_evaluator=None, score_cal=None, score_evaluator=None, t_ladder=(), tta=None,
+          tta_evaluator=None):
     """Model.run -> Evaluator.add over the batches of `feed` (the 'eval' split of lib_yolo.dataset_utils._Feed); returns the
     number of images.  points: a list that receives (time, images so far) after every batch.  vote (settings) and
     vote_evaluator: every batch's NMS rows are also voted (Engine.box_vote) and the voted rows scored by vote_evaluator.
@@ -302,14 +375,20 @@ def score(model, feed, evaluator, seed=0, max_batches=None, points=None, vote=No
     Engine.var_recal calibrates every batch's kept rows beside the raw ones and recal_evaluator scores them.  score_cal (a
     ScoreCalibration) and score_evaluator: likewise with Engine.score_recal.  t_ladder: [(sample count, evaluator)], increasing
     counts: Engine.t_ladder finishes every batch's pre-NMS rows at these counts right behind the forward, on the engine that ran
-    it, and each rung's rows go through rung_tail into its evaluator."""
+    it, and each rung's rows go through rung_tail into its evaluator.  tta (a byolo.tta.TTA on `model`) and tta_evaluator (a
+    TtaEvaluator): every batch also runs through tta.run and its rows are scored by tta_evaluator."""
     images = 0
     for step, b in enumerate(feed):
         if max_batches is not None and step >= max_batches:
             break
         res = model.run(b['img'], seed=seed + step, want_boxes=vote_evaluator is not None or soft_evaluator is not None)
-        evaluator.add(res['rows'], res['count'][:, 0], b['boxes'], b['labels'], b['counts'])
-        if t_ladder:                                      # (reads the forward's workspace: nothing forwards on this engine in between)
+        if getattr(model, 'tta', None) is not None:       # the model merged its views itself: `evaluator` is a TtaEvaluator
+            evaluator.add(res, b['boxes'], b['labels'], b['counts'])
+        else:
+            evaluator.add(res['rows'], res['count'][:, 0], b['boxes'], b['labels'], b['counts'])
+        if tta_evaluator is not None:                     # every view again beside the plain forward (view 0 draws the same masks)
+            tta_evaluator.add(tta.run(b['img'], seed=seed + step, want_boxes=False), b['boxes'], b['labels'], b['counts'])
+        if t_ladder:                                     # (reads the forward's workspace: nothing forwards on this engine in between)
             eng = res.get('engine', model.engine)
             slabs = eng.t_ladder([k for k, _ in t_ladder], int(b['img'].shape[0]), model.T)
             for slab, (_, rev) in zip(slabs, t_ladder):
@@ -450,7 +529,14 @@ def evaluate(config, model='bayesian'):
     os.makedirs(out_path)                                 # like the inference scripts: refuses to overwrite an existing run
     new_ev = lambda: Evaluator(m, iou_thresh=cfg['iou_thresh'], min_score=cfg['min_score'], capacity=cfg['eval_capacity'], loc=cfg['localisation'],
                                iou_thresholds=cfg.get('iou_thresholds'), **subset_options(cfg), **pdq_options(cfg))
-    ev = new_ev()
+    ev_opts = dict(iou_thresh=cfg['iou_thresh'], min_score=cfg['min_score'], capacity=cfg['eval_capacity'], loc=cfg['localisation'],
+                   iou_thresholds=cfg.get('iou_thresholds'), **subset_options(cfg), **pdq_options(cfg))
+    ev = new_ev() if m.tta is None else TtaEvaluator(m, m.tta, **ev_opts)      # rows of merged views: the extended geometry, the view_* columns
+    ev_tta, tta = None, None
+    if cfg.get('tta_compare'):
+        from byolo.tta import TTA
+        tta = TTA(m, cfg['tta'])
+        ev_tta = TtaEvaluator(m, tta, **ev_opts)
     ev_vote = new_ev() if cfg['box_vote_compare'] else None
     sweep = [(settings, new_ev()) for settings in (cfg.get('box_vote_sweep') or [])]
     ev_soft = new_ev() if cfg.get('soft_nms_compare') else None
@@ -474,8 +560,10 @@ def evaluate(config, model='bayesian'):
         points = []
         images = score(m, feed, ev, seed=int(cfg['seed']), max_batches=cfg['eval_batches'], points=points, vote=cfg['box_vote'],
                        vote_evaluator=ev_vote, sweep=sweep, soft=cfg.get('soft_nms'), soft_evaluator=ev_soft, recal=recal,
-                       recal_evaluator=ev_recal, score_cal=score_cal, score_evaluator=ev_score, t_ladder=rungs)
+                       recal_evaluator=ev_recal, score_cal=score_cal, score_evaluator=ev_score, t_ladder=rungs, tta=tta,
+                       tta_evaluator=ev_tta)
         metrics = ev.finish()
+        tta_metrics = ev_tta.finish() if ev_tta is not None else None
         rung_metrics = [dict(e.finish(), T=k) for k, e in rungs]
         score_metrics = ev_score.finish() if ev_score is not None else None
         recal_metrics = ev_recal.finish() if ev_recal is not None else None
@@ -488,6 +576,9 @@ def evaluate(config, model='bayesian'):
         ev.close()
         if ev_vote is not None:
             ev_vote.close()
+        if ev_tta is not None:
+            ev_tta.close()
+            tta.close()
         for _, e in sweep:
             e.close()
         if ev_soft is not None:
@@ -510,6 +601,17 @@ def evaluate(config, model='bayesian'):
         for c, v in zip(metrics['classes'], soft_metrics['classes']):
             logging.info('class {:3d}: AP at IoU {:.2f}: NMS rows {:.4f}, soft-NMS rows {:.4f}; LAMR {:.4f}, {:.4f}'.format(
                 c['class'], cfg['iou_thresh'], c['ap'], v['ap'], c['lamr'], v['lamr']))
+    if tta_metrics is not None:
+        for c, v in zip(metrics['classes'], tta_metrics['classes']):
+            logging.info('class {:3d}: plain rows AP {:.4f}, LAMR {:.4f}, ECE {:.4f}; TTA rows AP {:.4f}, LAMR {:.4f}, ECE {:.4f}'.format(
+                c['class'], c['ap'], c['lamr'], c['ece'], v['ap'], v['lamr'], v['ece']))
+        for name in VIEW_COLUMNS:
+            u = tta_metrics['uncertainty'][name]
+            logging.info('TTA rows: {:12s}: mean over TP {:.6g}, over FP {:.6g}, AUROC FP over TP {:.4f}'.format(name, u['tp']['mean'], u['fp']['mean'], u['auroc_fp']))
+        if 'subsets' in tta_metrics:
+            from byolo.evaluate import subset_lines
+            for line in subset_lines(tta_metrics['subsets']):
+                logging.info('TTA rows: ' + line)
     if voted_metrics is not None:
         for c, v in zip(metrics['classes'], voted_metrics['classes']):
             logging.info('class {:3d}: AP at IoU {:.2f}: NMS rows {:.4f}, voted rows {:.4f}'.format(c['class'], cfg['iou_thresh'], c['ap'], v['ap']))
@@ -520,9 +622,9 @@ def evaluate(config, model='bayesian'):
             name, u['tp']['mean'], u['tp']['finite'], u['tp']['nonfinite'], u['fp']['mean'], u['fp']['finite'], u['fp']['nonfinite'],
             u['auroc_fp']))
     if 'ladder' in metrics:
-        other = voted_metrics if voted_metrics is not None else soft_metrics
+        other = voted_metrics if voted_metrics is not None else soft_metrics if soft_metrics is not None else tta_metrics
         for line in ladder_lines(metrics['ladder'], other['ladder'] if other is not None else None,
-                                 names=('NMS rows', 'voted rows' if soft_metrics is None else 'soft-NMS rows')):
+                                 names=('NMS rows', 'TTA rows' if tta_metrics is not None else 'voted rows' if soft_metrics is None else 'soft-NMS rows')):
             logging.info(line)
     if 'subsets' in metrics:
         from byolo.evaluate import subset_lines
@@ -531,7 +633,7 @@ def evaluate(config, model='bayesian'):
     if 'pdq' in metrics:                                  # one line per result: raw against voted, recalibrated, every rung
         from byolo.pdq import log_line
         named = [('', metrics), ('box_vote rows: ', voted_metrics), ('soft-NMS rows: ', soft_metrics), ('var_recal rows: ', recal_metrics),
-                 ('score_recal rows: ', score_metrics)]
+                 ('score_recal rows: ', score_metrics), ('TTA rows: ', tta_metrics)]
         named += [('box_vote_sweep[{}]: '.format(k), r) for k, r in enumerate(sweep_metrics)]
         named += [('t_ladder T = {:3d}: '.format(r['T']), r) for r in rung_metrics]
         for prefix, r in named:
@@ -555,6 +657,9 @@ def evaluate(config, model='bayesian'):
     if soft_metrics is not None:                          # likewise: the hard NMS's result beside the soft-NMS's
         metrics = dict({k: v for k, v in metrics.items() if k not in soft_metrics}, nms={k: metrics[k] for k in soft_metrics},
                        soft_nms=soft_metrics)
+    if tta_metrics is not None:                           # likewise: the plain model's result beside the merged views'
+        metrics = dict({k: v for k, v in metrics.items() if k not in tta_metrics}, nms={k: metrics[k] for k in tta_metrics},
+                       tta=tta_metrics)
     if recal_metrics is not None:                         # likewise: the raw rows' result beside the recalibrated rows'
         metrics = dict({k: v for k, v in metrics.items() if k not in recal_metrics}, raw={k: metrics[k] for k in recal_metrics},
                        var_recal=recal_metrics)
@@ -569,6 +674,8 @@ def evaluate(config, model='bayesian'):
         json.dump(metrics, f, indent=1)
     elapsed = int(time.time() - start)
     logging.info('----- FINISHED in {:02d}:{:02d}:{:02d} -----'.format(elapsed // 3600, (elapsed // 60) % 60, elapsed % 60))
+    if m.tta is not None:
+        m.tta.close()
     m.engine.close()
     return metrics
 

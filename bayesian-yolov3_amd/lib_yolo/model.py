@@ -85,6 +85,12 @@ class ModelBuilder:
         self.__var_recal = opts.pop('var_recal', None)
         # 'score_recal': a path | dict | byolo.score_recal.ScoreCalibration: the kept rows' score recalibrated behind the NMS (Engine.set_score_recal)
         self.__score_recal = opts.pop('score_recal', None)
+        # 'tta': True | {'flip', 'sizes', 'iou_min', 'min_score'} | {'views': [...]}: test-time augmentation (byolo/tta.py) -- Model.run
+        # then runs every view and merges their rows in front of the NMS.  A bad setting is a ValueError naming the field, here.
+        self.__tta = opts.pop('tta', None)
+        if self.__tta is not None and self.__tta is not False:
+            from byolo import tta as _tta
+            _tta.check_settings(self.__tta, self.__input_size)
         self.engine = Engine(img_size=shape[1:], cls_cnt=cls_cnt, **opts)
         self.T = 1
 
@@ -121,7 +127,11 @@ class ModelBuilder:
             self.engine.set_var_recal(self.__var_recal)
         if self.__score_recal is not None:
             self.engine.set_score_recal(self.__score_recal)
-        return Model(self.__layers, self.__det_layers, self.__cls_cnt, obj_idx, cls_start_idx, builder=self)
+        m = Model(self.__layers, self.__det_layers, self.__cls_cnt, obj_idx, cls_start_idx, builder=self)
+        if self.__tta is not None and self.__tta is not False:
+            from byolo import tta as _tta
+            m.tta = _tta.TTA(m, self.__tta)
+        return m
 
     def __update_layers(self, index, name, kind):
         assert index == len(self.__layers), 'layer numbering out of sync with libbyolo'
@@ -262,6 +272,7 @@ class Model:
         self.last = None
         self.range_fallback = True          # run(): BYOLO_ERR_RANGE -> switch this model to the fp32 mode and re-run
         self.precision_switches = 0
+        self.tta = None                     # a byolo.tta.TTA (engine_options['tta']): run() is then its run()
         base = 0
         for dl in det_layers:
             dl._model = self
@@ -295,7 +306,12 @@ class Model:
         with `precision='f32'`.
         `slot`: workspace arena of the call (forwards in flight on different HIP streams must not share one).
         `t_shard` = (t0, t1): run samples t0 .. t1 - 1 of the image's T only and return their per-box SUMS in 'boxes' (the T axis
-        sharded over ranks, Engine.forward / include/byolo.h byolo_set_tshard; one image, no NMS)."""
+        sharded over ranks, Engine.forward / include/byolo.h byolo_set_tshard; one image, no NMS).
+        With engine_options['tta'] the call is byolo.tta.TTA.run: every view's rows merged in front of the NMS, the same keys plus
+        view_n / view_bits / view_score / view_var / view_off; `t_shard` is then a ValueError."""
+        if self.tta is not None:
+            return self.tta.run(img, T=self.T, seed=seed, dropout_on=dropout_on, want_boxes=want_boxes, want_nms=want_nms, first_image=first_image,
+                                out=out, mask_bits=mask_bits, slot=slot, precision=precision, t_shard=t_shard)
         if not self.engine.finalized:
             self.engine.finalize()
         kw = dict(T=self.T, seed=seed, dropout_on=dropout_on, want_boxes=want_boxes, want_nms=want_nms,

@@ -1029,6 +1029,58 @@ BYOLO_API size_t byolo_score_recal_fit_workspace_bytes(int64_t n, int32_t K);
 BYOLO_API int32_t byolo_score_recal_fit(const double* d_x, const double* d_y, const int64_t* d_seg, int32_t n_seg, int64_t n,
                                         int32_t K, double l2, int64_t min_n, double* d_out, void* d_ws, size_t ws_bytes, void* stream);
 
+/* ---- test-time augmentation (mirrored and rescaled views merged in front of the NMS; no counterpart in the reference;
+ * csrc/tta.hip; INTEGRATION.md "Test-time augmentation" has the definitions in full, tests/_tta_ref.py restates them) ----------
+ * A view is the same frame mirrored left-right and / or at a second size.  Every view's pre-NMS rows go into ONE candidate set
+ * per image, the union [B, Nu, D] with Nu = sum Nv and the views in order; byolo_sort_nms / byolo_soft_nms, byolo_box_vote and
+ * byolo_score_recal_apply then run on the union as on any rows.  byolo_forward is not involved: byolo/tta.py composes the stages.
+ * byolo_tta_view_f32: float32 frames d_in [B, src_h, src_w, 3] -> d_out [B, out_h, out_w, 3]: TF1's legacy bilinear resize
+ * (src = dst * in / out, no half-pixel offset; skipped when the sizes are equal) and the left-right flip of byolo_augment_batch,
+ * operation for operation: the bytes byolo_augment_batch writes for the whole uint8 frame whose * (1.0f / 255.0f) is d_in.  The same
+ * size with flip is a mirrored copy.  Handle-less (errors: byolo_last_error(NULL)); d_out must not overlap d_in; B < 1 is a no-op.
+ * byolo_tta_merge: one view's rows d_rows [B, Nv, D] -> rows row_off .. row_off + Nv - 1 of d_union [B, Nu, D]; the other rows of
+ * the union are not touched.  Boxes are normalised: a rescaled view needs no coordinate change.  flip: column 1 = 1.0f - column 3
+ * and column 3 = 1.0f - column 1 (one float32 rounding; a NaN keeps its bits); the variances of the raw location values and the
+ * 4 x 4 determinant do not change under t_x -> -t_x.  size_idx g (the view's size among the distinct sizes, 0 = the model's own):
+ * column layer_col gains 3 g as a float (exact; g = 0 and a non-finite id keep their bits), so that the ids of all views index ONE
+ * byolo_eval_loc_cfg of 3 n_sizes layers -- the geometry byolo_box_vote, the localisation residuals and the PDQ take for merged
+ * rows.  kind: BYOLO_DET_*, D = 5 + C / 14 + C / 21 + C with C in 1 .. 128; layer_col: -1 for standard rows (they have no ids),
+ * D - 2 otherwise.  Handle-less.  Refused with BYOLO_ERR_ARG, the argument named, before anything is launched: a D the kind cannot
+ * have, a layer_col that is not the kind's, row_off + Nv beyond Nu, a NULL or misaligned pointer, a union that overlaps the rows.
+ * B < 1 or Nv < 1 is a no-op.
+ * byolo_tta_support: behind the NMS on the union (d_kept / d_count of byolo_sort_nms or byolo_soft_nms on d_union with the same
+ * obj_idx / cls_start_idx / nms_mode).  The kept row k is the union row d_kept[b][k] (its box before any voting).  For every kept
+ * row of the d_count[b][0] real ones and every view v, the WITNESS is the union row i in view_off[v] .. view_off[v + 1] - 1 of the
+ * same image with: the class of k as the NMS decides it (a row of no class has no witness and is none); score >= min_score; four
+ * finite box values; IoU(k, i) > iou_min, the NMS's float32 IoU; among those the highest score, the lowest index on a tie.
+ *   d_view_n     [B, cap] int32   the number of views with a witness
+ *   d_view_bits  [B, cap] int32   bit v: view v has a witness
+ *   d_view_score [B, cap] float   the float64 sum of the witnesses' scores in view order, / n_views (an absent witness counts 0),
+ *                                 rounded once
+ *   d_view_var   [B, cap, 4] float the population variance over the witnesses of (cx, cy, w, h), cx = (x0 + x1) 0.5, w = x1 - x0
+ *                                 on the sorted corners: float64 on the float32 inputs, mean = sum / n in view order, then
+ *                                 sum (c - mean)^2 / n in view order (no fused multiply-add), rounded once; 0 for n <= 1
+ * all 0 in the padding (k >= count).  Deterministic; an image gives the same bytes at any position of any batch.
+ * iou_min = 0.5 and min_score = 0.001 are starting values that nobody has tuned.  Refused with BYOLO_ERR_ARG, the field named: a
+ * wrong struct_bytes, n_views outside 1 .. BYOLO_TTA_MAX_VIEWS, view_off not starting at 0, not ascending or beyond Nu, iou_min
+ * negative or NaN, min_score NaN; a workspace below byolo_tta_support_workspace_bytes(B, Nu) is BYOLO_ERR_NOMEM. */
+#define BYOLO_TTA_MAX_VIEWS 8
+typedef struct byolo_tta_support_cfg {
+    int32_t struct_bytes;          /* sizeof(byolo_tta_support_cfg) of the caller's header: a mismatch is BYOLO_ERR_ARG */
+    int32_t n_views;
+    float iou_min, min_score;
+    int32_t view_off[BYOLO_TTA_MAX_VIEWS + 1];
+} byolo_tta_support_cfg;
+BYOLO_API int32_t byolo_tta_view_f32(const float* d_in, int32_t B, int32_t src_h, int32_t src_w, int32_t flip, int32_t out_h,
+                                     int32_t out_w, float* d_out, void* stream);
+BYOLO_API int32_t byolo_tta_merge(const float* d_rows, int32_t B, int64_t Nv, int32_t D, int32_t kind, int32_t layer_col, int32_t flip,
+                                  int32_t size_idx, float* d_union, int64_t Nu, int64_t row_off, void* stream);
+BYOLO_API size_t byolo_tta_support_workspace_bytes(int32_t B, int64_t Nu);
+BYOLO_API int32_t byolo_tta_support(byolo_t* h, const float* d_union, int32_t B, int64_t Nu, int32_t D, int32_t obj_idx,
+                                    int32_t cls_start_idx, int32_t nms_mode, const byolo_tta_support_cfg* cfg, const int32_t* d_kept,
+                                    const int32_t* d_count, int32_t cap, int32_t* d_view_n, int32_t* d_view_bits, float* d_view_score,
+                                    float* d_view_var, void* d_ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
